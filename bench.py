@@ -8,9 +8,10 @@ in the post-burn-in range and is accumulated into the per-chain running sums (KL
 `klara_run` IS the `for i in 1:nsteps` loop (BasicMCJob.jl:219-238): the library's default of 32 transitions per kernel launch is
 the headline (config.steps_per_launch), one transition per launch is reported in `extra`.
 
-Timed region: `--reps` (5) repetitions of exactly `--steps` transitions, each bracketed by a barrier + torch.cuda.synchronize()
-on both sides; a rank's time runs from leaving the opening barrier to its own synchronize() after the K steps, the repetition's
-time is the MAX over ranks (the closing barrier's own latency is not part of any rank's K steps); `value` uses the MEDIAN repetition.  With --gpus N every rank owns its own shard
+Timed region: exactly `--steps` transitions (K) after `--warmup` ones, bracketed by a barrier + torch.cuda.synchronize() on both sides; a
+rank's time runs from leaving the opening barrier to its own synchronize() after the K steps, the region's time is the MAX over ranks (the
+closing barrier's own latency is not part of any rank's K steps).  `--reps R` times R such regions one after the other and `value` uses the
+MEDIAN (the job then runs R x K timed transitions).  With --gpus N every rank owns its own shard
 (weak scaling: 65,536 chains per GPU, global chain ids = rank * 65,536 + local; `--scaling strong`: `--total-chains` sharded over
 the ranks), no data-path collective; the only exchange is the end-of-run reduction of the chain summaries — pooled on the device
 and, for N > 1, all-reduced over RCCL THROUGH THE LIBRARY'S OWN C ABI (`--collective klara`, the default: rank 0 calls
@@ -21,7 +22,9 @@ path a Julia binding calls, include/klara_hip.h) — once, after the job's last 
 transitions short).  `--collective torch` gathers through the Python mirror instead (klara.jl_amd/distributed.py: device ->
 NumPy -> torch.distributed.all_reduce over `--torch-backend`), `--collective both` times the two side by side.
 
-Prints ONE JSON line (rank 0).  Keys beyond the driver's contract:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`) with its `config`; `--dump-outputs DIR` also writes what the timed job hands back after its last
+step (dump_outputs below).  `--full` adds the measurements the headline does not need, each with runs of its own:
   roofline      the dominant transition kernel.  `bound` = "valu": the kernel is bound by vector-ALU issue (in-kernel Philox +
                 Box-Muller), HBM moves a few per cent of its peak (`hbm`).  `frac` is ALGORITHMIC: `achieved` = the vector
                 instructions the algorithm needs per launch (scripts/instruction_budget.py: one count per operation of the stream
@@ -33,7 +36,8 @@ Prints ONE JSON line (rank 0).  Keys beyond the driver's contract:
                 from the ones the counters were collected on.  `hbm` gives the byte side: SURVEY section 8(d)'s contract bytes,
                 the bytes this kernel has to move, the PMC traffic and the fraction of 8 TB/s each amounts to.
   cpu_baseline  the CPU oracle ("port" of the reference path, OpenMP over chains) on a bounded sample of the same workload
-  extra         the other configurations, each with its own {bound, frac, kernel, source} object
+                (one rank only; `--no-cpu-baseline` leaves it out)
+  extra         the other configurations, each with its own {bound, frac, kernel, source} object (one rank only; `--no-extra` leaves them out)
 """
 import argparse
 import json
@@ -56,6 +60,31 @@ NSIMD = 1024
 # library itself, on the device, launch by launch (klara_desc.sparse_moves = 0): no caller hint.
 PMC_JSON = ROOT / "profiles" / "r6_pmc_kernels.json"
 PMC_EXPECT = {}             # filled by main(): the launch length the committed counters must have been collected at
+DUMP_BUDGET_BYTES = 64 * 10 ** 6    # --dump-outputs: at most this many bytes of .npy data in all
+DUMP_MAX_CHAINS = 16384             # ... and the per-chain arrays of at most this many chains (65,536 chains x 403 doubles would be 211 MB)
+DUMP_SEED = 20261015                # the fixed sample of chains a larger job is dumped for
+
+
+def dump_outputs(out_dir, per_chain, pooled, chain_ids, max_chains=DUMP_MAX_CHAINS, seed=DUMP_SEED):
+    """--dump-outputs: `per_chain` arrays (chain on the first axis) for a fixed, seeded sample of the chains — every chain of a job that fits
+    — with the global ids of the sampled chains as `chain_index`, and `pooled` arrays whole; one float64 DIR/<name>.npy each, within
+    DUMP_BUDGET_BYTES.  The same job gives the same sample, so two builds can be compared array for array.  Returns the names written."""
+    import numpy as np
+    pooled = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in pooled.items()}
+    per_chain = dict(chain_index=np.asarray(chain_ids), **per_chain)
+    n = len(per_chain["chain_index"])
+    row_bytes = sum(8 * int(np.prod(np.shape(v)[1:], dtype=np.int64)) for v in per_chain.values())
+    headers = 4096 * (len(per_chain) + len(pooled))           # (room for the .npy headers, 128 bytes each in practice)
+    cap = min(max_chains, (DUMP_BUDGET_BYTES - headers - sum(v.nbytes for v in pooled.values())) // row_bytes)
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    arrays = {k: np.ascontiguousarray(np.asarray(v)[rows], dtype=np.float64) for k, v in per_chain.items()}
+    arrays.update(pooled)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(out_dir / f"{k}.npy", v)
+    assert sum((out_dir / f"{k}.npy").stat().st_size for k in arrays) <= DUMP_BUDGET_BYTES
+    return sorted(arrays)
 
 
 def budgets():
@@ -146,7 +175,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1024)
     ap.add_argument("--warmup", type=int, default=128)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed region; the median is reported")
+    ap.add_argument("--reps", type=int, default=1, help="timed regions of --steps transitions each, one after the other; the median is reported")
     ap.add_argument("--spl", type=int, default=0, help="transitions per kernel launch (0 = library default 32; 1 = one iterate! per launch)")
     ap.add_argument("--chains", type=int, default=NCHAINS_PER_GPU, help="chains per GPU (weak scaling)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
@@ -157,8 +186,13 @@ def main():
                     help="transitions of an identical scratch job run straight before the timed repetitions so that the device clocks "
                          "are at their steady state (0 = off); the measured job gets exactly --warmup steps")
     ap.add_argument("--no-save", action="store_true", help="drop the save rule (no running sums): the transition kernel alone")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the roofline pass of the dominant kernel, the other configurations (extra) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed job hands back after its last step as DIR/<name>.npy (float64; a fixed, seeded sample of the chains, "
+                         f"at most {DUMP_BUDGET_BYTES // 10 ** 6} MB in all)")
     ap.add_argument("--collective", choices=("klara", "torch", "both"), default="klara",
                     help="the job's one exchange (summary gather): klara = the library's own RCCL communicator behind the C ABI "
                          "(klara_comm_init / klara_gather_moments); torch = the Python mirror over torch.distributed; both = klara, then torch for the A/B")
@@ -337,6 +371,19 @@ def main():
                      "max_rel_mean_var_difference": (float(max(np.max(np.abs(summ_t["mean"] - summ["mean"]) / (np.abs(summ["mean"]) + 1e-300)),
                                                                np.max(np.abs(summ_t["var"] - summ["var"]) / summ["var"])))
                                                      if "var" in summ and "var" in summ_t else None)}
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the timed job hands back after its last step: its state (klara_get_state), the per-chain accept counts and running sums of
+        # mean(chain), and the summaries of the job's one exchange (pooled over every rank; the per-chain arrays are rank 0's chains)
+        x, lt, g = eng.state()
+        per_chain = {"x": x, "logtarget": lt, "gradlogtarget": g, "accept_count": eng.accept_counts()[0]}
+        if monitor:
+            s, q, _ = eng.chain_sums()
+            per_chain.update(chain_sum=s, chain_sumsq=q)
+        pooled = {"summary_counts": [summ["nsamples"], summ["naccept"], summ["ntransitions"]]}
+        pooled.update({f"summary_{k}": summ[k] for k in ("mean", "var") if k in summ})
+        dumped = dump_outputs(args.dump_outputs, per_chain, pooled, offset + np.arange(n))
+        del x, lt, g, per_chain
     lay_kind, lay_g, lay_e = eng.layout()
     launch_counts = eng.launch_modes()[0] if hasattr(L.load(), 'klara_get_launch_modes') else [0, 0, 0]
     acc_rate = float(summ["acceptance"]) if summ is not None and "acceptance" in summ else None
@@ -374,7 +421,8 @@ def main():
                                       "ranks_by_transition_count": ranks_by_count, "error": collective_error, "torch_group_error": tgroup_error,
                                       "ab": gather_ab},
                        "streams": "library default (2 chain partitions on 2 HIP streams)" if args.streams == 0 else args.streams,
-                       "timed_region": f"median of {args.reps} repetitions of {args.steps} transitions",
+                       "timed_region": (f"median of {args.reps} repetitions of {args.steps} transitions" if args.reps > 1 else
+                                        f"{args.steps} transitions after {args.warmup} warm-up transitions"),
                        "repetition_ms_per_step": [t_ * 1e3 / args.steps for t_ in times],
                        "per_rank_ms_per_step": [statistics.median(rt[r] for rt in rank_times) * 1e3 / args.steps for r in range(world)],
                        "rank_time_max_over_min": max(statistics.median(rt[r] for rt in rank_times) for r in range(world))
@@ -384,11 +432,14 @@ def main():
                        "timed_region_kernel_ms_per_step": statistics.median(kernel_ms_per_step),
                        "repetition_kernel_ms_per_step": kernel_ms_per_step},
         }
+        if dumped is not None:
+            out["config"]["dump_outputs"] = dumped
     eng.close()
     if comm is not None:
         comm.close()
 
-    if rank == 0:
+    # -- --full: what the headline figure does not need, each measured in runs of its own after the timed job is gone
+    if rank == 0 and args.full:
         out["roofline"] = rf = roofline_pass(K, L, n, spl, monitor, offset, local_rank, stream)
         # the same fraction over the TIMED REGION itself (HIP events around each repetition's K steps on this rank): there the library runs
         # the job as two chain partitions on two streams whose kernels overlap, so no single launch has a duration of its own — work / elapsed
@@ -398,9 +449,9 @@ def main():
             rf["frac_timed_region_source"] = ("necessary vector instructions per transition of this rank's chains x 4 / (klara_last_run_ms over the timed "
                                               "repetitions / steps) / peak: multi-launch runs overlap two chain partitions on two streams (a launch's ramp, its last "
                                               "round of wavefronts and the gap to the next launch are filled by the other partition), `frac` prices one launch alone")
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         out["extra"] = extra_measurements(K, L, n, stream)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(L)
     if rank == 0:
         print(json.dumps(out))

@@ -70,7 +70,7 @@ try:
             loaded[pm["key"]] = [pm["loaded_vgpr"], pm["loaded_scratch"]]
 except Exception as exc:
     loaded = {"error": repr(exc)}
-out = {"bench_config": bench_cfg, "loaded_kernel_attributes": loaded, "headline_kernel_trace": trace, "source": "rocprofv3 --pmc passes of scripts/profile_round.sh (bench.py --steps 64 --warmup 16 --reps 1 --no-cpu-baseline), one counter "
+out = {"bench_config": bench_cfg, "loaded_kernel_attributes": loaded, "headline_kernel_trace": trace, "source": "rocprofv3 --pmc passes of scripts/profile_round.sh (bench.py --full --steps 64 --warmup 16 --reps 1 --no-cpu-baseline), one counter "
                  "group per run, --kernel-trace only; means per WORKING dispatch (a counter's values below 5 % of its maximum — the early returns of the idle sibling of device-decided launches — are dropped and counted in n_dropped_early_returns), chip totals (GRBM_GUI_ACTIVE: sum over the 8 XCDs); "
                  "FETCH_SIZE / WRITE_SIZE in KiB as reported (FETCH_SIZE is doubled by the reader, see profiles/README.md)",
        "kernels": rows}

@@ -264,7 +264,7 @@ def test_bench_two_ranks_on_one_device_logic():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            str(root / "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--reps", "3", "--backend", "gloo", "--same-device",
-           "--no-extra", "--no-cpu-baseline", "--clock-warmup", "0"]
+           "--full", "--no-extra", "--no-cpu-baseline", "--clock-warmup", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -303,14 +303,14 @@ def test_bench_starts_its_own_ranks_without_a_launcher():
 
 
 def test_bench_single_gpu_line_at_the_drivers_flags():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` as the driver runs it (extras and CPU baseline off to keep the test short): one JSON
-    line, the contract's keys, value = chains x steps / time, a VALU roofline below 1 whose launch duration was measured in this run."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5` as the driver runs it, with `--full` for the roofline pass (extras and CPU baseline off to keep
+    the test short): one JSON line, the contract's keys, value = chains x steps / time, a VALU roofline below 1 whose launch duration was measured in this run."""
     import json
     import subprocess
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-extra", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-extra", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -324,6 +324,48 @@ def test_bench_single_gpu_line_at_the_drivers_flags():
     # frac is algorithmic: the instruction budget of the kernel that ran x 4 issue cycles / (launch duration x 1024 SIMDs x 2.4 GHz)
     assert rf["frac"] == pytest.approx(4.0 * rf["necessary_valu_insts_per_launch"] / (rf["launch_us"] * 1e-6) / (1024 * 2.4e9), rel=1e-9)
     assert rf["pmc"]["stale"] in (None, False, True) and (rf["utilisation"] is None or rf["frac"] <= rf["utilisation"] <= 1.0)
+
+
+def test_bench_plain_line_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR`, twice: the plain line holds the headline and its config and nothing that
+    needs runs of its own (no roofline, extra or CPU baseline); the job ran exactly warm-up + steps transitions; DIR holds float64 arrays within
+    64 MB — the final state of a fixed sample of chains (lt = -|x|^2, gradient -2x), their accept counts and running sums, the pooled summaries —
+    and the second run, same arguments, hands back the same state bit for bit."""
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    dumps = []
+    for k in range(2):
+        d_out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(d_out)],
+                           capture_output=True, text=True, timeout=600, cwd=str(root))
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert (d["n_gpus"], d["steps"], d["warmup"], d["higher_is_better"], d["dtype"], d["unit"]) == (1, 20, 5, True, "f64", "transitions/s")
+        assert d["value"] == pytest.approx(65536 * 20 / (d["ms_per_step"] * 20e-3), rel=1e-9) and d["value"] > 1e9
+        assert not {"roofline", "extra", "cpu_baseline"} & set(d)
+        assert d["config"]["collective"]["ranks_by_transition_count"] == pytest.approx(1.0)        # ntransitions / ((5 + 20) x 65,536)
+        assert len(d["config"]["repetition_ms_per_step"]) == 1 and d["config"]["repetition_ms_per_step"][0] == pytest.approx(d["ms_per_step"])
+        files = {p.stem: p for p in d_out.glob("*.npy")}
+        assert set(d["config"]["dump_outputs"]) == set(files) and sum(p.stat().st_size for p in files.values()) <= 64 * 10 ** 6
+        a = {k_: np.load(p) for k_, p in files.items()}
+        assert all(v.dtype == np.float64 for v in a.values())
+        idx = a["chain_index"]
+        assert len(idx) == 16384 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 65536
+        assert a["x"].shape == (16384, 100) and a["gradlogtarget"].shape == (16384, 100) and a["chain_sum"].shape == (16384, 100)
+        assert np.allclose(a["logtarget"], -(a["x"] ** 2).sum(axis=1), rtol=1e-12, atol=1e-12)
+        assert np.allclose(a["gradlogtarget"], -2.0 * a["x"], rtol=1e-14, atol=0.0)
+        assert np.all(a["accept_count"] <= 25) and a["summary_counts"][2] == 25 * 65536
+        assert a["summary_mean"].shape == (100,) and np.all(a["summary_var"] > 0)
+        dumps.append(a)
+    for k_ in ("chain_index", "x", "logtarget", "gradlogtarget", "accept_count", "summary_counts"):
+        assert np.array_equal(dumps[0][k_], dumps[1][k_]), k_
+    for k_ in ("chain_sum", "chain_sumsq", "summary_mean", "summary_var"):
+        assert np.allclose(dumps[0][k_], dumps[1][k_], rtol=1e-12, atol=1e-12), k_
 
 
 def test_bench_gathers_through_the_librarys_own_communicator():
