@@ -67,12 +67,21 @@ typedef enum klara_status {
     KLARA_ERR_COMPILE = 8          /* CUSTOM target: the user's source did not compile (klara_compile_log) */
 } klara_status;
 
-/* src/samplers/{MH,MALA,HMC,SliceSampler}.jl */
+/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA}.jl */
 typedef enum klara_sampler {
     KLARA_SAMPLER_MH = 0,      /* MH(sigma): symmetric normal random walk, MH.jl:63-66            */
     KLARA_SAMPLER_MALA = 1,    /* MALA(driftstep), MALA.jl:61-70                                   */
     KLARA_SAMPLER_HMC = 2,     /* HMC(leapstep, nleaps), HMC.jl:89-100                             */
-    KLARA_SAMPLER_SLICE = 3    /* SliceSampler(widths, stepout), SliceSampler.jl:22-34             */
+    KLARA_SAMPLER_SLICE = 3,   /* SliceSampler(widths, stepout), SliceSampler.jl:22-34             */
+    /* SMMALA(driftstep) (transform = nothing), SMMALA.jl:127-137: MALA with the position-dependent metric G(x) of the target —
+     * for KLARA_TARGET_LOGISTIC with D <= 8 on the row-split kernels, G = X' diag(r (1 - r)) X + I / lambda
+     * (doc/examples/swiss/SMMALA/analytical.jl:20-23).  Draws exactly what MALA draws (D normals and one accept uniform per
+     * transition); C = L^-T with G = L L' in place of chol(inv(G))', and a proposal whose metric is not positive definite is
+     * rejected.  Also KLARA_TARGET_CUSTOM in the plain whole-vector form with D <= 8, one chain per lane, whose source
+     * defines KLARA_USER_FN void klara_user_tensorlogtarget(const double* x, int D, const double* data, long long ndata, double* G) (the
+     * metric, row-major D x D; a source without it is KLARA_ERR_COMPILE).  Every other target (the likelihood + prior form and pair closures
+     * included), and D >= 9, is KLARA_ERR_UNSUPPORTED. */
+    KLARA_SAMPLER_SMMALA = 4
 } klara_sampler;
 
 /* Target families evaluated on device (stand-ins for the user closures of
@@ -175,7 +184,7 @@ typedef struct klara_desc {
 
     /* sampler parameters */
     const double* mh_sigma;      /* MH: proposal std-devs, D doubles (MH.jl:63: MvNormal(x, sigma))   */
-    double   driftstep;          /* MALA (MALA.jl:65: > 0)                                           */
+    double   driftstep;          /* MALA (MALA.jl:65: > 0), SMMALA (SMMALA.jl:132: > 0)               */
     double   leapstep;           /* HMC  (HMC.jl:94: > 0)                                            */
     int32_t  nleaps;             /* HMC  (HMC.jl:95: > 0)                                            */
     int32_t  slice_stepout;      /* SliceSampler.stepout                                             */

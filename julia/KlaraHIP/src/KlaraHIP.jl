@@ -29,7 +29,7 @@
 # `finalizer(f, obj)`): the three differences are confined to the compatibility block below, everything else is common syntax.
 module KlaraHIP
 import Klara
-import Klara: output, MCJob, MH, MALA, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
+import Klara: output, MCJob, MH, MALA, SMMALA, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
               BasicContMuvParameterState, BasicContMuvParameterNState, erf_rate_score, logistic_rate_score,
               Parameter, GenericModel, VariableState, VariableStateVector
 import Distributions
@@ -53,6 +53,7 @@ end
 # ---------------------------------------------------------------- constants of include/klara_hip.h
 const KLARA_ABI_VERSION = UInt32(6)
 const SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE = Int32(0), Int32(1), Int32(2), Int32(3)
+const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothing; the logistic target with D <= 8
 const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
@@ -167,6 +168,7 @@ rowmajor(A::Matrix{Float64}) = collect(transpose(A))       # Julia is column-maj
 
 # Klara's structs -> klara_desc.  Field names read from Klara (file:line in /root/reference/src):
 #   MALA.driftstep                         samplers/MALA.jl:61-70
+#   SMMALA.driftstep (transform = nothing) samplers/SMMALA.jl:127-137
 #   HMC.leapstep, HMC.nleaps               samplers/HMC.jl:89-100
 #   SliceSampler.widths, .stepout          samplers/SliceSampler.jl:22-34
 #   MH.setproposal (sigma is inside the closure: MH(sigma) = MH(x -> MvNormal(x, sigma)))   samplers/MH.jl:46-66
@@ -214,7 +216,10 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
                            :steps_per_launch => steps_per_launch, :bm_batchlen => bm_batchlen,
                            :nsteps => mcrange.nsteps, :burnin => mcrange.burnin, :thinning => mcrange.thinning)
     # --- sampler
-    if isa(sampler, MALA)
+    if isa(sampler, SMMALA)                                 # samplers/SMMALA.jl:127-137; the metric is the target's (LogisticTarget)
+        sampler.transform === nothing || error("SMMALA: a transform of the metric (e.g. softabs) is not run on the device")
+        kw[:sampler] = SAMPLER_SMMALA; kw[:driftstep] = Float64(sampler.driftstep)
+    elseif isa(sampler, MALA)
         kw[:sampler] = SAMPLER_MALA; kw[:driftstep] = Float64(sampler.driftstep)
     elseif isa(sampler, HMC)
         kw[:sampler] = SAMPLER_HMC; kw[:leapstep] = Float64(sampler.leapstep); kw[:nleaps] = Int32(sampler.nleaps)
@@ -228,7 +233,7 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         sig = sqrt.(Distributions.var(prop)); push!(keep, sig)
         kw[:sampler] = SAMPLER_MH; kw[:mh_sigma] = pointer(sig)
     else
-        error("sampler $(typeof(sampler)) is not on the device path (MH, MALA, HMC, SliceSampler are)")
+        error("sampler $(typeof(sampler)) is not on the device path (MH, MALA, SMMALA, HMC, SliceSampler are)")
     end
     # --- tuner
     tn = tuner === nothing ? VanillaMCTuner() : tuner

@@ -21,7 +21,7 @@ LOGIT_MAX_LDS_DOUBLES = 18432     # KLARA_LOGIT_MAX_LDS_DOUBLES
 # klara_status
 OK, ERR_INVALID_ARG, ERR_NONFINITE_INIT, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_STATE, ERR_SLICE_STUCK, ERR_COMPILE = range(9)
 # klara_sampler
-SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE = range(4)
+SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE, SAMPLER_SMMALA = range(5)
 # klara_target
 TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = range(5)
 # klara_tuner / mode

@@ -70,6 +70,19 @@ class MALA(MCSampler):
         self.driftstep = float(driftstep)
 
 
+class SMMALA(MCSampler):
+    """SMMALA(driftstep=1., transform=nothing) — SMMALA.jl:127-137.  The metric is the target's tensorlogtarget: on the device the
+    logistic regression with D <= 8 (X' diag(r (1 - r)) X + I / lambda, doc/examples/swiss/SMMALA/analytical.jl:20-23).  A
+    `transform` of the metric (e.g. softabs) is not run on the device and is refused."""
+    kind = L.SAMPLER_SMMALA
+
+    def __init__(self, driftstep: float = 1.0, transform=None):
+        assert driftstep > 0, "Drift step is not positive"
+        if transform is not None:
+            raise NotImplementedError("SMMALA: a transform of the metric (e.g. softabs) is not supported on the device")
+        self.driftstep, self.transform = float(driftstep), None
+
+
 class HMC(MCSampler):
     """HMC(leapstep=0.1, nleaps=10) — HMC.jl:89-100."""
     kind = L.SAMPLER_HMC
@@ -425,7 +438,7 @@ class BasicMCJob:
         self.bm_batchlen, self.acov_maxlag = int(bm_batchlen), int(acov_maxlag)
         if isinstance(sampler, MH):
             kw["mh_sigma"] = sampler.sigma
-        elif isinstance(sampler, MALA):
+        elif isinstance(sampler, (MALA, SMMALA)):
             kw["driftstep"] = sampler.driftstep
         elif isinstance(sampler, HMC):
             kw["leapstep"], kw["nleaps"] = sampler.leapstep, sampler.nleaps

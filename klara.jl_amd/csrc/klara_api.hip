@@ -288,12 +288,22 @@ static klara_status select_layout(const klara_desc& d, int* kind, int* G, int* E
     return KLARA_OK;
 }
 
+// SMMALA (KLARA_SAMPLER_SMMALA), D <= 8 on the group layout (E = 2 / 4 / 8): the logistic target (kinds 0 / 2) and a user-defined target in the
+// plain whole-vector form, one chain per lane, whose source defines klara_user_tensorlogtarget (the likelihood + prior form and pair closures are not taken)
+static bool smmala_custom_source(const char* src) { return src != nullptr && !pair_source(src) && !custom_lik_prior(src); }
+static bool smmala_eligible(const klara_desc& d)
+{
+    if (d.ndims > 8) return false;
+    if (d.target == KLARA_TARGET_LOGISTIC) return !logit_mfma_eligible(d);
+    return d.target == KLARA_TARGET_CUSTOM && smmala_custom_source(d.custom_src);
+}
+
 static klara_status validate(const klara_desc* d)
 {
     if (!d) return KLARA_ERR_INVALID_ARG;
     if (d->struct_size != sizeof(klara_desc) || d->abi_version != KLARA_ABI_VERSION) return KLARA_ERR_INVALID_ARG;
     if (d->nchains <= 0 || d->ndims <= 0 || d->chain_offset < 0) return KLARA_ERR_INVALID_ARG;
-    if (d->sampler < KLARA_SAMPLER_MH || d->sampler > KLARA_SAMPLER_SLICE) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler < KLARA_SAMPLER_MH || d->sampler > KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
     if (d->target < KLARA_TARGET_GAUSS_DIAG || d->target > KLARA_TARGET_CUSTOM) return KLARA_ERR_INVALID_ARG;
     if (d->tuner < KLARA_TUNER_VANILLA || d->tuner > KLARA_TUNER_DUAL_AVERAGING) return KLARA_ERR_INVALID_ARG;
     if (d->tuner == KLARA_TUNER_DUAL_AVERAGING) {                // DualAveragingMCTuner.jl:65-70
@@ -315,6 +325,7 @@ static klara_status validate(const klara_desc* d)
         for (int i = 0; i < d->ndims; ++i) if (!(d->mh_sigma[i] > 0.0)) return KLARA_ERR_INVALID_ARG;
         break;
     case KLARA_SAMPLER_MALA:                                     // MALA.jl:65
+    case KLARA_SAMPLER_SMMALA:                                   // SMMALA.jl:132 "Drift step is not positive"
         if (!(d->driftstep > 0.0)) return KLARA_ERR_INVALID_ARG;
         break;
     case KLARA_SAMPLER_HMC:                                      // HMC.jl:94-95
@@ -538,6 +549,8 @@ extern "C" klara_status klara_create(const klara_desc* desc, klara_handle** out)
     *out = nullptr;
     klara_status st = validate(desc);
     if (st != KLARA_OK) return st;
+    // SMMALA runs on the row-split logistic kernels only (D <= 8, the rows in LDS); every other job of it is refused before anything is allocated
+    if (desc->sampler == KLARA_SAMPLER_SMMALA && !smmala_eligible(*desc)) return KLARA_ERR_UNSUPPORTED;
     // the logistic regression beyond 16 parameters — or beyond 8 when its rows, padded to 16 columns, do not fit the LDS — runs as a closure
     if (desc->target == KLARA_TARGET_LOGISTIC && !logit_mfma_eligible(*desc) &&
         (desc->ndims > 16 || (desc->ndims > 8 && (size_t)desc->logit_ndata * 17 > KLARA_LOGIT_MAX_LDS_DOUBLES))) {
@@ -585,6 +598,7 @@ static klara_status create_impl(const klara_desc* desc, klara_handle** out, int 
     st = select_layout(*desc, &kind, &G, &E, custom_lanes, &custom_wpb);
     if (st != KLARA_OK) return st;
     if (desc->tuner_mode == KLARA_TUNE_POOLED && desc->sampler == KLARA_SAMPLER_SLICE) return KLARA_ERR_UNSUPPORTED;
+    if (desc->sampler == KLARA_SAMPLER_SMMALA && G != 1) return KLARA_ERR_UNSUPPORTED;     // (one chain per lane: KLARA_CUSTOM_LANES may ask for more)
     // the logistic kernels keep the data rows (padded to E columns, + the responses) in LDS next to the 8 KB of math tables: up to
     // 144 KB of the CU's 160 (swiss: 200 x 5 doubles = 8 KB); beyond the 56 KB a launch gets by default the launchers raise the
     // kernel's limit, and fewer workgroups share a CU
@@ -688,7 +702,7 @@ static klara_status create_impl(const klara_desc* desc, klara_handle** out, int 
         if (desc->monitor & KLARA_MON_HIST_LT) CKH(dalloc(&h->hist_lt, (size_t)h->hist_cols * N));
         if (desc->monitor & KLARA_MON_HIST_LLLP) { CKH(dalloc(&h->hist_ll, (size_t)h->hist_cols * N)); CKH(dalloc(&h->hist_lp, (size_t)h->hist_cols * N)); }
         if (desc->monitor & KLARA_MON_HIST_GRAD) {
-            if (desc->sampler != KLARA_SAMPLER_MALA && desc->sampler != KLARA_SAMPLER_HMC) {
+            if (desc->sampler != KLARA_SAMPLER_MALA && desc->sampler != KLARA_SAMPLER_HMC && desc->sampler != KLARA_SAMPLER_SMMALA) {
                 free_all(h); delete h; return KLARA_ERR_INVALID_ARG;   // no gradient is carried by MH / slice
             }
             CKH(dalloc(&h->hist_g, (size_t)h->hist_cols * N * D));
@@ -823,7 +837,7 @@ static KParams make_params(klara_handle* h)
     p.da_kappa = d.da_kappa; p.da_t0 = d.da_t0;
     // sampler_state(..., tuner::DualAveragingMCTuner): lambda = nleaps*leapstep, mu = log(10*step) (HMC.jl:124-133,192-213)
     p.da_lambda = (double)d.nleaps * d.leapstep; p.da_mu = kd_log(10.0 * d.leapstep);
-    p.step0 = d.sampler == KLARA_SAMPLER_MH ? 1.0 : d.sampler == KLARA_SAMPLER_MALA ? d.driftstep
+    p.step0 = d.sampler == KLARA_SAMPLER_MH ? 1.0 : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
             : d.sampler == KLARA_SAMPLER_HMC ? d.leapstep : (double)NAN;
     p.sqrt_step0 = std::sqrt(p.step0); p.inv_step0 = 1.0 / p.step0;
     p.burnin = d.burnin; p.thinning = d.thinning; p.nsteps_total = d.nsteps;
@@ -960,7 +974,7 @@ static klara_status init_common(klara_handle* h)
     h->acov_n = 0;
     // tuner_state: samplers.jl:29-45 — step per sampler, accepted = proposed = 0, totproposed = period
     const double step0 = d.sampler == KLARA_SAMPLER_MH ? 1.0
-                       : d.sampler == KLARA_SAMPLER_MALA ? d.driftstep
+                       : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
                        : d.sampler == KLARA_SAMPLER_HMC ? d.leapstep : (double)NAN;
     hipLaunchKernelGGL(k_fill_tune, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, st, h->tune_step,
                        h->tune_acc, h->tune_prop, h->tune_tot, NT, step0, (long long)d.period);
@@ -970,7 +984,7 @@ static klara_status init_common(klara_handle* h)
                            d.da_eps0bar, d.da_h0bar);
         HIPCHK(hipGetLastError());
     }
-    const int needgrad = d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_HMC;
+    const int needgrad = d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_HMC || d.sampler == KLARA_SAMPLER_SMMALA;
     KParams p = make_params(h);
     hipError_t e;
     if (h->kind == 1) e = klara_launch_dense_init(p, h->E, h->Pfrag, h->dense_mu, needgrad, grid_for(h), st);
@@ -983,6 +997,7 @@ static klara_status init_common(klara_handle* h)
           : h->G == 32 ? klara_launch_diagt_init_q32(p, h->E / 2, needgrad, grid_for(h), st)
                        : klara_launch_diagt_init_q64(p, h->E / 2, needgrad, grid_for(h), st);
     else if (h->kind == 4) e = klara_launch_hiert_init(p, h->E / 2, d.hier_ntimes, needgrad, grid_for(h), st);
+    else if (d.sampler == KLARA_SAMPLER_SMMALA && d.target == KLARA_TARGET_LOGISTIC) e = klara_launch_smmala_init(p, h->E, grid_for(h), lds_for(h), st);
     else if (d.target == KLARA_TARGET_CUSTOM) e = klara_jit_launch_init(h->jit, p, needgrad, grid_for(h), lds_for(h), st, 64 * h->custom_wpb);
     else if (d.target == KLARA_TARGET_GAUSS_DIAG)
         e = launch_init_t<KLARA_TARGET_GAUSS_DIAG>(p, h->E, h->G, needgrad, grid_for(h), lds_for(h), st);
@@ -1197,6 +1212,7 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
     case KLARA_SAMPLER_MH: return klara_launch_mh(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
     case KLARA_SAMPLER_MALA: return klara_launch_mala(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
     case KLARA_SAMPLER_HMC: return klara_launch_hmc(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
+    case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
     default: return klara_launch_slice(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
     }
 }
@@ -2505,7 +2521,8 @@ extern "C" klara_status klara_selftest_mfma_f64_4x4x4(int32_t device, const doub
 
 extern "C" klara_status klara_check_custom_target(const char* src, int32_t sampler, int32_t ndims)
 {
-    if (!src || sampler < KLARA_SAMPLER_MH || sampler > KLARA_SAMPLER_SLICE || ndims <= 0) return KLARA_ERR_INVALID_ARG;
+    if (!src || sampler < KLARA_SAMPLER_MH || sampler > KLARA_SAMPLER_SMMALA || ndims <= 0) return KLARA_ERR_INVALID_ARG;
+    if (sampler == KLARA_SAMPLER_SMMALA && (ndims > 8 || !smmala_custom_source(src))) return KLARA_ERR_UNSUPPORTED;
     const int modes[1] = { 0 };
     std::string src2;
     if (pair_as_whole(src, sampler, ndims)) { src2 = pair_as_whole_source(src); src = src2.c_str(); }

@@ -5,6 +5,8 @@
 //
 //   KLARA_USER_FN double klara_user_logtarget(const double* x, int D, const double* data, long long ndata);
 //   KLARA_USER_FN void   klara_user_gradlogtarget(const double* x, int D, const double* data, long long ndata, double* g);
+//   KLARA_USER_FN void   klara_user_tensorlogtarget(const double* x, int D, const double* data, long long ndata, double* G);   (SMMALA only:
+//                        the metric, a row-major symmetric D x D matrix; D <= 8, one chain per lane; the upper triangle is read)
 //
 // in the C subset both hipcc and a host C compiler accept (KLARA_D is predefined to the job's dimension so that loops
 // unroll and x / g stay in registers; kd_exp, kd_log, kd_fma, kd_erf and IEEE + - * / sqrt are bit-reproducible on host and
@@ -82,9 +84,22 @@ KLARA_PRAGMA_UNROLL_E
         ll = 0.0; lp = 0.0;
 #endif
     }
-    template <bool WANT_LT, bool WANT_GRAD>
-    __device__ __forceinline__ void eval(const LaneCtx<E>& cx, const double (&x)[E], double& ltpart, double (&g)[E]) const
+    // NTRI > 0 (the SMMALA sampler, one chain per lane, D <= 8): gm[] receives the upper triangle of the user's tensor (a row-major D x D
+    // matrix filled by klara_user_tensorlogtarget, the tensorlogtarget closure of BasicContMuvParameter), packed as in klara_kernels.h ktri
+    template <bool WANT_LT, bool WANT_GRAD, int NTRI = 0>
+    __device__ __forceinline__ void eval(const LaneCtx<E>& cx, const double (&x)[E], double& ltpart, double (&g)[E], double* gm = nullptr) const
     {
+#ifdef KLARA_SMMALA
+        if constexpr (NTRI > 0) {
+            double gt[KLARA_D * KLARA_D];
+            klara_user_tensorlogtarget(x, D, data, ndata, gt);
+KLARA_PRAGMA_UNROLL_E
+            for (int a = 0; a < E; ++a) {
+KLARA_PRAGMA_UNROLL_E
+                for (int b = a; b < E; ++b) gm[ktri(a, b, E)] = (b < KLARA_D) ? gt[a * KLARA_D + b] : 0.0;
+            }
+        }
+#endif
         if (staged) {
             stage(cx, x);
             if (WANT_LT) { lt_full = klara_user_logtarget(xs, D, data, ndata); ltpart = 0.0; }
@@ -121,5 +136,6 @@ KLARA_PRAGMA_UNROLL_E
         }
     }
     __device__ __forceinline__ double finalize(double red) const { return staged ? lt_full : red; }
+    static __device__ __forceinline__ double metric_diag(const KParams&) { return 0.0; }     // the user's tensor is the whole metric
 };
 template <int E> struct TargetSel<KLARA_TARGET_CUSTOM, E> { using type = CustomTarget<E>; };

@@ -192,10 +192,10 @@ std::string trans_expr(int sampler, int E, int G, int mode)
     snprintf(b, sizeof b, "k_transitions<%d, KLARA_TARGET_CUSTOM, %d, %d, %d>", sampler, E, G, mode);
     return b;
 }
-std::string init_expr(int E, int G)
+std::string init_expr(int sampler, int E, int G)
 {
     char b[96];
-    snprintf(b, sizeof b, "k_init<KLARA_TARGET_CUSTOM, %d, %d>", E, G);
+    snprintf(b, sizeof b, sampler == KLARA_SAMPLER_SMMALA ? "k_init_smmala<KLARA_TARGET_CUSTOM, %d, %d>" : "k_init<KLARA_TARGET_CUSTOM, %d, %d>", E, G);
     return b;
 }
 
@@ -233,10 +233,16 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
             }
         }
     }
-    const bool needgrad = sampler == KLARA_SAMPLER_MALA || sampler == KLARA_SAMPLER_HMC;
+    const bool needgrad = sampler == KLARA_SAMPLER_MALA || sampler == KLARA_SAMPLER_HMC || sampler == KLARA_SAMPLER_SMMALA;
+    // SMMALA: the metric is the user's klara_user_tensorlogtarget (klara_custom.h); a source without it cannot run the sampler
+    if (sampler == KLARA_SAMPLER_SMMALA && !pf && strstr(src, "klara_user_tensorlogtarget") == nullptr) {
+        g_log = "the SMMALA sampler needs klara_user_tensorlogtarget(const double* x, int D, const double* data, long long ndata, double* G)";
+        return KLARA_ERR_COMPILE;
+    }
     std::string tu;
     tu += "#define KLARA_D " + std::to_string(D) + "\n";
     if (!needgrad) tu += "#define KLARA_CUSTOM_NOGRAD 1\n";
+    if (sampler == KLARA_SAMPLER_SMMALA) tu += "#define KLARA_SMMALA 1\n";
     int unroll_max = KLARA_JIT_UNROLL_MAX_E;
     if (const char* s = getenv("KLARA_JIT_UNROLL_MAX_E")) unroll_max = atoi(s);
     const bool loops = E > unroll_max;                    // element loops over scratch-resident arrays (klara_kernels.h)
@@ -259,7 +265,7 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
         g_log = "hiprtcCreateProgram failed";
         return KLARA_ERR_COMPILE;
     }
-    const std::string ie = pf ? pair_init_expr(*pf) : init_expr(E, G);
+    const std::string ie = pf ? pair_init_expr(*pf) : init_expr(sampler, E, G);
     r->AddNameExpression(prog, ie.c_str());
     std::vector<std::string> te;
     for (int i = 0; i < nmodes; ++i) { te.push_back(pf ? pair_trans_expr(sampler, *pf, modes[i]) : trans_expr(sampler, E, G, modes[i])); r->AddNameExpression(prog, te.back().c_str()); }

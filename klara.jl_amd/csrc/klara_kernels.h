@@ -36,9 +36,15 @@
 #define KLARA_LOGIT_BATCH 4
 #endif
 #define KLARA_LOGIT_BATCH_OF(E) ((E) <= 4 ? KLARA_LOGIT_BATCH : ((KLARA_LOGIT_BATCH) > 3 ? 3 : KLARA_LOGIT_BATCH))
+// ... in the SMMALA kernels, whose two factor states and metric triangle hold the registers the longer batches would take
+#ifndef KLARA_LOGIT_BATCH_SMMALA
+#define KLARA_LOGIT_BATCH_SMMALA 2
+#endif
 template <int N> struct KInt { static constexpr int value = N; };
 template <int N> __device__ __forceinline__ constexpr int kstride(KInt<N>) { return N; }
 __device__ __forceinline__ constexpr int kstride(int v) { return v; }
+// packed symmetric E x E matrices of the SMMALA sampler: entry (a, b), a <= b, row by row (the lower factor L_ij, i >= j, sits at ktri(j, i))
+__host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { return a * E - (a * (a - 1)) / 2 + (b - a); }
 // nothing is scheduled across a stage boundary of the batched row evaluation
 // (KLARA_PIN(v): the value is "produced" here as far as the compiler knows, so arithmetic on it cannot be hoisted above this point)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -462,13 +468,19 @@ struct LogisticTarget {
         __syncthreads();
         sX = X; sy = y; sL12 = l12; ndata = p.ndata; D = p.D; lambda = p.lambda; lpconst = p.lpconst;
     }
-    template <bool WANT_LT, bool WANT_GRAD>
+    // NTRI > 0 (the SMMALA sampler): gm[] receives the upper triangle of X' diag(r (1 - r)) X (swiss/SMMALA/analytical.jl:20-23, without the
+    // I / lambda), E x E packed row by row (ktri), accumulated in the same row loop and butterfly as the other sums
+    template <bool WANT_LT, bool WANT_GRAD, int NTRI = 0>
     __device__ __forceinline__ void eval(const LaneCtx<E>& cx, const double (&x)[E], double& ltpart,
-                                         double (&g)[E]) const
+                                         double (&g)[E], double* gm = nullptr) const
     {
         // rows r = rq, rq + RS, ... of the design matrix belong to this lane (RS = 1: all of them); the RS lane
         // partials are combined by one xor butterfly below (the oracle sums in the same order, layout kind 2)
         double dotxy = 0.0, slog = 0.0, gacc[E];
+        if constexpr (NTRI > 0) {
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 0; k < NTRI; ++k) gm[k] = 0.0;
+        }
 KLARA_PRAGMA_UNROLL_E
         for (int e = 0; e < E; ++e) gacc[e] = 0.0;
         // One data row: everything a row contributes, in the oracle's order.  The rows of a lane are r = rq, rq + RS, ...: every
@@ -538,11 +550,20 @@ KLARA_PRAGMA_UNROLL_E
 KLARA_PRAGMA_UNROLL_E
                     for (int e = 0; e < E; ++e) gacc[e] = kd_fma(row[j][e], res, gacc[e]);
                 }
+                if constexpr (NTRI > 0) {
+                    const double wr = lg[j] * (1.0 - lg[j]);                      // r.*(1-r)
+KLARA_PRAGMA_UNROLL_E
+                    for (int a = 0; a < E; ++a) {
+                        const double ta = row[j][a] * wr;
+KLARA_PRAGMA_UNROLL_E
+                        for (int b = a; b < E; ++b) gm[ktri(a, b, E)] = kd_fma(ta, row[j][b], gm[ktri(a, b, E)]);
+                    }
+                }
             }
         };
         // The rows of a lane are r = rq, rq + RS, ...: every lane takes ndata / RS of them (a wave-uniform count: scalar loops) and the
         // lanes with rq < ndata % RS one more.
-        constexpr int RB = KLARA_LOGIT_BATCH_OF(E);
+        constexpr int RB = NTRI > 0 ? KLARA_LOGIT_BATCH_SMMALA : KLARA_LOGIT_BATCH_OF(E);
         const int nfull = ndata / cx.RS, tail = ndata - nfull * cx.RS;
         const int nbat = nfull / RB;
         if (cx.RS == 4) { for (int b = 0; b < nbat; ++b) rows_of(KInt<RB>(), cx.rq + b * RB * 4, KInt<4>()); }      // (the default split)
@@ -550,14 +571,22 @@ KLARA_PRAGMA_UNROLL_E
         for (int it = nbat * RB; it < nfull; ++it) rows_of(KInt<1>(), cx.rq + it * cx.RS, cx.RS);
         if (cx.rq < tail) rows_of(KInt<1>(), cx.rq + nfull * cx.RS, cx.RS);
         if (cx.RS > 1) {
-            double red[E + 2];
+            double red[E + 2 + NTRI];
             red[0] = dotxy; red[1] = slog;
 KLARA_PRAGMA_UNROLL_E
             for (int e = 0; e < E; ++e) red[2 + e] = gacc[e];
-            group_allreduce<E + 2>(red, cx.RS, cx.lane);
+            if constexpr (NTRI > 0) {
+KLARA_PRAGMA_UNROLL_E
+                for (int k = 0; k < NTRI; ++k) red[E + 2 + k] = gm[k];
+            }
+            group_allreduce<E + 2 + NTRI>(red, cx.RS, cx.lane);
             dotxy = red[0]; slog = red[1];
 KLARA_PRAGMA_UNROLL_E
             for (int e = 0; e < E; ++e) gacc[e] = red[2 + e];
+            if constexpr (NTRI > 0) {
+KLARA_PRAGMA_UNROLL_E
+                for (int k = 0; k < NTRI; ++k) gm[k] = red[E + 2 + k];
+            }
         }
         if (WANT_LT) {
             double dotpp = 0.0;
@@ -573,6 +602,8 @@ KLARA_PRAGMA_UNROLL_E
         }
     }
     __device__ __forceinline__ double finalize(double red) const { return red; }
+    // the SMMALA metric's diagonal term beyond gm[] (analytical.jl:22: + eye(D) / v[1])
+    static __device__ __forceinline__ double metric_diag(const KParams& p) { return 1.0 / p.lambda; }
 };
 
 // KLARA_TARGET_HIER_NORMAL (BUGS "Rats", builder-defined — include/klara_hip.h, oracle ko_hier_eval).
@@ -881,6 +912,147 @@ KLARA_PRAGMA_UNROLL_E
         for (int e = 0; e < E; ++e) { x[e] = xp[e]; g[e] = gp[e]; }
         lt = ltp;
     }
+    return acc;
+}
+
+// ---- SMMALA (src/samplers/SMMALA.jl, iterate/SMMALA.jl:107-221): the metric G(x) of a chain, its Cholesky factor and the drift --------
+// All of it in the lane's registers, over all E elements: the padding elements i >= D get G_ii = 1 and zero off the diagonal, so their
+// factor is the identity block and every padded term below is an exact zero (tests/smmala_ref.c runs the same loops).
+template <int E>
+struct SmmalaRegs {
+    static constexpr int NT = E * (E + 1) / 2;
+    double L[NT];        // lower factor, L_ij (i >= j) at ktri(j, i):  G = L L'
+    double r[E];         // 1 / L_ii, formed once per factorisation
+    double f[E];         // G^-1 grad = L^-T L^-1 grad (the "first term" of SMMALA.jl)
+    double ld;           // sum_i log L_ii
+};
+
+// G from the butterflied triangle gm (+ T::metric_diag on the real diagonal: I / lambda of the logistic target, 0 for a user's tensor), then G = L L' column by column in ascending k.
+// Returns false when a pivot is not a finite positive number (SMMALA deviation 4): the factor then
+// holds finite stand-ins and the caller rejects (or, at a start state, raises KLARA_ERR_NONFINITE_INIT).
+template <int E>
+__device__ __forceinline__ bool smmala_factor(const double* gm, int D, double diag, SmmalaRegs<E>& s)
+{
+    bool pd = true;
+    double ld = 0.0;
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {
+        double sj = j < D ? gm[ktri(j, j, E)] + diag : 1.0;
+KLARA_PRAGMA_UNROLL_E
+        for (int k = 0; k < j; ++k) sj = sj - s.L[ktri(k, j, E)] * s.L[ktri(k, j, E)];
+        const bool ok = sj > 0.0 && kfinite(sj);
+        pd = pd && ok;
+        const double ljj = __builtin_sqrt(ok ? sj : 1.0);
+        const double rj = 1.0 / ljj;
+        s.L[ktri(j, j, E)] = ljj; s.r[j] = rj;
+        ld = ld + kd_log(ljj);
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j + 1; i < E; ++i) {
+            double t = (i < D && j < D) ? gm[ktri(j, i, E)] : 0.0;
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 0; k < j; ++k) t = t - s.L[ktri(k, i, E)] * s.L[ktri(k, j, E)];
+            s.L[ktri(j, i, E)] = t * rj;
+        }
+    }
+    s.ld = ld;
+    return pd;
+}
+// v = L^-T z (back substitution, i descending, k ascending)
+template <int E>
+__device__ __forceinline__ void smmala_solve_lt(const SmmalaRegs<E>& s, const double (&z)[E], double (&v)[E])
+{
+KLARA_PRAGMA_UNROLL_E
+    for (int i = E - 1; i >= 0; --i) {
+        double t = z[i];
+KLARA_PRAGMA_UNROLL_E
+        for (int k = i + 1; k < E; ++k) t = t - s.L[ktri(i, k, E)] * v[k];
+        v[i] = t * s.r[i];
+    }
+}
+// s.f = L^-T (L^-1 g)
+template <int E>
+__device__ __forceinline__ void smmala_drift(SmmalaRegs<E>& s, const double (&g)[E])
+{
+    double y[E];
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {
+        double t = g[i];
+KLARA_PRAGMA_UNROLL_E
+        for (int k = 0; k < i; ++k) t = t - s.L[ktri(k, i, E)] * y[k];
+        y[i] = t * s.r[i];
+    }
+    smmala_solve_lt<E>(s, y, s.f);
+}
+// d' G d = |L' d|^2 (SMMALA deviation 3): (L' d)_i = sum_{k >= i} L_ki d_k, k ascending
+template <int E>
+__device__ __forceinline__ double smmala_quad(const SmmalaRegs<E>& s, const double (&d)[E])
+{
+    double q = 0.0;
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {
+        double w = s.L[ktri(i, i, E)] * d[i];
+KLARA_PRAGMA_UNROLL_E
+        for (int k = i + 1; k < E; ++k) w = w + s.L[ktri(i, k, E)] * d[k];
+        q = q + w * w;
+    }
+    return q;
+}
+// the metric, its factor and the drift at x with gradient g (the launch start of a chain group and the SMMALA start-state check)
+template <class T, int E>
+__device__ __forceinline__ bool smmala_state_at(const KParams& p, const T& tg, const LaneCtx<E>& cx, const double (&x)[E], const double (&g)[E],
+                                                SmmalaRegs<E>& s)
+{
+    double gm[SmmalaRegs<E>::NT], dummy, gd[E];
+    tg.template eval<false, false, SmmalaRegs<E>::NT>(cx, x, dummy, gd, gm);
+    const bool pd = smmala_factor<E>(gm, p.D, T::metric_diag(p), s);
+    smmala_drift<E>(s, g);
+    return pd;
+}
+
+// iterate!(job, SMMALA, Multivariate) — iterate/SMMALA.jl:107-221, with C = L^-T (G = L L') in place of chol(inv(G))'
+// (SMMALA deviations 1-4).  `s` is the chain's current factor state; on acceptance it becomes the proposal's.
+template <class T, int E, bool PLAIN, bool COMMIT = true>
+__device__ __forceinline__ bool step_smmala(const KParams& p, const T& tg, const LaneCtx<E>& cx,
+                                            unsigned long long gchain, unsigned long long t,
+                                            const double (&z)[E], const AccDraw& ad, double h,
+                                            double (&x)[E], double (&g)[E], double& lt, SmmalaRegs<E>& s, Proposal<E>& prop)
+{
+    constexpr int NT = SmmalaRegs<E>::NT;
+    const double halfh = 0.5 * h, sq = KCNT ? __builtin_sqrt(h) : p.sqrt_step0;
+    const double inv_h = KCNT ? 1.0 / h : p.inv_step0;                              // dot(.)/step as dot(.) * (1/step), as MALA
+    const double dlogh = (double)p.D * kd_log(h);                                   // logdet(step G^-1) = D log(step) - 2 sum log L_ii
+    double mu[E], v[E], xp[E], dd[E], gp[E], gm[NT], red[1];
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) mu[e] = x[e] + halfh * s.f[e];                      // :112
+    smmala_solve_lt<E>(s, z, v);
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) xp[e] = mu[e] + sq * v[e];                          // :113
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) dd[e] = xp[e] - mu[e];
+    const double fwd = 0.5 * ((dlogh - 2.0 * s.ld) + smmala_quad<E>(s, dd) * inv_h); // :123-131 (needs G(x) only: formed before the evaluation)
+    tg.template eval<true, true, NT>(cx, xp, red[0], gp, gm);                       // :115
+    group_allreduce<1>(red, cx.G, cx.lane);
+    const double ltp = tg.finalize(red[0]);
+    SmmalaRegs<E> sn;
+    const bool pd = smmala_factor<E>(gm, p.D, T::metric_diag(p), sn);               // :133 (the factor instead of inv)
+    smmala_drift<E>(sn, gp);                                                        // :135
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) dd[e] = x[e] - (xp[e] + halfh * sn.f[e]);           // :137
+    const double rev = 0.5 * ((dlogh - 2.0 * sn.ld) + smmala_quad<E>(sn, dd) * inv_h);
+    double ratio = ltp - lt;                                                        // :121
+    ratio += fwd;
+    ratio -= rev;                                                                   // :139-147
+    const bool acc = accept_log_test<E>(p, cx, gchain, t, ad, ratio > 0.0, ratio) && pd;   // :149
+    if (!COMMIT) {
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) { prop.x[e] = xp[e]; prop.g[e] = gp[e]; }
+        prop.lt = ltp;
+    } else if (acc) {                                                               // :150-170
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) { x[e] = xp[e]; g[e] = gp[e]; }
+        lt = ltp;
+    }
+    if (acc) s = sn;                                                                // the metric, its factor and the drift travel with the state
     return acc;
 }
 
@@ -1212,7 +1384,9 @@ template <int SAMPLER, int TARGET, int E, int GT, int MODE>
 // (MALA and HMC on the logistic target at E = 4 — cfg 4 — ask for 4 wavefronts per SIMD: its row loop is a chain of exp / log / division latencies that two
 //  wavefronts cannot cover; the 128-register budget spills 156-272 B outside the row loop and still measured 1.01e9 against 8.1e8
 //  transitions/s with running sums, 1.05e9 against 9.4e8 without, same box)
-__global__ __launch_bounds__(256, (TARGET == KLARA_TARGET_CUSTOM && GT > 1 ? 2 /* staged closures: two workgroups' rows fit a CU's LDS */ :
+__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && !(MODE & 1)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
+                                                                                                  metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2) */ :
+                                   TARGET == KLARA_TARGET_CUSTOM && GT > 1 ? 2 /* staged closures: two workgroups' rows fit a CU's LDS */ :
                                    E == 2 ? (TARGET == KLARA_TARGET_GAUSS_DIAG ? KLARA_E2_DIAG_WAVES : 3) : (E == 4 ? (TARGET == KLARA_TARGET_LOGISTIC && SAMPLER == KLARA_SAMPLER_MALA ? KLARA_E4_WAVES_LOGISTIC
                                                                   : TARGET == KLARA_TARGET_LOGISTIC && SAMPLER == KLARA_SAMPLER_HMC ? KLARA_E4_WAVES_LOGISTIC_HMC
                                                                   : ((MODE & 3) == 3 ? KLARA_E4_WAVES_PLAIN : KLARA_E4_WAVES))
@@ -1241,7 +1415,7 @@ void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
     gdouble* const hist_g = NOMON ? nullptr : p.hist_g;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using T = typename TargetSel<TARGET, E>::type;
-    constexpr bool NEEDG = (SAMPLER == KLARA_SAMPLER_MALA || SAMPLER == KLARA_SAMPLER_HMC);
+    constexpr bool NEEDG = (SAMPLER == KLARA_SAMPLER_MALA || SAMPLER == KLARA_SAMPLER_HMC || SAMPLER == KLARA_SAMPLER_SMMALA);
     constexpr bool NEEDZ = (SAMPLER != KLARA_SAMPLER_SLICE);
 
     LaneCtx<E> cx = make_ctx<E, GT, RSPL>(p);
@@ -1311,6 +1485,11 @@ KLARA_PRAGMA_UNROLL_E
         AccDraw ad = { 0.5, 0.0, false };
         const int acc_slot = (p.D + 1) >> 1;
         if (NEEDZ) lane_normals<E>(cx, p.seed, gchain, kl.t0, z, ad, acc_slot, (p.D + 1) >> 1);   // before the loaded state is touched
+        // SMMALA: the factor state of the group's current states, formed again from x and its gradient at every launch (the same
+        // operations as when the state was accepted, so the bits do not depend on the launch length); a state is only ever reached through a
+        // positive-definite metric (checked at the start state by k_init_smmala)
+        SmmalaRegs<E> sms;
+        if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA) smmala_state_at<T, E>(p, tg, cx, cur.x, cur.g, sms);
 
         TuneRegs tn;
         if (per_chain_tune) tn = { cur.step, cur.accepted, cur.proposed, cur.totproposed, 0, 0.0, 0.0 };
@@ -1329,7 +1508,9 @@ KLARA_PRAGMA_UNROLL_E
             const unsigned long long t = kl.t0 + (unsigned long long)s;
             if (KCNT) tune_count_proposal(p, tn);
             bool acc;
-            if (SAMPLER == KLARA_SAMPLER_MH) acc = step_mh<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop);
+            if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA)
+                acc = step_smmala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, sms, prop);
+            else if (SAMPLER == KLARA_SAMPLER_MH) acc = step_mh<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_MALA) acc = step_mala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_HMC) {
                 double a_prob = 0.0;
@@ -1447,6 +1628,33 @@ __global__ __launch_bounds__(256) void k_init(const KParams p, int needgrad)
 KLARA_PRAGMA_UNROLL_E
         for (int e = 0; e < E; ++e) bad = bad || (cx.valid[e] && !kfinite(g[e]));
     }
+    if (cx.chain_ok && cx.q == 0 && cx.rq == 0) p.LT[cx.chain] = lt;
+    if (bad) klara_raise(p.error_flag, KLARA_ERR_NONFINITE_INIT);
+}
+
+// initialize!(pstate, parameter, sampler::SMMALA) (SMMALA.jl:139-181): the log-target, its gradient and the metric at the start state, which
+// must factor (SMMALA deviation 5: KLARA_ERR_NONFINITE_INIT where the reference's chol throws).  One evaluation gives all
+// three.  (`needgrad` only keeps the signature of k_init, which the run-time compiled path launches the same way.)
+template <int TARGET, int E, int GT>
+__global__ __launch_bounds__(256) void k_init_smmala(const KParams p, int needgrad)
+{
+    kd_tables_to_lds();
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using T = typename TargetSel<TARGET, E>::type;
+    const LaneCtx<E> cx = make_ctx<E, GT>(p);
+    T tg;
+    tg.init(p, cx, reinterpret_cast<double*>(smem));
+    double x[E], g[E], red[1], gm[SmmalaRegs<E>::NT];
+    load_vec<E>(cx, p.X, p.D, x);
+    tg.template eval<true, true, SmmalaRegs<E>::NT>(cx, x, red[0], g, gm);
+    group_allreduce<1>(red, cx.G, cx.lane);
+    const double lt = tg.finalize(red[0]);
+    SmmalaRegs<E> s;
+    const bool pd = smmala_factor<E>(gm, p.D, T::metric_diag(p), s);
+    bool bad = cx.chain_ok && (!kfinite(lt) || !pd);
+    store_vec<E>(cx, p.GR, p.D, g);
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) bad = bad || (cx.valid[e] && !kfinite(g[e]));
     if (cx.chain_ok && cx.q == 0 && cx.rq == 0) p.LT[cx.chain] = lt;
     if (bad) klara_raise(p.error_flag, KLARA_ERR_NONFINITE_INIT);
 }

@@ -25,6 +25,10 @@ hipError_t klara_launch_hmc(const KParams* p, const KLaunch& kl, int mode, int t
                            hipStream_t st);
 hipError_t klara_launch_slice(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
                            hipStream_t st);
+// SMMALA on the logistic target, E in {2, 4, 8} (klara_smmala.hip), and its start-state kernel (log-target, gradient, metric check)
+hipError_t klara_launch_smmala(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
+                               hipStream_t st);
+hipError_t klara_launch_smmala_init(const KParams& p, int E, dim3 grid, size_t lds, hipStream_t st);
 // dense (MFMA) kernels; NE in {8,16,25,32}
 // (Pfrag: the fragment-ordered precision matrix, followed — hasmu — by the 4 NE zero-padded entries of the mean)
 hipError_t klara_launch_dense(const KParams* p, const KLaunch& kl, int sampler, int tuner, bool plain, int NE, const double* Pfrag, bool hasmu,

@@ -108,8 +108,11 @@ class CustomTarget:
         KLARA_USER_FN double klara_user_logtarget(const double* x, int D, const double* data, long long ndata);
         KLARA_USER_FN void   klara_user_gradlogtarget(const double* x, int D, const double* data, long long ndata, double* g);
 
-    (the gradient only for MALA / HMC); it is compiled for gfx950 when the job is created (include/klara_hip.h,
-    KLARA_TARGET_CUSTOM).  `data` is an optional read-only block of doubles handed to both functions."""
+        KLARA_USER_FN void   klara_user_tensorlogtarget(const double* x, int D, const double* data, long long ndata, double* G);
+
+    (the gradient only for MALA / HMC / SMMALA; the tensor — the metric of `tensorlogtarget=`, a row-major symmetric D x D matrix — only for
+    SMMALA, D <= 8, in this plain whole-vector form); it is compiled for gfx950 when the job is created (include/klara_hip.h,
+    KLARA_TARGET_CUSTOM).  `data` is an optional read-only block of doubles handed to every function."""
     ndims: int
     source: str
     data: Optional[np.ndarray] = None
@@ -153,8 +156,16 @@ class CustomTarget:
     def is_pairwise(self) -> bool:
         return "KLARA_USER_PAIR_TARGET" in self.source
 
+    @property
+    def has_tensor(self) -> bool:
+        """the source defines klara_user_tensorlogtarget (what the SMMALA sampler needs)"""
+        return "klara_user_tensorlogtarget" in self.source
+
     def check(self, sampler: int) -> None:
-        """Compile only (no GPU needed); raises KlaraError with the compiler's log on failure."""
+        """Compile only (no GPU needed); raises KlaraError with the compiler's log on failure (for SMMALA also when the source has no
+        klara_user_tensorlogtarget, or is a likelihood + prior / pair-closure source, or D > 8)."""
+        if int(sampler) == L.SAMPLER_SMMALA and not self.has_tensor:
+            raise L.KlaraError(L.ERR_COMPILE, "klara_check_custom_target: the SMMALA sampler needs klara_user_tensorlogtarget")
         L.check(L.load().klara_check_custom_target(self.source.encode(), int(sampler), self.ndims), "klara_check_custom_target")
 
 
