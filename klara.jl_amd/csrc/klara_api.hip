@@ -11,12 +11,7 @@
 #include <new>
 #include <unordered_map>
 #include <vector>
-#include "klara_launch.h"
-
-// user-defined targets keep the whole vector in one lane (klara_custom.h): pow2ceil(D) elements per lane
-#ifndef KLARA_CUSTOM_MAXD
-#define KLARA_CUSTOM_MAXD 1024           // (round 6: 64 lanes x 16 elements of the staged form; 256 before)
-#endif
+#include "klara_plan.h"
 
 // device-decided kernel choice (KAuto): launches shorter than this are issued as one kernel chosen on the host
 #ifndef KLARA_AUTO_PAIR_MIN_STEPS
@@ -33,9 +28,7 @@ thread_local hipFuncAttributes* klara_attr_query = nullptr;     // see klara_lau
 
 struct klara_handle {
     klara_desc d;
-    // layout
-    int kind, G, E;            // kind 0: group layout (G lanes x E elems); kind 1: MFMA (E = NE); kind 2: logistic row split
-    int RS = 1;                // kind 2: lanes sharing one chain's data rows (G = 1 there)
+    KlaraPlan plan;            // layout, kernels, grids and LDS of the job, planned once by klara_create (klara_plan.h)
     // device buffers
     double *X = nullptr, *GR = nullptr, *LT = nullptr;
     double* tune_step = nullptr;
@@ -53,15 +46,12 @@ struct klara_handle {
     double *hist_lt = nullptr, *hist_g = nullptr, *hist_ll = nullptr, *hist_lp = nullptr;
     unsigned long long* clock_probe = nullptr;        // pair-transposed kernels: (s_memtime, s_memrealtime) at the end / start of one workgroup of the last launch
     bool pair_enqueued = false;                       // a launch of this handle has enqueued both kernel families (their one-time scratch set-up is behind us)
-    int custom_wpb = 4;                               // staged closures: wavefronts per workgroup (2 where four wavefronts' rows do not fit the LDS)
-    int custom_rows = 2;                              // staged closures: vectors per chain in LDS (3 for the likelihood + prior form)
     int* err = nullptr; int* flag_host = nullptr;     // error flag as the kernels address it; the same word as the host reads it (null: err is device memory)
     double *vecparam = nullptr, *gw = nullptr, *gmu = nullptr, *lX = nullptr, *ly = nullptr, *Pfrag = nullptr,
            *hY = nullptr, *hxc = nullptr;
     double* pooled_out = nullptr;   // 2*D doubles + 1 u64 scratch for pooled summaries
     double* pool_partial = nullptr; // KLARA_POOL_BLOCKS x (2 D doubles + 1 u64): stage-1 partials of the pooled summaries
     double* cdata = nullptr; KlaraJit* jit = nullptr;   // user-defined target: data block, run-time compiled kernels
-    bool jit_pair = false;          // ... given as a pair closure: run-time compiled k_diagt instantiations (layout kind 3)
     // streaming batch means (bm_batchlen > 0): running sum at the last batch boundary, Welford mean / M2 of the batch means
     double *bm_prev = nullptr, *bm_mean = nullptr, *bm_m2 = nullptr; long long bm_count = 0;
     KParams* d_params = nullptr;    // device copy of the handle's static kernel parameters
@@ -77,226 +67,21 @@ struct klara_handle {
     long long m_prop = 0, m_tot = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr; long long last_launches = 0; bool timed = false;
-    // layout kind 3: the chain groups are cut into `nparts` contiguous partitions, partition j > 0 runs on its own
+    // layout kind 3: the chain groups are cut into plan.nparts contiguous partitions, partition j > 0 runs on its own
     // internal stream.  Chains are independent, so partition j's transition t+1 only follows its own transition t; the
     // streams drift apart and one partition's kernel fills the SIMDs while the other's drains / ramps up.
-    int nparts = 1; hipStream_t side[3] = { nullptr, nullptr, nullptr }; hipEvent_t fork_ev = nullptr, join_ev[3] = { nullptr, nullptr, nullptr };
-    // layout kind 3, untuned MH / MALA with 17 <= D <= 104: the 4-lanes-per-chain kernels are available as well (np4 pairs per lane).
+    hipStream_t side[3] = { nullptr, nullptr, nullptr }; hipEvent_t fork_ev = nullptr, join_ev[3] = { nullptr, nullptr, nullptr };
+    // layout kind 3, untuned MH / MALA with 17 <= D <= 104: the 4-lanes-per-chain kernels are available as well (plan.np4 pairs per lane).
     // They sum in the 8-lane order, so which of the two kernel families runs a launch changes no bit; with running sums on, the
     // choice is taken on the device launch by launch (KAuto, klara_diagt.h): auto_cells = [partition][launch parity] decision,
     // auto_ctr = [partition] launch counter, auto_mirror = host-visible {mode, accepted} per partition (may be null).
-    bool q4_ok = false; int np4 = 0;
     int* auto_cells = nullptr; unsigned long long* auto_ctr = nullptr; int* auto_mirror = nullptr; int* auto_mirror_dev = nullptr;
     long long launch_idx = 0;
-    double auto_threshold = 0.06;   // acceptance above which a launch keeps resident sums (8 lanes) — the measured crossover: the 4-lane kernels' folds are atomic adds
-                                    // since round 4 (flat to ~4.5 % acceptance, saturating the atomic units beyond: profiles/r4_acceptance_cost_atomic.txt; round 3's
-                                    // read-modify-write folds crossed at 0.12, profiles/r3_acceptance_cost_probe.txt)
     int query_lanes = 4;            // klara_get_kernel_attributes: which of the two kernel families to report
     long long n_launch_mode[3] = { 0, 0, 0 };   // launches issued as: forced / single 4-lane, forced / single 8-lane, device-decided pair
 };
 
-static int cnt_predicate(const klara_desc& d)
-{
-    if (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_SLICE) return d.verbose != 0;
-    return (d.tuner == KLARA_TUNER_VANILLA && d.verbose) || d.tuner == KLARA_TUNER_ACCEPT_RATE ||
-           (d.tuner == KLARA_TUNER_DUAL_AVERAGING && d.verbose);
-}
-
-static int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-
-// layout kind 3 serves the jobs whose transition is pure elementwise work plus three sums (see klara_diagt.h):
-// diagonal Gaussian, every sampler, every tuner, any monitor
-static bool diagt_eligible(const klara_desc& d)
-{
-    if (d.target != KLARA_TARGET_GAUSS_DIAG) return false;
-    // (D <= 16: the group layout already puts a chain on <= 4 lanes, 16..64 chains per wavefront)
-    if (d.ndims < 17 || d.ndims > 2 * 64 * KLARA_DIAGT_NP_MAX) return false;       // (Q = 8, 16, 32 or 64 lanes per chain)
-    if (const char* s = getenv("KLARA_LAYOUT_KIND")) { if (atoi(s) == 0) return false; }
-    if (getenv("KLARA_LAYOUT_E")) return false;
-    return true;
-}
-
-// the slice sampler on the pair-transposed layout with nothing counting: every lane takes its elements through a whole launch on
-// its own (klara_diagt_slice.h); a wavefront only waits for its slowest lane once per element slot and launch, so longer launches waste less
-static bool slice_free_eligible(const klara_desc& d)
-{
-    static const bool lockstep = getenv("KLARA_SLICE_LOCKSTEP") != nullptr;
-    const uint32_t lane_local = KLARA_MON_ACCEPT | KLARA_MON_SUMMARIES | KLARA_MON_HISTORY | KLARA_MON_HIST_LT;
-    const bool values_kept = (d.monitor & KLARA_MON_HISTORY) != 0 || d.acov_maxlag > 0;       // (the log-target history is formed from the saved values)
-    // (nothing counts AND nothing tunes — a pooled or dual-averaging tuner setting, verbose or not, runs k_diagt<SLICE> at its 32 transitions per
-    // launch: the launch length and the kernel choice come from this one predicate)
-    const bool plain = !cnt_predicate(d) && d.tuner_mode == KLARA_TUNE_PER_CHAIN && d.tuner != KLARA_TUNER_DUAL_AVERAGING;
-    return diagt_eligible(d) && d.sampler == KLARA_SAMPLER_SLICE && plain && !lockstep &&
-           (d.monitor & ~lane_local) == 0 && (!(d.monitor & KLARA_MON_HIST_LT) || values_kept);
-}
-// transitions per launch when klara_desc.steps_per_launch = 0
-static long long default_steps_per_launch(const klara_desc& d) { return slice_free_eligible(d) ? KLARA_DEFAULT_STEPS_PER_LAUNCH_SLICE : KLARA_DEFAULT_STEPS_PER_LAUNCH; }
-
-// untuned MH / MALA on the pair-transposed layout up to D = 104: 4 lanes per chain, 16 chains per wavefront, NP = ceil(D/8) in 3..13
-// (klara_launch.h) — kernels that keep no resident running sums (a moving chain's sums are folded into memory by atomic adds)
-static bool q4_eligible(const klara_desc& d)
-{
-    const bool plain = !cnt_predicate(d) && d.tuner_mode == KLARA_TUNE_PER_CHAIN && d.tuner != KLARA_TUNER_DUAL_AVERAGING;
-    // (round 5: HMC too while no saved-sample monitor is on — 12.5 of 13 pair slots real at D = 100 instead of 6.25 of 7, the reductions in the 8-lane order as
-    // for MH / MALA; with running sums or a history the 8-lane kernels keep it: at HMC's acceptance every transition would fold)
-    // (a non-unit diagonal beyond 9 pairs per lane spills: those stay on 8 lanes)
-    const bool hmc_ok = d.sampler == KLARA_SAMPLER_HMC && (d.monitor & ~(uint32_t)KLARA_MON_ACCEPT) == 0 && d.acov_maxlag == 0 &&
-                        ((d.gauss_w == nullptr && d.gauss_mu == nullptr) || d.ndims <= 72) && !getenv("KLARA_DIAGT_NO_Q4_HMC");
-    return diagt_eligible(d) && plain && (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_MALA || hmc_ok) && d.ndims <= 104 &&
-           !getenv("KLARA_DIAGT_NO_Q4");
-}
-
-// layout kind 4 (klara_hiert.h): MH / MALA / HMC on the hierarchical target, 8 lanes per chain, 4 units per lane
-static bool hiert_eligible(const klara_desc& d)
-{
-    if (d.target != KLARA_TARGET_HIER_NORMAL || d.sampler == KLARA_SAMPLER_SLICE) return false;
-    if (d.hier_nunits < 9 || d.hier_nunits > 32) return false;
-    if (const char* s = getenv("KLARA_LAYOUT_KIND")) { if (atoi(s) == 0) return false; }
-    if (getenv("KLARA_LAYOUT_E")) return false;
-    return true;
-}
-
-// a user target given as a pair closure (`#define KLARA_USER_PAIR_TARGET 1` + klara_user_pair, include/klara_hip.h)
-static bool pair_source(const char* src) { return src != nullptr && strstr(src, "KLARA_USER_PAIR_TARGET") != nullptr && strstr(src, "KLARA_PAIR_AS_WHOLE") == nullptr; }
-static bool pair_form(const klara_desc& d) { return d.target == KLARA_TARGET_CUSTOM && pair_source(d.custom_src); }
-// ... that the pair-transposed kernels do not serve (fewer than 9 pairs, the slice sampler): it runs as a whole-vector closure, the sum over its pairs
-// formed by klara_custom_compose.h (round 5; these jobs used to be refused)
-// (round 6: the slice sampler takes pair closures on the few-lanes kernels too — k_diagt<SLICE, .., USERPAIR> —; KLARA_PAIR_SLICE_AS_WHOLE=1 keeps the whole-vector form of round 5)
-static bool pair_as_whole(const char* src, int sampler, int ndims)
-{
-    return pair_source(src) && (ndims < 17 || (sampler == KLARA_SAMPLER_SLICE && getenv("KLARA_PAIR_SLICE_AS_WHOLE") != nullptr));
-}
 static std::string pair_as_whole_source(const char* src) { return std::string("#define KLARA_PAIR_AS_WHOLE 1\n") + src; }
-
-// Whole-vector closures (klara_custom.h).  Up to 32 dimensions a lane keeps the whole vector in registers (one chain per lane); beyond,
-// the chain is spread over G lanes with E = 2 ceil(D / 2G) <= 16 elements each and evaluations read the vector from the chain's row of
-// LDS (STAGED).  G: enough lanes for 16 elements per lane, and a workgroup's rows (4 wavefronts x 64 / G chains) within the 56 KB of
-// dynamic LDS a launch gets without asking.  `lanes` = 1 keeps one chain per lane at any D (the library's own heavy closures — the
-// logistic regression beyond 8 parameters, the dense Gaussian beyond 128 dimensions — cost O(n D) / O(D^2) per evaluation, and the
-// G identical evaluations of the staged form would multiply exactly that part; KLARA_CUSTOM_LANES=1 in the environment for a user's).
-static size_t custom_stage_bytes(int D, int G, int nrows, int wpb)        // (klara_custom.h klara_custom_stage_stride)
-{
-    int s = nrows * ((D + 1) & ~1) + 2;
-    if ((2 * s) % 64 == 0) s += 2;
-    return (size_t)wpb * (size_t)(64 / G) * (size_t)s * sizeof(double);
-}
-// wpb: wavefronts per workgroup of the staged kernels — 4, or 2 where four wavefronts' rows would not fit and force more lanes per chain
-static void custom_layout(int D, int lanes, bool lik_prior, int* G, int* E, int* wpb)
-{
-    *wpb = 4;
-    if (const char* s = getenv("KLARA_CUSTOM_LANES")) { const int v = atoi(s); if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) lanes = v; }
-    if (lanes == 1 || (lanes == 0 && D <= 32)) { *G = 1; *E = pow2ceil(D < 2 ? 2 : D); return; }
-    int g = lanes > 1 ? lanes : 4;
-    while (g < 64 && (D + 2 * g - 1) / (2 * g) > 8) g *= 2;                      // at most 16 elements per lane (round 6: up to 64 lanes — one chain per wavefront —: D <= 1024)
-    const int nrows = lik_prior ? 3 : 2;
-    int w = 4;
-    if (const char* s = getenv("KLARA_CUSTOM_WPB")) { const int v = atoi(s); if (v == 2 || v == 4) w = v; }
-    else if (g >= 8 && custom_stage_bytes(D, g, nrows, 4) > KLARA_LDS_DEFAULT_DYNAMIC) w = 2;     // (measured: D = 128 +20 %, D = 256 +21 %; at 4 lanes x 16 elements the kernels spill and 8 x 8 on four wavefronts is faster)
-    while (g < 64 && custom_stage_bytes(D, g, nrows, w) > KLARA_LDS_DEFAULT_DYNAMIC) g *= 2;
-    *G = g; *E = 2 * ((D + 2 * g - 1) / (2 * g)); *wpb = w;
-}
-static bool custom_lik_prior(const char* src) { return src != nullptr && strstr(src, "KLARA_USER_LIKELIHOOD_PRIOR") != nullptr; }
-
-// the dense Gaussian beyond the LDS-resident layouts (D = 129 .. 256) stays on the matrix cores for every sampler — HMC (every tuner), MALA, MH
-// and (round 5) the slice sampler (klara_dense_big.h); beyond D = 256 the closure form (klara_create)
-static bool dense_streamed(const klara_desc& d)
-{
-    return d.target == KLARA_TARGET_GAUSS_DENSE && d.ndims > 128 && d.ndims <= 256 && getenv("KLARA_DENSE_NO_STREAM") == nullptr &&
-           (d.sampler != KLARA_SAMPLER_SLICE || getenv("KLARA_DENSE_SLICE_NO_STREAM") == nullptr);
-}
-
-// the dense Gaussian beyond D = 256 (round 6): the tile of 16 chains on a WORKGROUP of W = 4, 8, 12 or 16 wavefronts that deal the ceil(D / 16) row tiles
-// of P evenly, 2 .. 4 each (klara_dense_split.h, layout kind 6; MH, MALA, HMC with every tuner; 257 <= D <= 1024).  KLARA_DENSE_SPLIT=1 in the environment puts the smaller
-// dense targets on it as well (measurements, tests).
-static bool dense_split(const klara_desc& d)
-{
-    if (d.target != KLARA_TARGET_GAUSS_DENSE || d.ndims > 64 * 16) return false;
-    if (getenv("KLARA_DENSE_NO_SPLIT") != nullptr) return false;
-    if (d.ndims > 256) return true;
-    const char* s = getenv("KLARA_DENSE_SPLIT");
-    return s != nullptr && atoi(s) != 0;
-}
-
-// the logistic regression beyond 16 parameters on the matrix cores (klara_logit_mfma.h, layout kind 5): X p and X' (y - 1/(1+exp(-Xp))) of 16 chains per
-// wavefront as two MFMA passes over streamed fragments of X; every sampler, every tuner, the monitors of the dense layouts.  The likelihood / prior
-// history keeps the closure form (klara_create).
-static bool logit_mfma_eligible(const klara_desc& d)
-{
-    // (also 9 .. 16 parameters whose rows, padded to 16 columns, do not fit the LDS of the row-split kernels: the stream has no such limit)
-    const bool beyond_rowsplit = d.ndims > 16 || (d.ndims > 8 && (size_t)d.logit_ndata * 17 > KLARA_LOGIT_MAX_LDS_DOUBLES);
-    // (the kernels address the fragment stream with 32-bit byte offsets: 2 x 16 ceil(n / 16) x 4 NE doubles stay below 2 GB — 2 million rows at 128 parameters)
-    const size_t stream_bytes = 2 * 16 * (((size_t)d.logit_ndata + 31) / 32 * 2) * 4 * (8 * (((size_t)d.ndims + 31) / 32)) * sizeof(double);
-    if (stream_bytes >= ((size_t)1 << 31)) return false;
-    return d.target == KLARA_TARGET_LOGISTIC && beyond_rowsplit && d.ndims <= 256 && d.logit_ndata >= 1 &&
-           !(d.monitor & KLARA_MON_HIST_LLLP) && getenv("KLARA_LOGIT_NO_MFMA") == nullptr;
-}
-
-static klara_status select_layout(const klara_desc& d, int* kind, int* G, int* E, int custom_lanes = 0, int* custom_wpb = nullptr)
-{
-    if (logit_mfma_eligible(d)) { *kind = 5; *G = 4; *E = 8 * ((d.ndims + 31) / 32); return KLARA_OK; }
-    if (hiert_eligible(d)) { *kind = 4; *G = 8; *E = 8; return KLARA_OK; }
-    const int D = d.ndims;
-    if (dense_split(d)) { *kind = 6; *G = klara_split_waves(D); *E = klara_split_new(D); return KLARA_OK; }      // G: wavefronts per tile of 16 chains (klara_dense_split.h klara_split_waves)
-    if (d.target == KLARA_TARGET_GAUSS_DENSE) {
-        *kind = 1; *G = 4;
-        if (D <= 32) *E = 8; else if (D <= 64) *E = 16; else if (D <= 100) *E = 25; else if (D <= 128) *E = 32;
-        else if (dense_streamed(d)) *E = 8 * ((D + 31) / 32);       // HMC to D = 256 (NE = 40, 48, 56, 64): P streamed from memory, momentum in LDS (klara_dense_big.h)
-        else return KLARA_ERR_UNSUPPORTED;
-        return KLARA_OK;
-    }
-    *kind = 0;
-    if (d.target == KLARA_TARGET_CUSTOM && pair_form(d)) {
-        // pair closure (klara_diagt.h USERPAIR): the pair-transposed layout, Q = 8 / 16 / 32 lanes per chain
-        if (D < 17 || D > 2 * 64 * KLARA_DIAGT_NP_MAX) return KLARA_ERR_UNSUPPORTED;       // (fewer than 9 pairs: use the whole-vector form)
-        const int Q = D <= 128 ? 8 : (D <= 256 ? 16 : (D <= 512 ? 32 : 64));
-        *kind = 3; *G = Q; *E = 2 * ((D + 2 * Q - 1) / (2 * Q));
-        return KLARA_OK;
-    }
-    if (d.target == KLARA_TARGET_CUSTOM) {       // whole-vector closure: one chain per lane, or staged through LDS on G lanes (klara_custom.h)
-        if (D > KLARA_CUSTOM_MAXD) return KLARA_ERR_UNSUPPORTED;
-        int wpb = 4;
-        custom_layout(D, custom_lanes, custom_lik_prior(d.custom_src), G, E, &wpb);
-        if (*G > 1 && (*E > 16 || custom_stage_bytes(D, *G, custom_lik_prior(d.custom_src) ? 3 : 2, wpb) > KLARA_LDS_DEFAULT_DYNAMIC)) { *G = 1; *E = pow2ceil(D); wpb = 4; }
-        if (custom_wpb) *custom_wpb = wpb;
-        return KLARA_OK;
-    }
-    if (d.target == KLARA_TARGET_LOGISTIC) {
-        *G = 1;   // every lane holds the whole parameter vector; klara_create may turn on the row split (kind 2)
-        if (D <= 2) *E = 2; else if (D <= 4) *E = 4; else if (D <= 8) *E = 8; else if (D <= 16) *E = 16; else return KLARA_ERR_UNSUPPORTED;
-        return KLARA_OK;
-    }
-    // diagonal Gaussian and nothing tunes: the pair-transposed layout
-    // (klara_diagt.h), Q = 8 lanes per chain, NP element pairs per lane
-    if (diagt_eligible(d)) {
-        // lanes per chain of the layout, i.e. of the summation order klara_get_layout reports.  (Untuned MH / MALA up to D = 104 also
-        // run on 4-lane kernels that reproduce the 8-lane order: q4_eligible.)
-        const int Q = D <= 128 ? 8 : (D <= 256 ? 16 : (D <= 512 ? 32 : 64));
-        const int np = (D + 2 * Q - 1) / (2 * Q);                                 // NP = ceil(D/2 / Q) exactly (see klara_diagt.h)
-        if (np >= 2 && np <= KLARA_DIAGT_NP_MAX) { *kind = 3; *G = Q; *E = 2 * np; return KLARA_OK; }
-    }
-    // diagonal Gaussian: E elements per lane, G lanes; optional override for layout experiments
-    // D <= 128: E = 2 or 4, whichever wastes fewer lanes; on a tie E = 4 (twice the chains per wavefront
-    // amortise the per-wave fixed work — measured 80 us vs 90 us per launch at D = 100, 65,536 chains)
-    int e = (D <= 256) ? 4 : (D <= 512) ? 8 : 0;
-    if (D <= 128 && pow2ceil((D + 1) / 2) * 2 < pow2ceil((D + 3) / 4) * 4) e = 2;
-    if (const char* s = getenv("KLARA_LAYOUT_E")) {
-        const int v = atoi(s);
-        if ((v == 2 || v == 4 || v == 8) && (D + v - 1) / v <= 64) e = v;
-    }
-    if (e == 0 || (d.target == KLARA_TARGET_HIER_NORMAL && e > 4)) return KLARA_ERR_UNSUPPORTED;
-    *E = e; *G = pow2ceil((D + e - 1) / e);
-    return KLARA_OK;
-}
-
-// SMMALA (KLARA_SAMPLER_SMMALA), D <= 8 on the group layout (E = 2 / 4 / 8): the logistic target (kinds 0 / 2) and a user-defined target in the
-// plain whole-vector form, one chain per lane, whose source defines klara_user_tensorlogtarget (the likelihood + prior form and pair closures are not taken)
-static bool smmala_custom_source(const char* src) { return src != nullptr && !pair_source(src) && !custom_lik_prior(src); }
-static bool smmala_eligible(const klara_desc& d)
-{
-    if (d.ndims > 8) return false;
-    if (d.target == KLARA_TARGET_LOGISTIC) return !logit_mfma_eligible(d);
-    return d.target == KLARA_TARGET_CUSTOM && smmala_custom_source(d.custom_src);
-}
 
 static klara_status validate(const klara_desc* d)
 {
@@ -457,16 +242,6 @@ static bool free_all(klara_handle* h)
 
 static KParams make_params(klara_handle* h);
 
-// the k_transitions MODE values a job can launch (see launch_steps): nothing counts/tunes and nothing is monitored -> 3 and
-// its one-transition-per-launch form 7; nothing counts/tunes -> 1; general -> 0
-static int kernel_modes(const klara_desc& d, int (&modes)[2])
-{
-    const bool plain = !cnt_predicate(d) && d.tuner_mode == KLARA_TUNE_PER_CHAIN && d.tuner != KLARA_TUNER_DUAL_AVERAGING;
-    if (plain && d.monitor == 0) { modes[0] = 3; modes[1] = 7; return 2; }
-    modes[0] = plain ? 1 : 0;
-    return 1;
-}
-
 // The logistic-regression target beyond D = 8 (the row-split kernels hold the whole parameter vector of a chain in every lane's
 // registers and the data rows in LDS): the same closures — doc/examples/swiss/MALA/analytical.jl:11-18, operation for operation what
 // LogisticTarget::eval and the oracle's ko_logistic_eval compute with all rows on one lane — as source text for the run-time compiled
@@ -541,70 +316,9 @@ KLARA_USER_FN double klara_user_logtarget(const double* x, int D, const double* 
 }
 )SRC";
 
-static klara_status create_impl(const klara_desc* desc, klara_handle** out, int custom_lanes = 0);
-
-extern "C" klara_status klara_create(const klara_desc* desc, klara_handle** out)
+static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, klara_handle** out)
 {
-    if (!out) return KLARA_ERR_INVALID_ARG;
-    *out = nullptr;
-    klara_status st = validate(desc);
-    if (st != KLARA_OK) return st;
-    // SMMALA runs on the row-split logistic kernels only (D <= 8, the rows in LDS); every other job of it is refused before anything is allocated
-    if (desc->sampler == KLARA_SAMPLER_SMMALA && !smmala_eligible(*desc)) return KLARA_ERR_UNSUPPORTED;
-    // the logistic regression beyond 16 parameters — or beyond 8 when its rows, padded to 16 columns, do not fit the LDS — runs as a closure
-    if (desc->target == KLARA_TARGET_LOGISTIC && !logit_mfma_eligible(*desc) &&
-        (desc->ndims > 16 || (desc->ndims > 8 && (size_t)desc->logit_ndata * 17 > KLARA_LOGIT_MAX_LDS_DOUBLES))) {
-        if (desc->ndims > KLARA_CUSTOM_MAXD) return KLARA_ERR_UNSUPPORTED;
-        if (desc->monitor & KLARA_MON_HIST_LLLP) return KLARA_ERR_UNSUPPORTED;
-        const size_t n = (size_t)desc->logit_ndata, D = (size_t)desc->ndims;
-        std::vector<double> blk(2 + n * (D + 1));
-        blk[0] = desc->logit_lambda;
-        blk[1] = (double)desc->ndims * kd_log(2.0 * 3.141592653589793 * desc->logit_lambda);
-        memcpy(blk.data() + 2, desc->logit_X, n * D * sizeof(double));
-        memcpy(blk.data() + 2 + n * D, desc->logit_y, n * sizeof(double));
-        klara_desc dd = *desc;
-        dd.target = KLARA_TARGET_CUSTOM; dd.custom_src = KLARA_LOGIT_WIDE_SRC; dd.custom_data = blk.data(); dd.custom_ndata = (int64_t)blk.size();
-        dd.logit_X = nullptr; dd.logit_y = nullptr; dd.logit_ndata = 0;
-        return create_impl(&dd, out, 1);
-    }
-    if (desc->target == KLARA_TARGET_CUSTOM && pair_as_whole(desc->custom_src, desc->sampler, desc->ndims)) {
-        const std::string src2 = pair_as_whole_source(desc->custom_src);
-        klara_desc dd = *desc;
-        dd.custom_src = src2.c_str();
-        return create_impl(&dd, out);
-    }
-    if (desc->target == KLARA_TARGET_GAUSS_DENSE && desc->ndims > 128 && !dense_streamed(*desc) && !dense_split(*desc)) {
-        if (desc->ndims > KLARA_CUSTOM_MAXD) return KLARA_ERR_UNSUPPORTED;
-        if (desc->monitor & KLARA_MON_HIST_LLLP) return KLARA_ERR_UNSUPPORTED;
-        const size_t D = (size_t)desc->ndims;
-        std::vector<double> blk(1 + D * D + D, 0.0);
-        blk[0] = desc->gauss_const;
-        memcpy(blk.data() + 1, desc->gauss_prec, D * D * sizeof(double));
-        if (desc->gauss_mu) memcpy(blk.data() + 1 + D * D, desc->gauss_mu, D * sizeof(double));
-        klara_desc dd = *desc;
-        dd.target = KLARA_TARGET_CUSTOM; dd.custom_src = KLARA_DENSE_WIDE_SRC; dd.custom_data = blk.data(); dd.custom_ndata = (int64_t)blk.size();
-        dd.gauss_prec = nullptr; dd.gauss_mu = nullptr;
-        return create_impl(&dd, out, 1);
-    }
-    return create_impl(desc, out);
-}
-
-static klara_status create_impl(const klara_desc* desc, klara_handle** out, int custom_lanes)
-{
-    klara_status st = validate(desc);
-    if (st != KLARA_OK) return st;
-    int kind, G, E;
-    int custom_wpb = 4;
-    st = select_layout(*desc, &kind, &G, &E, custom_lanes, &custom_wpb);
-    if (st != KLARA_OK) return st;
-    if (desc->tuner_mode == KLARA_TUNE_POOLED && desc->sampler == KLARA_SAMPLER_SLICE) return KLARA_ERR_UNSUPPORTED;
-    if (desc->sampler == KLARA_SAMPLER_SMMALA && G != 1) return KLARA_ERR_UNSUPPORTED;     // (one chain per lane: KLARA_CUSTOM_LANES may ask for more)
-    // the logistic kernels keep the data rows (padded to E columns, + the responses) in LDS next to the 8 KB of math tables: up to
-    // 144 KB of the CU's 160 (swiss: 200 x 5 doubles = 8 KB); beyond the 56 KB a launch gets by default the launchers raise the
-    // kernel's limit, and fewer workgroups share a CU
-    if (desc->target == KLARA_TARGET_LOGISTIC && kind != 5 && (size_t)desc->logit_ndata * (size_t)(E + 1) > KLARA_LOGIT_MAX_LDS_DOUBLES)
-        return KLARA_ERR_UNSUPPORTED;
-
+    const int kind = plan.kind, G = plan.G, E = plan.E;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || desc->device < 0 || desc->device >= ndev)
         return KLARA_ERR_HIP;
@@ -612,21 +326,7 @@ static klara_status create_impl(const klara_desc* desc, klara_handle** out, int 
 
     klara_handle* h = new (std::nothrow) klara_handle();
     if (!h) return KLARA_ERR_NOMEM;
-    h->d = *desc; h->kind = kind; h->G = G; h->E = E;
-    h->custom_rows = (desc->target == KLARA_TARGET_CUSTOM && custom_lik_prior(desc->custom_src)) ? 3 : 2;
-    h->custom_wpb = custom_wpb;
-    if (desc->target == KLARA_TARGET_LOGISTIC && kind != 5) {
-        // D <= 8 parameters cannot fill a wavefront's lanes usefully, the ndata-row likelihood can: RS lanes share a chain
-        // and each takes every RS-th row (fixed by ndata alone, so results do not depend on how chains are sharded)
-        // 4 lanes from 64 rows on (round 4; rounds 1-3: 8 from 128 rows).  With the rows of an evaluation going through their stages in batches
-        // a wavefront no longer needs partners to cover its LDS round trips, so the kernels run at 2 wavefronts per SIMD with the registers
-        // of a 4-row batch, and 16 chains per wavefront share the sampler's per-wavefront work instead of 8: swiss (200 rows), 32,768 chains,
-        // same box, running sums on: 2.10e9 transitions/s at 4 lanes against 1.88e9 at 8 (gpurun_out/r4_gpu3/ab_logit.txt; profiles/README.md)
-        int rs = desc->logit_ndata >= 64 ? 4 : 1;
-        if (const char* s = getenv("KLARA_LOGIT_ROWSPLIT")) { const int v = atoi(s); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) rs = v; }
-        h->RS = rs;
-        if (rs > 1) h->kind = 2;
-    }
+    h->d = *desc; h->plan = plan;
     const size_t N = (size_t)desc->nchains, D = (size_t)desc->ndims;
     const bool pooled = desc->tuner_mode == KLARA_TUNE_POOLED;
     const size_t NT = pooled ? 1 : N;
@@ -638,30 +338,20 @@ static klara_status create_impl(const klara_desc* desc, klara_handle** out, int 
     if (desc->stream) { h->stream = (hipStream_t)desc->stream; h->own_stream = false; }
     else { CKH(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking)); h->own_stream = true; }
     CKH(hipEventCreate(&h->ev0)); CKH(hipEventCreate(&h->ev1));
-    if (h->kind == 3) {
-        h->q4_ok = q4_eligible(*desc);
-        h->np4 = (desc->ndims + 7) / 8;
-        const long long cpw = h->q4_ok ? 16 : 64 / G, groups = (desc->nchains + cpw - 1) / cpw;
-        int np = groups >= 4096 ? 2 : 1;                       // >= one full round of wavefronts (4 per SIMD) per partition
-        if (desc->nstreams >= 1 && desc->nstreams <= 4) np = desc->nstreams;
-        if (const char* s = getenv("KLARA_STREAMS")) { const int v = atoi(s); if (v >= 1 && v <= 4) np = v; }
-        if (desc->tuner_mode == KLARA_TUNE_POOLED) np = 1;     // the pooled tuner update sits between launches, on one stream
-        if (desc->acov_maxlag > 0) np = 1;                     // ... and so does the consumer of the launch's saved samples
-        if (np > groups) np = (int)groups;
-        h->nparts = np;
+    if (kind == 3) {
+        const int np = plan.nparts;
         if (np > 1) CKH(hipEventCreateWithFlags(&h->fork_ev, hipEventDisableTiming));
         for (int j = 0; j + 1 < np; ++j) {
             CKH(hipStreamCreateWithFlags(&h->side[j], hipStreamNonBlocking));
             CKH(hipEventCreateWithFlags(&h->join_ev[j], hipEventDisableTiming));
         }
         CKH(dalloc(&h->clock_probe, 4)); CKH(hipMemset(h->clock_probe, 0, 4 * sizeof(unsigned long long)));
-        if (h->q4_ok && (desc->monitor & KLARA_MON_SUMMARIES)) {
+        if (plan.q4_ok && (desc->monitor & KLARA_MON_SUMMARIES)) {
             CKH(dalloc(&h->auto_cells, 8)); CKH(dalloc(&h->auto_ctr, 4));
             if (hipHostMalloc((void**)&h->auto_mirror, 16 * sizeof(int), hipHostMallocMapped) == hipSuccess) {
                 for (int i = 0; i < 16; ++i) h->auto_mirror[i] = (i & 3) == 0 ? 1 : ((i & 3) == 2 ? -1 : 0);
                 if (hipHostGetDevicePointer((void**)&h->auto_mirror_dev, h->auto_mirror, 0) != hipSuccess) { hipHostFree(h->auto_mirror); h->auto_mirror = nullptr; h->auto_mirror_dev = nullptr; }
             } else { h->auto_mirror = nullptr; (void)hipGetLastError(); }
-            if (const char* s = getenv("KLARA_AUTO_THRESHOLD")) { const double v = atof(s); if (v >= 0.0 && v <= 1.0) h->auto_threshold = v; }
         }
     }
 
@@ -718,19 +408,15 @@ static klara_status create_impl(const klara_desc* desc, klara_handle** out, int 
         CK(upload(&h->hxc, desc->hier_xc, (size_t)desc->hier_ntimes));
     } else if (desc->target == KLARA_TARGET_CUSTOM) {
         if (desc->custom_ndata > 0) CK(upload(&h->cdata, desc->custom_data, (size_t)desc->custom_ndata));
-        if (pair_form(*desc)) {
+        if (plan.jit_pair) {
             // k_diagt instantiations for this job: fused launches always; one transition per launch where that kernel exists
-            const bool plain_ = !cnt_predicate(h->d) && desc->tuner_mode == KLARA_TUNE_PER_CHAIN && desc->tuner != KLARA_TUNER_DUAL_AVERAGING;
             const bool mon_ = (h->d.monitor & ~(uint32_t)KLARA_MON_ACCEPT) != 0, da_ = desc->tuner == KLARA_TUNER_DUAL_AVERAGING;
-            const bool tune_ = !plain_ || da_;
+            const bool tune_ = !plan.plain || da_;
             if (desc->monitor & KLARA_MON_HIST_LLLP) { free_all(h); delete h; return KLARA_ERR_INVALID_ARG; }
             const int modes[2] = { 0, 1 };
-            h->jit_pair = true;
             CK(klara_jit_create_pair(desc->custom_src, desc->sampler, desc->ndims, E / 2, G, mon_, tune_, da_, modes, (!mon_ && !tune_ && desc->sampler != KLARA_SAMPLER_SLICE) ? 2 : 1, true, &h->jit));
         } else {
-        int modes[2];
-        const int nmodes = kernel_modes(h->d, modes);           // (h->d: the monitor word with what the library turned on itself)
-        CK(klara_jit_create(desc->custom_src, desc->sampler, desc->ndims, E, G, modes, nmodes, true, &h->jit));
+            CK(klara_jit_create(desc->custom_src, desc->sampler, desc->ndims, E, G, plan.modes, plan.nmodes, true, &h->jit));
         }
     } else if (desc->target == KLARA_TARGET_LOGISTIC && kind == 5) {
         // the A fragments of both MFMA passes in the order of consumption (klara_logit_mfma.h logitm_eval), zero beyond the n rows / D columns:
@@ -804,6 +490,42 @@ static klara_status create_impl(const klara_desc* desc, klara_handle** out, int 
     return KLARA_OK;
 }
 
+extern "C" klara_status klara_create(const klara_desc* desc, klara_handle** out)
+{
+    if (!out) return KLARA_ERR_INVALID_ARG;
+    *out = nullptr;
+    klara_status st = validate(desc);
+    if (st != KLARA_OK) return st;
+    KlaraPlan plan;
+    st = klara_plan_job(*desc, klara_read_overrides(), &plan);
+    if (st != KLARA_OK) return st;
+    // a closure form: the job as a user-defined target, with the data block its closure reads
+    klara_desc dd = *desc;
+    std::vector<double> blk;
+    std::string src;
+    if (plan.rewrite == KLARA_REWRITE_LOGIT_WIDE) {            // [lambda, D log(2 pi lambda), X, y]
+        const size_t n = (size_t)desc->logit_ndata, D = (size_t)desc->ndims;
+        blk.resize(2 + n * (D + 1));
+        blk[0] = desc->logit_lambda;
+        blk[1] = (double)desc->ndims * kd_log(2.0 * 3.141592653589793 * desc->logit_lambda);
+        memcpy(blk.data() + 2, desc->logit_X, n * D * sizeof(double));
+        memcpy(blk.data() + 2 + n * D, desc->logit_y, n * sizeof(double));
+        dd.custom_src = KLARA_LOGIT_WIDE_SRC; dd.logit_X = nullptr; dd.logit_y = nullptr; dd.logit_ndata = 0;
+    } else if (plan.rewrite == KLARA_REWRITE_DENSE_WIDE) {     // [c, P, mu]
+        const size_t D = (size_t)desc->ndims;
+        blk.assign(1 + D * D + D, 0.0);
+        blk[0] = desc->gauss_const;
+        memcpy(blk.data() + 1, desc->gauss_prec, D * D * sizeof(double));
+        if (desc->gauss_mu) memcpy(blk.data() + 1 + D * D, desc->gauss_mu, D * sizeof(double));
+        dd.custom_src = KLARA_DENSE_WIDE_SRC; dd.gauss_prec = nullptr; dd.gauss_mu = nullptr;
+    } else if (plan.rewrite == KLARA_REWRITE_PAIR_AS_WHOLE) {
+        src = pair_as_whole_source(desc->custom_src);
+        dd.custom_src = src.c_str();
+    }
+    if (plan.rewrite == KLARA_REWRITE_LOGIT_WIDE || plan.rewrite == KLARA_REWRITE_DENSE_WIDE) { dd.target = KLARA_TARGET_CUSTOM; dd.custom_data = blk.data(); dd.custom_ndata = (int64_t)blk.size(); }
+    return create_impl(&dd, plan, out);
+}
+
 extern "C" klara_status klara_destroy(klara_handle* h)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;
@@ -827,7 +549,7 @@ static KParams make_params(klara_handle* h)
     p.hist = (decltype(p.hist))h->hist; p.hist_cols = h->hist_cols; p.error_flag = (decltype(p.error_flag))h->err;
     p.hist_lt = (decltype(p.hist_lt))h->hist_lt; p.hist_g = (decltype(p.hist_g))h->hist_g;
     p.hist_ll = (decltype(p.hist_ll))h->hist_ll; p.hist_lp = (decltype(p.hist_lp))h->hist_lp;
-    p.nchains = d.nchains; p.chain_offset = d.chain_offset; p.D = d.ndims; p.G = h->G; p.rs = h->RS;
+    p.nchains = d.nchains; p.chain_offset = d.chain_offset; p.D = d.ndims; p.G = h->plan.G; p.rs = h->plan.RS;
     p.pooled = d.tuner_mode == KLARA_TUNE_POOLED;
     p.seed = d.seed + h->epoch * KLARA_EPOCH_KEY_STRIDE;      // (mod 2^64)
     p.vecparam = (decltype(p.vecparam))h->vecparam; p.nleaps = d.nleaps; p.stepout = d.slice_stepout;
@@ -848,38 +570,6 @@ static KParams make_params(klara_handle* h)
     p.cdata = (decltype(p.cdata))h->cdata; p.cndata = d.custom_ndata;
     p.clock_probe = (decltype(p.clock_probe))h->clock_probe;
     return p;
-}
-
-// one wave per chain group for the init kernels and the MFMA kernels
-static dim3 grid_for(const klara_handle* h)
-{
-    if (h->kind == 6) return dim3((unsigned)((h->d.nchains + 15) / 16));          // one workgroup (G wavefronts) per tile of 16 chains
-    const long long cpw = (h->kind == 1 || h->kind == 5) ? 16 : 64 / (h->G * h->RS);
-    const long long waves = (h->d.nchains + cpw - 1) / cpw;
-    const long long wpb = h->kind == 5 ? 4 : h->kind == 1 ? (h->E > 32 ? 4 : 8) : h->custom_wpb;      // (streamed layouts: one wavefront per SIMD, workgroups of 4)
-    return dim3((unsigned)((waves + wpb - 1) / wpb));
-}
-
-// group-layout transition kernels are persistent over `groups_per_wave` chain groups (prefetch of the
-// next group's state overlaps the current group's compute); keep >= ~8 waves per SIMD of work for balance
-static dim3 grid_for_transitions(const klara_handle* h)
-{
-    const long long cpw = 64 / (h->G * h->RS);
-    const long long groups = (h->d.nchains + cpw - 1) / cpw;
-    long long gpw = 4;
-    while (gpw > 1 && groups / gpw < 8192) gpw >>= 1;
-    if (const char* s = getenv("KLARA_GROUPS_PER_WAVE")) { const long long v = atoll(s); if (v >= 1 && v <= 1024) gpw = v; }
-    const long long waves = (groups + gpw - 1) / gpw;
-    return dim3((unsigned)((waves + h->custom_wpb - 1) / h->custom_wpb));
-}
-
-static size_t lds_for(const klara_handle* h)
-{
-    if (h->kind != 1 && h->kind != 5 && h->d.target == KLARA_TARGET_LOGISTIC)        // data rows + responses + the kernel's copy of kd_log12's table (LogisticTarget::lds_bytes)
-        return sizeof(double) * (((size_t)h->d.logit_ndata * (size_t)(h->E + 1) + 1) / 2 * 2 + 256);
-    if (h->kind == 0 && h->d.target == KLARA_TARGET_CUSTOM && h->G > 1)              // staged closure: the rows of a workgroup's chains
-        return custom_stage_bytes(h->d.ndims, h->G, h->custom_rows, h->custom_wpb);
-    return 0;
 }
 
 // ---- init kernels (group layout) instantiated here
@@ -986,24 +676,26 @@ static klara_status init_common(klara_handle* h)
     }
     const int needgrad = d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_HMC || d.sampler == KLARA_SAMPLER_SMMALA;
     KParams p = make_params(h);
+    const KlaraPlan& P = h->plan;
+    const dim3 grid(P.grid_init);
     hipError_t e;
-    if (h->kind == 1) e = klara_launch_dense_init(p, h->E, h->Pfrag, h->dense_mu, needgrad, grid_for(h), st);
-    else if (h->kind == 5) e = klara_launch_logit_mfma_init(p, h->E, h->Pfrag, h->ly, h->logit_nblocks, needgrad, grid_for(h), st);
-    else if (h->kind == 6) e = klara_launch_dense_split_init(p, h->G, h->E, h->Pfrag, h->dense_mu, needgrad, grid_for(h), st);
-    else if (h->kind == 3 && h->jit_pair) e = klara_jit_launch_init(h->jit, p, needgrad, grid_for(h), 0, st);
-    else if (h->kind == 3)
-        e = h->G == 8 ? klara_launch_diagt_init(p, h->E / 2, needgrad, grid_for(h), st)
-          : h->G == 16 ? klara_launch_diagt_init_q16(p, h->E / 2, needgrad, grid_for(h), st)
-          : h->G == 32 ? klara_launch_diagt_init_q32(p, h->E / 2, needgrad, grid_for(h), st)
-                       : klara_launch_diagt_init_q64(p, h->E / 2, needgrad, grid_for(h), st);
-    else if (h->kind == 4) e = klara_launch_hiert_init(p, h->E / 2, d.hier_ntimes, needgrad, grid_for(h), st);
-    else if (d.sampler == KLARA_SAMPLER_SMMALA && d.target == KLARA_TARGET_LOGISTIC) e = klara_launch_smmala_init(p, h->E, grid_for(h), lds_for(h), st);
-    else if (d.target == KLARA_TARGET_CUSTOM) e = klara_jit_launch_init(h->jit, p, needgrad, grid_for(h), lds_for(h), st, 64 * h->custom_wpb);
+    if (P.kind == 1) e = klara_launch_dense_init(p, P.E, h->Pfrag, h->dense_mu, needgrad, grid, st);
+    else if (P.kind == 5) e = klara_launch_logit_mfma_init(p, P.E, h->Pfrag, h->ly, h->logit_nblocks, needgrad, grid, st);
+    else if (P.kind == 6) e = klara_launch_dense_split_init(p, P.G, P.E, P.lds, h->Pfrag, h->dense_mu, needgrad, grid, st);
+    else if (P.kind == 3 && P.jit_pair) e = klara_jit_launch_init(h->jit, p, needgrad, grid, 0, st);
+    else if (P.kind == 3)
+        e = P.G == 8 ? klara_launch_diagt_init(p, P.E / 2, needgrad, grid, st)
+          : P.G == 16 ? klara_launch_diagt_init_q16(p, P.E / 2, needgrad, grid, st)
+          : P.G == 32 ? klara_launch_diagt_init_q32(p, P.E / 2, needgrad, grid, st)
+                      : klara_launch_diagt_init_q64(p, P.E / 2, needgrad, grid, st);
+    else if (P.kind == 4) e = klara_launch_hiert_init(p, P.E / 2, d.hier_ntimes, needgrad, grid, st);
+    else if (d.sampler == KLARA_SAMPLER_SMMALA && d.target == KLARA_TARGET_LOGISTIC) e = klara_launch_smmala_init(p, P.E, grid, P.lds, st);
+    else if (d.target == KLARA_TARGET_CUSTOM) e = klara_jit_launch_init(h->jit, p, needgrad, grid, P.lds, st, 64 * P.custom_wpb);
     else if (d.target == KLARA_TARGET_GAUSS_DIAG)
-        e = launch_init_t<KLARA_TARGET_GAUSS_DIAG>(p, h->E, h->G, needgrad, grid_for(h), lds_for(h), st);
+        e = launch_init_t<KLARA_TARGET_GAUSS_DIAG>(p, P.E, P.G, needgrad, grid, P.lds, st);
     else if (d.target == KLARA_TARGET_HIER_NORMAL)
-        e = launch_init_t<KLARA_TARGET_HIER_NORMAL>(p, h->E, h->G, needgrad, grid_for(h), lds_for(h), st);
-    else e = launch_init_t<KLARA_TARGET_LOGISTIC>(p, h->E, h->G, needgrad, grid_for(h), lds_for(h), st);
+        e = launch_init_t<KLARA_TARGET_HIER_NORMAL>(p, P.E, P.G, needgrad, grid, P.lds, st);
+    else e = launch_init_t<KLARA_TARGET_LOGISTIC>(p, P.E, P.G, needgrad, grid, P.lds, st);
     HIPCHK(e);
     int flag = 0;
     if (h->flag_host) { HIPCHK(hipStreamSynchronize(st)); flag = __atomic_load_n(h->flag_host, __ATOMIC_ACQUIRE); }
@@ -1034,7 +726,7 @@ extern "C" klara_status klara_init_state_normal(klara_handle* h)
     KParams p = make_params(h);
     const int D = h->d.ndims;
     int E = D <= 128 ? 2 : (D <= 256 ? 4 : (D <= 512 ? 8 : 16)), G = pow2ceil((D + E - 1) / E);       // (at most 64 lanes per chain: D <= 1024)
-    if ((h->kind == 0 || h->kind == 2) && h->d.target != KLARA_TARGET_CUSTOM) { E = h->E; G = h->G; }
+    if ((h->plan.kind == 0 || h->plan.kind == 2) && h->d.target != KLARA_TARGET_CUSTOM) { E = h->plan.E; G = h->plan.G; }
     p.G = G; p.rs = 1;     // the init stream is drawn without the row split (same values, any layout)
     const long long cpw = 64 / G, waves = (h->d.nchains + cpw - 1) / cpw;
     const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
@@ -1094,31 +786,23 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
 {
     const klara_desc& d = h->d;
     const KParams* p = h->d_params;
-    // PLAIN kernels: nothing counts proposals, nothing tunes (VanillaMCTuner, not verbose)
-    const bool plain = !cnt_predicate(d) && d.tuner_mode == KLARA_TUNE_PER_CHAIN && d.tuner != KLARA_TUNER_DUAL_AVERAGING;
-    int mode = (plain ? 1 : 0) | ((plain && d.monitor == 0) ? 2 : 0);         // 3: no monitors either
-    if (mode == 3 && kl.nsteps == 1) mode = 7;                                 // one iterate! per launch
-    if (h->kind == 1) return klara_launch_dense(p, kl, d.sampler, d.tuner, plain, h->E, h->Pfrag, h->dense_mu, grid_for(h), h->stream);
-    if (h->kind == 5) return klara_launch_logit_mfma(p, kl, d.sampler, d.tuner == KLARA_TUNER_DUAL_AVERAGING, h->E, h->Pfrag, h->ly, h->logit_nblocks, grid_for(h), h->stream);
-    if (h->kind == 6) return klara_launch_dense_split(p, kl, d.sampler, d.tuner == KLARA_TUNER_DUAL_AVERAGING, h->G, h->E, d.ndims, h->Pfrag, h->dense_mu, grid_for(h), h->stream);
-    if (h->kind == 3) {
+    const KlaraPlan& P = h->plan;
+    const int mode = (P.nmodes == 2 && kl.nsteps == 1) ? P.modes[1] : P.modes[0];     // (7: one iterate! per launch)
+    const dim3 grid(P.grid_init), grid_steps(P.grid_steps);
+    if (P.kind == 1) return klara_launch_dense(p, kl, d.sampler, d.tuner, P.plain, P.E, h->Pfrag, h->dense_mu, grid, h->stream);
+    if (P.kind == 5) return klara_launch_logit_mfma(p, kl, d.sampler, d.tuner == KLARA_TUNER_DUAL_AVERAGING, P.E, h->Pfrag, h->ly, h->logit_nblocks, grid, h->stream);
+    if (P.kind == 6) return klara_launch_dense_split(p, kl, d.sampler, d.tuner == KLARA_TUNER_DUAL_AVERAGING, P.G, P.E, P.split_mw, P.lds, d.ndims, h->Pfrag, h->dense_mu, grid, h->stream);
+    if (P.kind == 3) {
         const bool unitw = h->gw == nullptr && h->gmu == nullptr, onestep = kl.nsteps == 1;   // (device copies; the host pointers are dropped at create)
         const bool mon = (d.monitor & ~(uint32_t)KLARA_MON_ACCEPT) != 0;                      // a saved-sample monitor is on
         const bool da = d.tuner == KLARA_TUNER_DUAL_AVERAGING;                                 // (HMC only: validate())
-        const bool tune = !plain || da;                                                        // something counts proposals / tunes
-        // which kernel family runs the launch (q4_ok jobs: same bits either way)
+        const bool tune = !P.plain || da;                                                      // something counts proposals / tunes
+        // which kernel family runs the launch (q4_ok jobs: same bits either way): 0: 4 lanes per chain; 1: 8 lanes; -1: decided on the device
         const bool sums = (d.monitor & KLARA_MON_SUMMARIES) != 0;
-        // slice sampler: nothing counts and no history is kept -> the lanes run out of lockstep (klara_diagt_slice.h); same draws, same bits
-        const bool slice_free = slice_free_eligible(d);
-        int force = -1;                                      // 0: 4 lanes per chain; 1: 8 lanes; -1: decided on the device
-        if (!h->q4_ok) force = 1;
-        else if (d.sampler == KLARA_SAMPLER_HMC && onestep) force = 1;   // (one transition per launch: the 8-lane single-transition kernel measured 5 % faster)
-        else if (!sums) force = 0;                           // nothing to fold: the 4-lane kernels
-        else if (d.sparse_moves == 1) force = 0;
-        else if (d.sparse_moves == 2) force = 1;
-        if (h->q4_ok && sums) if (const char* sm = getenv("KLARA_SUM_MODE")) { const int v = atoi(sm); if (v == 0 || v == 1) force = v; }
+        // (one transition per launch of HMC: the 8-lane single-transition kernel measured 5 % faster)
+        int force = d.sampler == KLARA_SAMPLER_HMC && onestep ? 1 : P.family;
         const bool query = klara_attr_query != nullptr;       // klara_get_kernel_attributes: which kernel, not a launch
-        if (query && h->q4_ok) force = h->query_lanes == 8 ? 1 : 0;
+        if (query && P.q4_ok) force = h->query_lanes == 8 ? 1 : 0;
         const long long idx = query ? h->launch_idx : h->launch_idx++;
         for (int j = 0; j < nparts; ++j) {
             long long c0, c1;
@@ -1131,8 +815,8 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
                 const long long cpw = 64 / lanes;
                 kp.group0 = c0 / cpw; kp.group_end = (c1 + cpw - 1) / cpw;
                 const long long nw = kp.group_end - kp.group0;               // one wavefront per group of cpw chains
-                const int np = lanes == 4 ? h->np4 : h->E / 2;
-                if (h->jit_pair) return klara_jit_launch_pair(h->jit, (onestep && !tune && !mon && d.sampler != KLARA_SAMPLER_SLICE) ? 1 : 0, p, kp, nw, st);
+                const int np = lanes == 4 ? P.np4 : P.E / 2;
+                if (P.jit_pair) return klara_jit_launch_pair(h->jit, (onestep && !tune && !mon && d.sampler != KLARA_SAMPLER_SLICE) ? 1 : 0, p, kp, nw, st);
                 if (lanes == 4)
                     return d.sampler == KLARA_SAMPLER_MH ? klara_launch_diagt_mh_q4(p, kp, np, onestep && !tune, unitw, mon, tune, da, ka, nw, st)
                          : d.sampler == KLARA_SAMPLER_HMC ? klara_launch_diagt_hmc_q4(p, kp, np, false, unitw, mon, tune, da, ka, nw, st)
@@ -1141,8 +825,8 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
                 switch (d.sampler) {                                                                                                          \
                 case KLARA_SAMPLER_MH: return klara_launch_diagt_mh##SUFFIX(p, kp, np, onestep && !tune, unitw, mon, tune, da, ka, nw, st);        \
                 case KLARA_SAMPLER_SLICE:                                                                                                     \
-                    if (slice_free) {                                                                                                         \
-                        const hipError_t e_ = klara_launch_diagt_slice_free##SUFFIX(p, kp, np, unitw, mon, ka, nw, st);                        \
+                    if (P.slice_free) {                                                                                                       \
+                        const hipError_t e_ = klara_launch_diagt_slice_free##SUFFIX(p, kp, np, unitw, mon, ka, nw, P.slice_machines, st);      \
                         if (e_ != hipSuccess || h->hist_lt == nullptr || query) return e_;                                                    \
                         /* the saved states' log-targets, from their saved values (klara_diagt_slice.h) */                                   \
                         const long long nsaved_ = saved_upto(d, (long long)kl.t0 + kl.nsteps) - saved_upto(d, (long long)kl.t0);              \
@@ -1155,9 +839,9 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
                 if (lanes == 8) { KLARA_DIAGT_LAUNCH() } else if (lanes == 16) { KLARA_DIAGT_LAUNCH(_q16) } else if (lanes == 32) { KLARA_DIAGT_LAUNCH(_q32) } else { KLARA_DIAGT_LAUNCH(_q64) }
 #undef KLARA_DIAGT_LAUNCH
             };
-            if (force >= 0 && !(h->q4_ok && sums)) {
-                e = go(force == 0 ? 4 : h->G, KLARA_AUTO_NONE);
-                if (h->q4_ok) h->n_launch_mode[force == 0 ? 0 : 1] += (j == 0 && !query);      // (klara_get_launch_modes: which family ran)
+            if (force >= 0 && !(P.q4_ok && sums)) {
+                e = go(force == 0 ? 4 : P.G, KLARA_AUTO_NONE);
+                if (P.q4_ok) h->n_launch_mode[force == 0 ? 0 : 1] += (j == 0 && !query);      // (klara_get_launch_modes: which family ran)
             } else {
                 // running sums on a job both kernel families can run: every launch counts its accepted proposals and leaves the
                 // decision for the next one in the partition's cell of the other parity (KAuto)
@@ -1166,7 +850,7 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
                 ka.cell_out = h->auto_cells + 2 * j + (int)((idx + 1) & 1);
                 ka.acc_ctr = h->auto_ctr + j;
                 ka.mirror = h->auto_mirror_dev ? h->auto_mirror_dev + 4 * j : nullptr;
-                ka.thr_work = (unsigned long long)(h->auto_threshold * 65536.0 * (double)(c1 - c0) * (double)kl.nsteps);
+                ka.thr_work = (unsigned long long)(P.auto_threshold * 65536.0 * (double)(c1 - c0) * (double)kl.nsteps);
                 ka.fanout = nparts == 1 ? 4 : 1;             // a whole-job launch decides for every partition
                 ka.launch_idx = (int)idx;
                 if (force >= 0) {
@@ -1202,18 +886,18 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
         }
         return hipSuccess;
     }
-    if (h->kind == 4) {
+    if (P.kind == 4) {
         const bool mon = (d.monitor & ~(uint32_t)KLARA_MON_ACCEPT) != 0;
         const bool da = d.tuner == KLARA_TUNER_DUAL_AVERAGING;
-        return klara_launch_hiert(p, kl, d.sampler, h->E / 2, d.hier_ntimes, mon, !plain || da, da, grid_for(h), h->stream);
+        return klara_launch_hiert(p, kl, d.sampler, P.E / 2, d.hier_ntimes, mon, !P.plain || da, da, grid, h->stream);
     }
-    if (d.target == KLARA_TARGET_CUSTOM) return klara_jit_launch(h->jit, mode, p, kl, grid_for_transitions(h), lds_for(h), h->stream, 64 * h->custom_wpb);
+    if (d.target == KLARA_TARGET_CUSTOM) return klara_jit_launch(h->jit, mode, p, kl, grid_steps, P.lds, h->stream, 64 * P.custom_wpb);
     switch (d.sampler) {
-    case KLARA_SAMPLER_MH: return klara_launch_mh(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
-    case KLARA_SAMPLER_MALA: return klara_launch_mala(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
-    case KLARA_SAMPLER_HMC: return klara_launch_hmc(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
-    case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
-    default: return klara_launch_slice(p, kl, mode, d.target, h->E, h->G, grid_for_transitions(h), lds_for(h), h->stream);
+    case KLARA_SAMPLER_MH: return klara_launch_mh(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    case KLARA_SAMPLER_MALA: return klara_launch_mala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    case KLARA_SAMPLER_HMC: return klara_launch_hmc(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    default: return klara_launch_slice(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     }
 }
 
@@ -1240,7 +924,7 @@ __global__ __launch_bounds__(256) void k_bm_close(const double* __restrict__ sum
 static hipError_t launch_bm_close(klara_handle* h, int nparts)
 {
     const long long N = h->d.nchains, D = h->d.ndims;
-    const int np = h->kind == 3 ? nparts : 1;
+    const int np = h->plan.kind == 3 ? nparts : 1;
     for (int j = 0; j < np; ++j) {
         long long c0 = 0, c1 = N;
         if (np > 1) part_range(h, np, j, &c0, &c1);          // (the chains the partition's transition kernels cover)
@@ -1278,11 +962,10 @@ static long long saved_upto(const klara_desc& d, long long steps)
     return sd > d.burnin ? (sd - d.burnin - 1) / d.thinning + 1 : 0;
 }
 
-static PlannedLaunch plan_launch(const klara_desc& d, const RunCursor& c, long long remaining)
+static PlannedLaunch plan_launch(const klara_desc& d, long long spl, const RunCursor& c, long long remaining)
 {
     PlannedLaunch pl;
     const bool pooled_cnt = d.tuner_mode == KLARA_TUNE_POOLED && cnt_predicate(d);
-    const long long spl = d.steps_per_launch > 0 ? d.steps_per_launch : default_steps_per_launch(d);
     long long k = remaining < spl ? remaining : spl;
     if (pooled_cnt && c.m_tot <= d.burnin) {
         const long long to_boundary = d.period - (c.m_prop % d.period);
@@ -1494,8 +1177,7 @@ extern "C" klara_status klara_run_async(klara_handle* h, int64_t nsteps)
     // one partition's kernel fills the SIMDs while the other's ramps up or drains: 12.9 vs 14.1 us per transition at 65,536 x 100).
     // A run that is a single launch is issued whole on the caller's stream: two half-size kernels that start together only split
     // the machine unevenly (16.7 vs 17.8 us per transition for 20-transition runs).
-    const long long spl_run = d.steps_per_launch > 0 ? d.steps_per_launch : default_steps_per_launch(d);
-    const int nparts = nsteps > spl_run ? h->nparts : 1;
+    const int nparts = nsteps > h->plan.steps_per_launch ? h->plan.nparts : 1;
     if (nparts > 1) {                                      // fork: the partition streams start after everything queued so far
         HIPCHK(hipEventRecord(h->fork_ev, h->stream));
         for (int j = 0; j + 1 < nparts; ++j) HIPCHK(hipStreamWaitEvent(h->side[j], h->fork_ev, 0));
@@ -1504,7 +1186,7 @@ extern "C" klara_status klara_run_async(klara_handle* h, int64_t nsteps)
     RunCursor cur = { h->steps_done, h->m_prop, h->m_tot, h->bm_count };
     hipError_t err = hipSuccess;
     while (remaining > 0 && err == hipSuccess) {
-        const PlannedLaunch pl = plan_launch(d, cur, remaining);
+        const PlannedLaunch pl = plan_launch(d, h->plan.steps_per_launch, cur, remaining);
         KLaunch kl;
         kl.group0 = 0; kl.group_end = 0x7fffffffffffffffll;
         kl.t0 = (unsigned long long)cur.steps_done;
@@ -2265,9 +1947,9 @@ extern "C" klara_status klara_get_layout(klara_handle* h, int32_t* kind, int32_t
                                          int32_t* elems_per_lane)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;
-    if (kind) *kind = h->kind;
-    if (lanes_per_chain) *lanes_per_chain = h->kind == 2 ? h->RS : h->G;
-    if (elems_per_lane) *elems_per_lane = h->E;
+    if (kind) *kind = h->plan.kind;
+    if (lanes_per_chain) *lanes_per_chain = h->plan.kind == 2 ? h->plan.RS : h->plan.G;
+    if (elems_per_lane) *elems_per_lane = h->plan.E;
     return KLARA_OK;
 }
 
@@ -2522,19 +2204,17 @@ extern "C" klara_status klara_selftest_mfma_f64_4x4x4(int32_t device, const doub
 extern "C" klara_status klara_check_custom_target(const char* src, int32_t sampler, int32_t ndims)
 {
     if (!src || sampler < KLARA_SAMPLER_MH || sampler > KLARA_SAMPLER_SMMALA || ndims <= 0) return KLARA_ERR_INVALID_ARG;
-    if (sampler == KLARA_SAMPLER_SMMALA && (ndims > 8 || !smmala_custom_source(src))) return KLARA_ERR_UNSUPPORTED;
+    // the plain fused instantiation of the layout klara_create plans for a job of this target (one chain; zeros: VanillaMCTuner per chain, no monitor)
+    klara_desc d;
+    memset(&d, 0, sizeof(d));
+    d.sampler = sampler; d.target = KLARA_TARGET_CUSTOM; d.ndims = ndims; d.nchains = 1; d.custom_src = src;
+    KlaraPlan plan;
+    const klara_status st = klara_plan_job(d, klara_read_overrides(), &plan);
+    if (st != KLARA_OK) return st;
     const int modes[1] = { 0 };
-    std::string src2;
-    if (pair_as_whole(src, sampler, ndims)) { src2 = pair_as_whole_source(src); src = src2.c_str(); }
-    if (pair_source(src)) {                                 // pair closure: the plain fused instantiation of its layout
-        if (ndims > 2 * 64 * KLARA_DIAGT_NP_MAX) return KLARA_ERR_UNSUPPORTED;
-        const int Q = ndims <= 128 ? 8 : (ndims <= 256 ? 16 : (ndims <= 512 ? 32 : 64));
-        return klara_jit_create_pair(src, sampler, ndims, (ndims + 2 * Q - 1) / (2 * Q), Q, false, false, false, modes, 1, false, nullptr);
-    }
-    if (ndims > KLARA_CUSTOM_MAXD) return KLARA_ERR_UNSUPPORTED;
-    int G = 1, E = 2, wpb = 4;
-    custom_layout(ndims, 0, custom_lik_prior(src), &G, &E, &wpb);
-    return klara_jit_create(src, sampler, ndims, E, G, modes, 1, false, nullptr);
+    if (plan.jit_pair) return klara_jit_create_pair(src, sampler, ndims, plan.E / 2, plan.G, false, false, false, modes, 1, false, nullptr);
+    const std::string whole = plan.rewrite == KLARA_REWRITE_PAIR_AS_WHOLE ? pair_as_whole_source(src) : std::string(src);
+    return klara_jit_create(whole.c_str(), sampler, ndims, plan.E, plan.G, modes, 1, false, nullptr);
 }
 
 extern "C" const char* klara_compile_log(void) { return klara_jit_log(); }
@@ -2545,13 +2225,15 @@ extern "C" klara_status klara_selftest_plan(const klara_desc* desc, int32_t nrun
     if (!run_lengths || nruns <= 0 || !nlaunches) return KLARA_ERR_INVALID_ARG;
     const klara_status st = validate(desc);
     if (st != KLARA_OK) return st;
+    KlaraPlan plan;
+    (void)klara_plan_job(*desc, klara_read_overrides(), &plan);     // (the launch length of a job klara_create would refuse is planned too)
     RunCursor cur = { 0, 0, desc->period, 0 };           // tuner_state: totproposed starts at period (samplers.jl:39-45)
     long long n = 0;
     for (int r = 0; r < nruns; ++r) {
         long long remaining = run_lengths[r];
         if (remaining < 0) return KLARA_ERR_INVALID_ARG;
         while (remaining > 0) {
-            const PlannedLaunch pl = plan_launch(*desc, cur, remaining);
+            const PlannedLaunch pl = plan_launch(*desc, plan.steps_per_launch, cur, remaining);
             if (n < capacity) {
                 if (k) k[n] = pl.k;
                 if (save_col0) save_col0[n] = pl.save_col0;

@@ -25,7 +25,7 @@
 #include "klara_dense.h"
 
 // NEW (template parameter of everything below): elements per lane and wavefront, 4 per row tile a wavefront can own — 16, 24 or 32, whichever puts the fewest
-// wavefronts on a tile (klara_launch.h klara_split_new: 4 wavefronts to D = 512, 8 beyond; the fewest wavefronts that hold the tile measured fastest)
+// wavefronts on a tile (klara_plan.h klara_split_new: 4 wavefronts to D = 512, 8 beyond; the fewest wavefronts that hold the tile measured fastest)
 #define KLARA_SPLIT_WMAX 16            // wavefronts per workgroup (D <= 1024)
 #define KLARA_SPLIT_PAD 8              // k-steps of zeros behind the stream and rows behind the mean (>= R / 4 for every ring)
 #ifndef KLARA_SPLIT_RESIDENT
@@ -90,7 +90,7 @@ __device__ __forceinline__ SplitCtx<NEW> make_sctx(const KParams& p, const doubl
     s.par = 0u;
     return s;
 }
-// (klara_split_waves / klara_split_lds_bytes: klara_launch.h — the host's launch planning and the launcher share them)
+// (W, MW and the LDS bytes: klara_plan.h klara_plan_job, planned once per job; the launchers take them from the plan)
 // mu of the lane's element e (HASMU; zero past D)
 template <int NEW>
 __device__ __forceinline__ double split_mu(const SplitCtx<NEW>& s, int e)

@@ -1,10 +1,6 @@
 // klara_diagt_slice.hip — instantiates the pair-transposed slice-sampler kernels (layout kind 3) for gfx950.
 #include "klara_launch.h"
 #include "klara_diagt_slice.h"
-#include <cstdlib>
-#ifndef KLARA_SLICEF_DEFAULT_NM
-#define KLARA_SLICEF_DEFAULT_NM 1     // (same box, 65,536 x 100: 9.7e10 coordinate updates/s with one machine per lane, 9.5e10 with two: profiles/r5_ab_slice.txt)
-#endif
 
 #define KLARA_DIAGT_SLICE_CASE(NP_)                                                                                       \
     case NP_:                                                                                                              \
@@ -26,13 +22,12 @@ hipError_t KLARA_DIAGT_FN(klara_launch_diagt_slice)(const KParams* p, const KLau
     return e_;
 }
 
-// untuned jobs without a history monitor: every lane takes its element pairs through the whole launch on its own (klara_diagt_slice.h)
-hipError_t KLARA_DIAGT_FN(klara_launch_diagt_slice_free)(const KParams* p, const KLaunch& kl, int NP, bool unitw, bool mon, const KAuto& ka, long long nwaves, hipStream_t st)
+// untuned jobs without a history monitor: every lane takes its element pairs through the whole launch on its own (klara_diagt_slice.h), nm = 1 or 2 machines each
+hipError_t KLARA_DIAGT_FN(klara_launch_diagt_slice_free)(const KParams* p, const KLaunch& kl, int NP, bool unitw, bool mon, const KAuto& ka, long long nwaves, int nm, hipStream_t st)
 {
     const bool sums = mon;      // (template flag SUMS: a saved-sample monitor — running sums and / or value history — is on)
     if (NP < 1 || NP > KLARA_SLICEF_MAXNP) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((nwaves + 3) / 4)), blk(256);
-    static const int nm = getenv("KLARA_SLICE_MACHINES") ? atoi(getenv("KLARA_SLICE_MACHINES")) : KLARA_SLICEF_DEFAULT_NM;
     // dynamic LDS: the widths of the job's 2 NP Q element slots, and weights + means for a non-unit diagonal
     const size_t lds = (size_t)(unitw ? 1 : 3) * 2 * NP * KLARA_DIAGT_Q * sizeof(double);
 #define KLARA_SLICEF_GO(U, S)                                                                                          \

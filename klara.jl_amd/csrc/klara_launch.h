@@ -45,34 +45,11 @@ hipError_t klara_launch_logit_mfma(const KParams* p, const KLaunch& kl, int samp
                                    dim3 grid, hipStream_t st);
 hipError_t klara_launch_logit_mfma_init(const KParams& p, int NE, const double* F, const double* ypad, int nblocks, int needgrad, dim3 grid, hipStream_t st);
 int klara_logit_mfma_rbt();
-// dense Gaussian on a workgroup of W = 4 ceil(ceil(D / 16) / 16) wavefronts per tile of 16 chains (layout kind 6, klara_dense_split.h): 257 <= D <= 1024; MH, MALA, HMC
-// elements per lane and wavefront of the split dense layout (4 per row tile of P a wavefront can own): 16, 24 or 32 — whichever puts the FEWEST wavefronts on a
-// tile (the smaller one on a tie): the fewest wavefronts that hold the tile measured fastest at every size (profiles/r6_dense_split.txt), as long as their
-// registers are not short — so 257 <= D <= 384: 24 (4 wavefronts), 385 .. 512: 32 (4), 513 .. 768: 24 (8), 769 .. 1024: 32 (8; 24 there would be 12 wavefronts at
-// 168 registers with scratch: measured slower than 16).  KLARA_SPLIT_NEW=16|24|32 forces one.
-static inline int klara_split_new(int D)
-{
-    const int MT = (D + 15) / 16;
-    if (const char* e = getenv("KLARA_SPLIT_NEW")) { const int v = atoi(e); if (v == 16 || v == 24 || v == 32) return v; }
-    int best = 16, wbest = 4 * ((MT + 15) / 16);
-    for (int n = 24; n <= 32; n += 8) { const int w = 4 * ((MT + n - 1) / n); if (w < wbest && w <= 8) { best = n; wbest = w; } }
-    return best;
-}
-// wavefronts per tile of 16 chains: whole SIMD rounds, at most klara_split_new / 4 row tiles of P per wavefront
-static inline int klara_split_waves(int D)
-{
-    const int MT = (D + 15) / 16, n = klara_split_new(D), w = 4 * ((MT + n - 1) / n);
-    if (const char* e = getenv("KLARA_SPLIT_W")) { const int v = atoi(e); if (v >= w && v <= 16 && v % 4 == 0) return v; }      // (measurements: more wavefronts, fewer tiles each)
-    return w;
-}
-// LDS bytes of a workgroup: xb (4 MT rows of 64 doubles) + the partial sums (the 8 KB of detmath tables are static)
-static inline size_t klara_split_lds_bytes(int D)
-{
-    const size_t MT = ((size_t)D + 15) / 16;
-    return sizeof(double) * (4 * MT * 64 + 2 * 3 * (size_t)klara_split_waves(D) * 16);
-}
-hipError_t klara_launch_dense_split(const KParams* p, const KLaunch& kl, int sampler, bool da, int W, int NEW, int D, const double* Pfrag, bool hasmu, dim3 grid, hipStream_t st);
-hipError_t klara_launch_dense_split_init(const KParams& p, int W, int NEW, const double* Pfrag, bool hasmu, int needgrad, dim3 grid, hipStream_t st);      // row tiles per block the kernels were built for
+// dense Gaussian on a workgroup of W wavefronts per tile of 16 chains (layout kind 6, klara_dense_split.h): 257 <= D <= 1024; MH, MALA, HMC, slice.
+// W, NEW (elements per lane and wavefront), MW (registers for MW wavefronts per SIMD) and the workgroup's dynamic LDS bytes come from the job's plan (klara_plan.h)
+hipError_t klara_launch_dense_split(const KParams* p, const KLaunch& kl, int sampler, bool da, int W, int NEW, int MW, size_t lds, int D, const double* Pfrag, bool hasmu, dim3 grid,
+                                   hipStream_t st);
+hipError_t klara_launch_dense_split_init(const KParams& p, int W, int NEW, size_t lds, const double* Pfrag, bool hasmu, int needgrad, dim3 grid, hipStream_t st);
 
 // pair-transposed diagonal-Gaussian kernels (layout kind 3, klara_diagt.h).  The translation units klara_diagt_*.hip are
 // compiled four times: Q = 8 lanes per chain (17 <= D <= 128, NP = ceil(D/16) in 2..8), Q = 16 (129 <= D <= 256), Q = 32
@@ -96,7 +73,7 @@ hipError_t klara_launch_dense_split_init(const KParams& p, int W, int NEW, const
     hipError_t klara_launch_diagt_mala##SUFFIX(const KParams* p, const KLaunch& kl, int NP, bool onestep, bool unitw, bool mon, bool tune, bool da, const KAuto& ka, long long nwaves, hipStream_t st); \
     hipError_t klara_launch_diagt_hmc##SUFFIX(const KParams* p, const KLaunch& kl, int NP, bool onestep, bool unitw, bool mon, bool tune, bool da, const KAuto& ka, long long nwaves, hipStream_t st);  \
     hipError_t klara_launch_diagt_slice##SUFFIX(const KParams* p, const KLaunch& kl, int NP, bool unitw, bool mon, bool tune, const KAuto& ka, long long nwaves, hipStream_t st);                      \
-    hipError_t klara_launch_diagt_slice_free##SUFFIX(const KParams* p, const KLaunch& kl, int NP, bool unitw, bool mon, const KAuto& ka, long long nwaves, hipStream_t st);                           \
+    hipError_t klara_launch_diagt_slice_free##SUFFIX(const KParams* p, const KLaunch& kl, int NP, bool unitw, bool mon, const KAuto& ka, long long nwaves, int nm, hipStream_t st);                   \
     hipError_t klara_launch_diagt_hist_lt##SUFFIX(const KParams* p, const KLaunch& kl, int NP, bool unitw, long long col0, int ncols, long long ngroups, hipStream_t st);                              \
     hipError_t klara_launch_diagt_init##SUFFIX(const KParams& p, int NP, int needgrad, dim3 grid, hipStream_t st);
 KLARA_DIAGT_DECLARE()

@@ -25,7 +25,7 @@
 // lane's rows ascending, then (q0 + q1) + (q2 + q3); p.p likewise over the lane's elements.  Padding rows (>= n) and columns (>= D) are zeros in
 // the stream: they add exact zeros to every chain; a padding row's softplus term is masked.
 // MH, MALA, HMC (Vanilla / AcceptanceRate per chain or pooled / dual averaging) and the slice sampler (a probe = pass 1 + the rows; the chains of a tile out
-// of lockstep), every monitor of klara_dense_big.h.  The likelihood / prior history keeps the closure form.
+// of lockstep), every monitor of klara_dense_big.h.  A job with the likelihood / prior history is refused (KLARA_ERR_UNSUPPORTED).
 #pragma once
 #include "klara_dense_big.h"
 

@@ -481,6 +481,33 @@ def test_smaller_dense_targets_on_the_split_layout(name, monkeypatch):
     eng.close()
 
 
+def test_a_handle_keeps_its_plan_when_the_environment_changes(monkeypatch):
+    """klara_create plans a job once: KLARA_SPLIT_W set after the handle exists changes neither its layout nor the kernel it runs (nor the
+    registers MW the workgroup's LDS leaves room for), and the run gives the bits of the same job with the environment left alone.  (Only ever
+    toward MORE wavefronts: a library that re-reads the switch at launch would then over-size the LDS, never under-size it.)"""
+    monkeypatch.delenv("KLARA_SPLIT_W", raising=False)
+    case = cases.make_case("hmc_dense_d300_split")
+
+    def run(change_env):
+        eng = K.Engine(**cases.engine_kwargs(case))
+        layout, attrs = eng.layout(), eng.kernel_attributes()
+        if change_env:
+            monkeypatch.setenv("KLARA_SPLIT_W", "16")
+        assert eng.layout() == layout and eng.kernel_attributes() == attrs, (change_env, layout, eng.layout(), attrs, eng.kernel_attributes())
+        eng.init_state_normal()
+        eng.run(case["nsteps"])
+        x, lt, g = eng.state()
+        out = (layout, attrs, eng.accept_mask(), x, lt, g)
+        eng.close()
+        monkeypatch.delenv("KLARA_SPLIT_W", raising=False)
+        return out
+
+    ref, moved = run(False), run(True)
+    assert ref[0] == (6, 4, 24) and ref[0] == O.split_dense_layout(300)
+    assert ref[:2] == moved[:2]
+    assert all(np.array_equal(a, b) for a, b in zip(ref[2:], moved[2:]))
+
+
 @pytest.mark.parametrize("name", ["pair_quartic_slice_d100", "pair_banana_slice_d37", "pair_indexed_slice_d300", "pair_indexed_slice_d40_whole"])
 def test_slice_sampler_on_pair_closures_runs_on_the_few_lanes_kernels(name, monkeypatch):
     """Round 6: a pair closure under the slice sampler (rounds 1-4: refused; round 5: summed by the library and run as a whole-vector closure, every probe a full

@@ -865,6 +865,23 @@ def test_launch_planning_is_pure_host_logic(klib, seed):
             assert c + inside <= rcols, (a, b, c, inside, rcols)
 
 
+def test_launch_length_follows_the_environment_of_each_planning_call(klib, monkeypatch):
+    """A plain slice job on the diagonal Gaussian (D = 100) runs the free-running kernel at KLARA_DEFAULT_STEPS_PER_LAUNCH_SLICE transitions per
+    launch, and round 4's lockstep kernel (KLARA_SLICE_LOCKSTEP) at KLARA_DEFAULT_STEPS_PER_LAUNCH.  Every planning call reads the switches
+    anew: the first value a process sees is not kept for later jobs."""
+    widths = np.ones(100)
+    kw = dict(sampler=L.SAMPLER_SLICE, ndims=100, steps_per_launch=0, slice_widths=widths.ctypes.data_as(C.POINTER(C.c_double)))
+    lengths = []
+    for lockstep in (False, True, False):
+        if lockstep:
+            monkeypatch.setenv("KLARA_SLICE_LOCKSTEP", "1")
+        else:
+            monkeypatch.delenv("KLARA_SLICE_LOCKSTEP", raising=False)
+        k, _, _, _ = _plan(klib, [256], **kw)
+        lengths.append(int(k[0]))
+    assert lengths == [L.DEFAULT_STEPS_PER_LAUNCH_SLICE, L.DEFAULT_STEPS_PER_LAUNCH, L.DEFAULT_STEPS_PER_LAUNCH_SLICE]
+
+
 def _build_c_example(tmp_path):
     import subprocess
     exe = tmp_path / "readme_job"
