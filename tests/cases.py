@@ -261,6 +261,16 @@ def _split_cases():
 SPLIT_CASES = {k: (v[0], dict(v[1])) for k, v in _split_cases().items()}
 
 
+def rank_one_precision(d, rng):
+    """A dense positive definite precision from element-wise operations only (no matrix product, whose summation order is the BLAS's): diagonal in
+    [1, 2) plus three dense rank-one terms, every entry non-zero.  Draws d uniforms, then 3 x d normals from `rng`."""
+    pm = np.diag(1.0 + rng.random(d))
+    for _ in range(3):
+        u = rng.standard_normal(d)
+        pm = pm + np.outer(u, u) * (0.4 / d)
+    return pm
+
+
 def make_case(name):
     """name -> dict(engine kwargs..., target=<family object>, x0=None|array)."""
     c = {}
@@ -422,10 +432,7 @@ def make_case(name):
         rng = np.random.default_rng(2000 + d)
         # (a precision matrix built from element-wise operations only: a matrix product takes whatever summation order the box's BLAS has, and the golden
         # fixtures of these cases must not depend on the box — diagonal + three dense rank-one terms: every entry non-zero, positive definite)
-        pm = np.diag(1.0 + rng.random(d))
-        for _ in range(3):
-            u = rng.standard_normal(d)
-            pm = pm + np.outer(u, u) * (0.4 / d)
+        pm = rank_one_precision(d, rng)
         mu = rng.standard_normal(d) if "_mean" in name else None
         t = K.GaussDenseTarget(pm, const=0.75, mu=mu)
         n = kw.pop("nchains", 21)

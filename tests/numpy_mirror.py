@@ -12,7 +12,7 @@ What is restated here, and from where:
   * the tuning block iterate/MALA.jl:130-152 / HMC.jl:203-224 with tuners.jl:27-32 and AcceptanceRateMCTuner.jl:9,46;
   * the save rule BasicMCJob.jl:219-238 with BasicMCRange.jl:17-36, mean(chain) stats/mean.jl:7-11;
   * the targets: README.md:23,155 (-dot(z,z)), the MvNormal closures of test/BasicContMuvParameter.jl, the swiss logistic regression
-    doc/examples/swiss/MALA/analytical.jl:11-18, and the builder-defined dense Gaussian.
+    doc/examples/swiss/MALA/analytical.jl:11-18, and the builder-defined dense Gaussian, hierarchical normal model and pair quartic.
 """
 import math
 
@@ -94,6 +94,26 @@ def logistic_target(X, y, lam):
     def grad(p):     # :17-18
         xp = X @ p
         return X.T @ (y - 1.0 / (1.0 + np.exp(-xp))) - p / lam
+
+    return lt, grad
+
+
+def pair_quartic_target(c, k, d):
+    """The coupled quartic on element pairs (tests/cases.py SRC_PAIR_QUARTIC; BUILDER-DEFINED, not a target of the reference):
+    lt = -sum_i (x_i^2 / 2 + c x_i^4) - k/2 sum_P (x_{2P+1} - x_{2P})^2 over the floor(d / 2) whole pairs — the last coordinate of an odd d is a half
+    pair and has no coupling term.  Written from that formula with whole-vector NumPy operations; the gradient by hand from it."""
+    m = d // 2
+
+    def lt(x):
+        diff = x[1:2 * m:2] - x[0:2 * m:2]
+        return float(-np.sum(0.5 * x ** 2 + c * x ** 4) - 0.5 * k * np.sum(diff ** 2))
+
+    def grad(x):
+        diff = x[1:2 * m:2] - x[0:2 * m:2]
+        g = -(x + 4.0 * c * x ** 3)
+        g[0:2 * m:2] += k * diff
+        g[1:2 * m:2] -= k * diff
+        return g
 
     return lt, grad
 

@@ -555,18 +555,93 @@ def test_slice_sampler_on_pair_closures_with_counting_tuners_and_histories(extra
 def test_logistic_beyond_16_parameters_closure_form_still_matches(name, monkeypatch):
     """Round 6 moved the logistic regression beyond 16 parameters (and 9 .. 16 with rows that do not fit the LDS) onto the matrix cores; the run-time compiled
     closure form of rounds 1-5 (one chain per lane, all rows on it) remains behind KLARA_LOGIT_NO_MFMA=1: both forms against the oracle in their own summation
-    orders (layout kind 5: row sums over 4 lane-quarters; kind 0 on one lane), bit for bit — and with the SAME gradients (the fma chains are the same)."""
+    orders (layout kind 5: row sums over 4 lane-quarters; kind 0 on one lane), bit for bit — and with the SAME states and gradients in the two forms (the fma chains of the
+    gradient are the same; the oracle's two orders give equal bits on the CPU for these cases; only the log-target's row sum differs.  The slice sampler holds no gradient)."""
     case = cases.make_case(name)
     eng, job = _run_pair(case)
     assert eng.layout()[0] == 5
     _assert_same(eng, job, case)
-    g5 = eng.state()[2]
+    x5, _, g5 = eng.state()
     eng.close()
     monkeypatch.setenv("KLARA_LOGIT_NO_MFMA", "1")
     eng, job = _run_pair(case)
     assert eng.layout()[:2] == (0, 1)
     _assert_same(eng, job, case)
+    if case["sampler"] in (L.SAMPLER_MALA, L.SAMPLER_HMC):
+        x0_, _, g0 = eng.state()
+        assert np.array_equal(x5, x0_), (name, "the states of the two forms differ", float(np.max(np.abs(x5 - x0_))))
+        assert np.array_equal(g5, g0), (name, "the gradients of the two forms differ", float(np.max(np.abs(g5 - g0))))
     eng.close()
+
+
+def _close(a, b, rel):
+    """tests/test_gpu_literal.py's measure: |a - b| <= rel (|b| + mean |b|) everywhere"""
+    a, b = np.asarray(a, float), np.asarray(b, float)
+    return bool(np.all(np.abs(a - b) <= rel * (np.abs(b) + np.abs(b).mean())))
+
+
+def _run_on(case):
+    eng = K.Engine(**cases.engine_kwargs(case))
+    layout = tuple(eng.layout())
+    if case["x0"] is None:
+        eng.init_state_normal()
+    else:
+        eng.set_state(case["x0"])
+    eng.run(case["nsteps"])
+    out = (layout, eng.accept_mask()) + tuple(eng.state())
+    eng.close()
+    return out
+
+
+def _assert_two_layouts_agree(a, b, name):
+    """The same job on two kernel families draws the same normals and uniforms and differs in summation order only.  What the oracle's two orders show on the CPU for
+    each of the pairs below (all chains, all transitions): every accept decision identical, states and gradients bit-equal, log-targets different in their last
+    bits (below 4e-15 by _close's measure).  No oracle is involved here: a kernel family and its oracle branch that are wrong in the same way still differ from the other family."""
+    (_, ma, xa, lta, ga), (_, mb, xb, ltb, gb) = a, b
+    assert 0.2 < ma.mean() < 0.98, (name, ma.mean())
+    assert np.array_equal(ma, mb), (name, "accept decisions differ between the two layouts", np.argwhere(ma != mb)[:5])
+    assert np.array_equal(xa, xb), (name, "states differ between the two layouts", float(np.max(np.abs(xa - xb))))
+    assert np.array_equal(ga, gb), (name, "gradients differ between the two layouts", float(np.max(np.abs(ga - gb))))
+    assert _close(lta, ltb, 1e-12), (name, float(np.max(np.abs(lta - ltb))))
+
+
+@pytest.mark.parametrize("sampler,kw", [(L.SAMPLER_HMC, dict(leapstep=0.3, nleaps=10)), (L.SAMPLER_MALA, dict(driftstep=0.25))], ids=["hmc", "mala"])
+def test_dense_d256_streamed_layout_against_workgroup_split_layout(sampler, kw, monkeypatch):
+    """dense D = 256: the streamed layout (kind 1, k_dense_big) against KLARA_DENSE_SPLIT=1 (kind 6, k_dense_split), 2,043 chains x 50 transitions"""
+    monkeypatch.delenv("KLARA_DENSE_SPLIT", raising=False)
+    t = K.GaussDenseTarget(cases.rank_one_precision(256, np.random.default_rng(2256)), const=0.75)
+    case = dict(sampler=sampler, target=t, nchains=2048 - 5, nsteps=50, x0=None, seed=20260927, name="dense_d256_two_layouts", **kw)
+    a = _run_on(case)
+    monkeypatch.setenv("KLARA_DENSE_SPLIT", "1")
+    b = _run_on(case)
+    assert a[0] == (1, 4, 64) and b[0] == O.split_dense_layout(256) and b[0][0] == 6, (a[0], b[0])
+    _assert_two_layouts_agree(a, b, case["name"])
+
+
+def test_logistic_d20_matrix_core_layout_against_closure_form(monkeypatch):
+    """logistic regression D = 20, 200 rows, MALA: the matrix cores (kind 5, k_logit_mfma) against KLARA_LOGIT_NO_MFMA=1 (kind 0: one chain per lane)"""
+    monkeypatch.delenv("KLARA_LOGIT_NO_MFMA", raising=False)
+    X, y = cases.synthetic_logit(200, 20)
+    n = 2048 - 5
+    case = dict(sampler=L.SAMPLER_MALA, target=K.LogisticTarget(X, y, 10.0), driftstep=0.05, nchains=n, nsteps=50, seed=20260927, name="logit_d20_two_layouts",
+                x0=0.1 * np.random.default_rng(20).standard_normal((n, 20)))
+    a = _run_on(case)
+    monkeypatch.setenv("KLARA_LOGIT_NO_MFMA", "1")
+    b = _run_on(case)
+    assert a[0] == (5, 4, 8) and b[0][:2] == (0, 1), (a[0], b[0])
+    _assert_two_layouts_agree(a, b, case["name"])
+
+
+def test_diagonal_d100_pair_transposed_layout_against_group_layout(monkeypatch):
+    """diagonal Gaussian D = 100, MALA: the pair-transposed layout (kind 3, k_diagt) against the group layout forced with KLARA_LAYOUT_KIND=0"""
+    monkeypatch.delenv("KLARA_LAYOUT_KIND", raising=False)
+    mv = K.GaussDiagTarget.mvnormal(np.linspace(-2.0, 3.0, 100), np.linspace(0.5, 2.0, 100))
+    case = dict(sampler=L.SAMPLER_MALA, target=mv, driftstep=0.3, nchains=2048 - 5, nsteps=50, x0=None, seed=20260927, name="diag_d100_two_layouts")
+    a = _run_on(case)
+    monkeypatch.setenv("KLARA_LAYOUT_KIND", "0")
+    b = _run_on(case)
+    assert a[0][:2] == (3, 8) and b[0][0] == 0, (a[0], b[0])
+    _assert_two_layouts_agree(a, b, case["name"])
 
 
 # Vanilla / AcceptanceRate jobs on even-D diagonal Gaussians run on the pair-transposed layout by default (HMC on the
