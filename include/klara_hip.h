@@ -372,6 +372,30 @@ klara_status klara_get_chain_mcvar(klara_handle* h, int64_t batchlen, int64_t ma
 klara_status klara_get_chain_acov_mcvar(klara_handle* h, double* mcvar_imse, double* mcvar_ipse, int64_t* nsamples_out);
 /* Geyer's initial positive sequence estimator over the stored history (mcvar.jl:137-158), maxlag <= 0: n - 1 */
 klara_status klara_get_chain_mcvar_ipse(klara_handle* h, int64_t maxlag, double* mcvar_ipse);
+/* Zero-variance control variates lzv / qzv (src/stats/variance/zv.jl:9-84, Mira, Solgi & Imparato 2013) of EVERY chain over the stored
+ * value and gradlogtarget histories (KLARA_MON_HISTORY | KLARA_MON_HIST_GRAD, no ring, >= 2 saved steps: else KLARA_ERR_STATE).
+ * z = -gradlogtarget / 2; the control variates f are z (order 1, K = ndims) or z_i | 2 z_i x_i - 1 | x_i z_j + x_j z_i, i < j
+ * (order 2, K = ndims (ndims + 3) / 2); the coefficients solve  S_ff a = -S_fx  with the centred cross-products of the chain
+ * (zv.jl: a[:, i] = -inv(cov(f)) cov(f, x_i)) by Cholesky on the device; the corrected series is x + f a.  K > KLARA_ZV_MAX_TERMS:
+ * KLARA_ERR_UNSUPPORTED.  pooled != 0: one coefficient matrix from the concatenation of all chains' samples of this handle; zv_mean and
+ * zv_var stay per chain.  info: 0, 1 (a Cholesky pivot was not a positive finite number, e.g. a chain that never moved), 2 (fewer than
+ * K + 2 samples); in both cases the chain's outputs are NaN and the call still returns KLARA_OK. */
+#define KLARA_ZV_LINEAR 1
+#define KLARA_ZV_QUADRATIC 2
+#define KLARA_ZV_MAX_TERMS 128
+klara_status klara_get_chain_zv(klara_handle* h, int32_t order, int32_t pooled,
+                                double* coef,     /* per chain: nchains x K x D row-major, coef[c][k][i] = a[k, i]; pooled: K x D; may be NULL */
+                                double* zv_mean,  /* nchains x D, may be NULL */
+                                double* zv_var,   /* nchains x D, may be NULL */
+                                int32_t* info,    /* nchains (pooled: every entry the same), may be NULL */
+                                int64_t* nsamples_out);
+/* chain + f * a of one chain in NState layout (D x n), zv.jl's first return value; coef NULL: the chain's own coefficients, else K x D given (e.g. the pooled ones) */
+klara_status klara_get_chain_zv_series(klara_handle* h, int64_t local_chain, int32_t order, const double* coef,
+                                       double* value, int64_t capacity_cols, int64_t* ncols_out);
+/* lzv(s) / qzv(s) of ONE chain, both of zv.jl's return values from one fit: its own coefficients (coef: K x D row-major), info (0, 1, 2 as above) and
+ * the corrected series (value: NState layout, D x n); each of coef, info, value may be NULL */
+klara_status klara_get_chain_zv_one(klara_handle* h, int64_t local_chain, int32_t order, double* coef, int32_t* info,
+                                    double* value, int64_t capacity_cols, int64_t* ncols_out);
 /* Streaming form of mcvar(v, Val{:bm}) (src/stats/variance/mcvar.jl:35-41: batchlen * var(batch means) / (nbatches *
  * batchlen)) for klara_desc.bm_batchlen > 0: batch means are formed from the running sums at every batch boundary and
  * their mean / sum of squared deviations are updated in place (Welford), so no history is stored — 3 x nchains x ndims

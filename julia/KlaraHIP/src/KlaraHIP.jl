@@ -36,7 +36,7 @@ import Distributions
 import Distributions: Continuous, Multivariate
 import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
-       chainvalue, chainmeans, chainacceptance, chainmcvar_bm, streamkey, launchmodes, shaderclock, check_custom_target,
+       chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
@@ -400,6 +400,26 @@ function chainmcvar_bm(job::HIPMCJob)
     v = newarray(Float64, job.ndims, job.nchains); nb = Ref{Clonglong}(0)
     check(ccall((:klara_get_chain_bm, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Clonglong}), job.handle, v, nb), "klara_get_chain_bm")
     (v, nb[])
+end
+# Zero-variance control variates of EVERY chain on the device (klara_get_chain_zv; stats/variance/zv.jl:16-34, 50-80), from the stored value and
+# gradlogtarget (outopts :monitor => [:value, :gradlogtarget]): (mean of chain + f a: D x N, its sample variance: D x N, coefficients, info).
+# The coefficients come as the C ABI lays them out, a[i, k, c] = zv.jl's a[k, i] of chain c (D x K x N; pooled=true: one D x K matrix fitted to
+# all chains' samples together); info[c] is 0, 1 (singular) or 2 (fewer than K + 2 samples) — such a chain's columns are NaN.
+# Klara's own lzv / qzv are NOT redefined here: `lzv(output(job, c))` runs the reference's code on one chain's NState.
+function chainzv(job::HIPMCJob, order::Integer, pooled::Bool)
+    d = job.ndims
+    k = order == 1 ? d : div(d * (d + 3), 2)
+    a = pooled ? newarray(Float64, d, k) : newarray(Float64, d, k, job.nchains)
+    m = newarray(Float64, d, job.nchains); v = similar(m); info = newarray(Int32, job.nchains); n = Ref{Clonglong}(0)
+    check(ccall((:klara_get_chain_zv, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ref{Clonglong}),
+                job.handle, order, pooled ? 1 : 0, a, m, v, info, n), "klara_get_chain_zv")
+    (m, v, a, info)
+end
+function chainlzv(job::HIPMCJob; pooled=false)
+    chainzv(job, 1, pooled)
+end
+function chainqzv(job::HIPMCJob; pooled=false)
+    chainzv(job, 2, pooled)
 end
 # the Philox key the job draws from and the number of resets so far (klara_hip.h klara_reset)
 function streamkey(job::HIPMCJob)

@@ -9,7 +9,7 @@ from .engine import CustomTarget, Engine, GaussDenseTarget, GaussDiagTarget, Hie
 from .api import (  # noqa: F401
     HMC, MALA, MH, SMMALA, AcceptanceRateMCTuner, DualAveragingMCTuner, BasicContMuvParameter, BasicMCJob, BasicMCRange, GenericModel,
     MuvChains, SliceSampler, VanillaMCTuner, acceptance, chain_ess, chain_iact, chain_mcvar, erf_rate_score, likelihood_model, logistic, logistic_rate_score,
-    mcvar_iid, mean, output, reset, run,
+    mcvar_iid, mean, output, reset, run, chain_lzv, chain_qzv, lzv, qzv,
 )
 from .distributed import (CommBootstrapTimeout, KlaraComm, allreduce_moments, allreduce_summaries, bootstrap_comm, gather_engine_moments_klara,  # noqa: F401
                           gather_engine_summaries, shard_chains, torch_broadcast_bytes)  # noqa: F401

@@ -332,6 +332,50 @@ def chain_iact(chains: MuvChains, vtype: str = "imse", batchlen: int = 100, maxl
     return v / iid
 
 
+def _zv_engine(chains: MuvChains, name: str):
+    eng = chains._job.engine
+    missing = [f for f, bit in (("value", L.MON_HISTORY), ("gradlogtarget", L.MON_HIST_GRAD)) if not (eng.monitor & bit)]
+    if missing:
+        raise ValueError(f"{name} needs the stored value and gradlogtarget of every saved step: add {' and '.join(repr(m) for m in missing)} "
+                         f"to outopts monitor (missing: {', '.join(missing)})")
+    return eng
+
+
+def _chain_zv(chains: MuvChains, order: int, pooled: bool, name: str):
+    eng = _zv_engine(chains, name)
+    coef, zm, zv, info, _ = eng.chain_zv(order, pooled)
+    return zm, zv, coef, info
+
+
+def chain_lzv(chains: MuvChains, pooled: bool = False):
+    """lzv (stats/variance/zv.jl:16-34) for EVERY chain at once, on the device over the stored value and gradlogtarget histories:
+    (zv_mean (nchains x D), zv_var (nchains x D), a (nchains x D x D; pooled: D x D), info (nchains)) — mean and sample variance of the
+    corrected series chain + z a with z = -gradlogtarget / 2.  pooled=True fits ONE coefficient matrix to the concatenation of all
+    chains' samples (many short replicas); means and variances stay per chain.  info 1 (singular, e.g. a chain that never moved) or
+    2 (fewer than K + 2 samples) marks chains whose outputs are NaN."""
+    return _chain_zv(chains, L.ZV_LINEAR, pooled, "chain_lzv")
+
+
+def chain_qzv(chains: MuvChains, pooled: bool = False):
+    """qzv (zv.jl:50-80) for every chain at once: as chain_lzv with the K = D (D + 3) / 2 quadratic control variates (D <= 14)."""
+    return _chain_zv(chains, L.ZV_QUADRATIC, pooled, "chain_qzv")
+
+
+def _zv_one(chains: MuvChains, chain: int, order: int, name: str):
+    series, a, _ = _zv_engine(chains, name).chain_zv_one(chain, order)      # one fit of that chain on the device
+    return series.T, a
+
+
+def lzv(chains: MuvChains, chain: int = 0):
+    """lzv(s::ParameterNState{Continuous, Multivariate}) (zv.jl:38) of chain `chain`: (chain + z a (n x D), a (D x D)), from the device."""
+    return _zv_one(chains, chain, L.ZV_LINEAR, "lzv")
+
+
+def qzv(chains: MuvChains, chain: int = 0):
+    """qzv(s::ParameterNState{Continuous, Multivariate}) (zv.jl:84) of chain `chain`: (chain + qz a (n x D), a (K x D)), from the device."""
+    return _zv_one(chains, chain, L.ZV_QUADRATIC, "qzv")
+
+
 def acceptance(chains: MuvChains, diagnostics: bool = True) -> np.ndarray:
     """acceptance(s::MultivariateParameterNState; key=:accept) — stats/acceptance.jl:28-34:
     mean of the accept diagnostics over the saved steps (per chain)."""

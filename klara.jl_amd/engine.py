@@ -429,6 +429,49 @@ class Engine:
         L.check(self._lib.klara_get_chain_mcvar_ipse(self._h, int(maxlag), out.ctypes.data), "klara_get_chain_mcvar_ipse")
         return out
 
+    def zv_nterms(self, order: int) -> int:
+        """Control variates of lzv (order 1: ndims) / qzv (order 2: ndims (ndims + 3) / 2, zv.jl:52)."""
+        if order not in (L.ZV_LINEAR, L.ZV_QUADRATIC):
+            raise ValueError(f"order must be 1 (lzv) or 2 (qzv), not {order!r}")
+        return self.ndims if order == L.ZV_LINEAR else self.ndims * (self.ndims + 3) // 2
+
+    def chain_zv(self, order: int, pooled: bool = False, want=("coef", "mean", "var")):
+        """(coef, zv_mean, zv_var, info, nsamples) of lzv (order 1) / qzv (order 2) for every chain, from the on-device value and gradient
+        histories (klara_get_chain_zv, zv.jl): coef (nchains, K, ndims) — or (K, ndims) when pooled —, zv_mean and zv_var (nchains, ndims),
+        each None when not in `want`; info (nchains,) int32: 0, 1 (singular), 2 (too few samples) — such a chain's outputs are NaN."""
+        k = self.zv_nterms(order)
+        coef = np.empty((k, self.ndims) if pooled else (self.nchains, k, self.ndims)) if "coef" in want else None
+        zm = np.empty((self.nchains, self.ndims)) if "mean" in want else None
+        zv = np.empty((self.nchains, self.ndims)) if "var" in want else None
+        info = np.empty(self.nchains, dtype=np.int32); n = C.c_int64(0)
+        L.check(self._lib.klara_get_chain_zv(self._h, int(order), int(bool(pooled)), *[None if a is None else a.ctypes.data for a in (coef, zm, zv)],
+                                             info.ctypes.data, C.byref(n)), "klara_get_chain_zv")
+        return coef, zm, zv, info, int(n.value)
+
+    def chain_zv_series(self, chain: int, order: int, coef=None) -> np.ndarray:
+        """chain + f a of one chain in NState layout (ndims, nsaved), column-major — zv.jl's first return value, transposed; coef None:
+        the chain's own coefficients, else a given (K, ndims) matrix such as the pooled one."""
+        k = self.zv_nterms(order)
+        a = None if coef is None else _f64(coef, (k, self.ndims))
+        n = C.c_int64(0)
+        L.check(self._lib.klara_get_chain_zv_series(self._h, int(chain), int(order), None if a is None else a.ctypes.data, None, 0, C.byref(n)),
+                "klara_get_chain_zv_series")
+        v = np.empty((self.ndims, n.value), order="F")
+        L.check(self._lib.klara_get_chain_zv_series(self._h, int(chain), int(order), None if a is None else a.ctypes.data, v.ctypes.data, n.value,
+                                                    C.byref(n)), "klara_get_chain_zv_series")
+        return v
+
+    def chain_zv_one(self, chain: int, order: int):
+        """(corrected series (ndims, nsaved) column-major, a (K, ndims), info) of ONE chain from one fit on the device (klara_get_chain_zv_one):
+        what zv.jl's lzv(s) / qzv(s) return for that chain's NState, the series transposed."""
+        k = self.zv_nterms(order)
+        n, info = C.c_int64(0), C.c_int32(0)
+        L.check(self._lib.klara_get_chain_zv_one(self._h, int(chain), int(order), None, None, None, 0, C.byref(n)), "klara_get_chain_zv_one")
+        v = np.empty((self.ndims, n.value), order="F"); a = np.empty((k, self.ndims))
+        L.check(self._lib.klara_get_chain_zv_one(self._h, int(chain), int(order), a.ctypes.data, C.byref(info), v.ctypes.data, n.value, C.byref(n)),
+                "klara_get_chain_zv_one")
+        return v, a, int(info.value)
+
     def saved_steps(self) -> int:
         n = C.c_int64(0)
         L.check(self._lib.klara_saved_steps(self._h, C.byref(n)), "klara_saved_steps")

@@ -10,6 +10,8 @@ chain's history: what the device versions are tested against.
   mcvar(v, "bm", batchlen)   batch means, Flegal & Jones 2010                  mcvar.jl:35-41
   mcvar(v, "imse"|"ipse")    Geyer's initial monotone / positive sequence      mcvar.jl:75-105, 137-158
   mcse = sqrt(mcvar);  ess = len*iidvar/mcvar (convergence/ess.jl:3);  iact = mcvar/iidvar (convergence/iact.jl:3)
+  lzv / qzv(chain, grad)     zero-variance control variates, linear / quadratic       stats/variance/zv.jl:9-84
+                             (device: klara_get_chain_zv, which solves by Cholesky instead of inv — DESIGN.md §2)
 `v` is a 1-D series; the `*_chain` helpers apply an estimator to every dimension of a (D x n) NState value matrix.
 """
 from __future__ import annotations
@@ -92,3 +94,79 @@ def ess_chain(value, vtype="imse", *args):
 
 def iact_chain(value, vtype="imse", *args):
     return _per_dim(iact, value, vtype, *args)
+
+
+# ---- zero-variance control variates (stats/variance/zv.jl, Mira, Solgi & Imparato 2013): the literal restatement — cov, inv, multiply
+def zv_nterms(npars: int, order: int) -> int:
+    """Number of control variates: npars (lzv) or npars (npars + 3) / 2 (qzv, zv.jl:52)."""
+    return npars if order == 1 else npars * (npars + 3) // 2
+
+
+def zv_controls(chain: np.ndarray, grad: np.ndarray, order: int) -> np.ndarray:
+    """The control variates of zv.jl for an (n x D) chain and gradient: z = -grad / 2 (order 1, zv.jl:24) or
+    z_i | 2 z_i x_i - 1 | x_i z_j + x_j z_i for i < j, i outer and j inner (order 2, zv.jl:61-70)."""
+    chain = np.asarray(chain, dtype=np.float64)
+    grad = np.asarray(grad, dtype=np.float64)
+    if order == 1:
+        return -0.5 * grad
+    nsamples, npars = chain.shape
+    k = npars * (npars + 3) // 2
+    qz = np.empty((nsamples, k))
+    z = -grad / 2
+    qz[:, :npars] = z
+    qz[:, npars:2 * npars] = 2 * z * chain - 1
+    l = 2 * npars
+    for i in range(npars - 1):
+        for j in range(i + 1, npars):
+            qz[:, l] = chain[:, i] * z[:, j] + chain[:, j] * z[:, i]
+            l += 1
+    return qz
+
+
+def _zv_matrix(chain: np.ndarray, f: np.ndarray):
+    npars, k = chain.shape[1], f.shape[1]
+    a = np.empty((k, npars))
+    for i in range(npars):                                           # zv.jl:26-31, 72-77
+        augmentedcov = np.atleast_2d(np.cov(np.column_stack([f, chain[:, i]]), rowvar=False))
+        precision = np.linalg.inv(augmentedcov[:k, :k])
+        sigma = augmentedcov[:k, k]
+        a[:, i] = -precision @ sigma
+    return chain + f @ a, a
+
+
+def lzv(chain, grad):
+    """lzv(chain, grad) of zv.jl:9-34: (chain + z a, a) with z = -grad / 2 and a[:, i] = -inv(cov(z)) cov(z, chain[:, i]).
+    (n x D) matrices give an (n x D) series and a (D x D); vectors give the univariate method (a series and a scalar)."""
+    chain = np.asarray(chain, dtype=np.float64)
+    grad = np.asarray(grad, dtype=np.float64)
+    if chain.ndim == 1:
+        z = -0.5 * grad
+        augmentedcov = np.cov(np.column_stack([z, chain]), rowvar=False)
+        a = -augmentedcov[0, 1] / augmentedcov[0, 0]
+        return chain + z * a, float(a)
+    return _zv_matrix(chain, zv_controls(chain, grad, 1))
+
+
+def qzv(chain, grad):
+    """qzv(chain, grad) of zv.jl:42-80: the quadratic polynomial, K = D (D + 3) / 2 control variates; vectors give the univariate
+    method (a series and a of length 2)."""
+    chain = np.asarray(chain, dtype=np.float64)
+    grad = np.asarray(grad, dtype=np.float64)
+    if chain.ndim == 1:
+        z = -0.5 * grad
+        qz = np.column_stack([z, 2 * z * chain - 1])
+        augmentedcov = np.cov(np.column_stack([qz, chain]), rowvar=False)
+        a = -np.linalg.inv(augmentedcov[:2, :2]) @ augmentedcov[:2, 2]
+        return chain + qz @ a, a
+    return _zv_matrix(chain, zv_controls(chain, grad, 2))
+
+
+def lzv_chain(value, gradlogtarget):
+    """lzv(s::ParameterNState{Continuous, Multivariate}) (zv.jl:38) for one chain's (D x n) value and gradlogtarget matrices:
+    (corrected series (n x D), a (D x D))."""
+    return lzv(np.asarray(value).T, np.asarray(gradlogtarget).T)
+
+
+def qzv_chain(value, gradlogtarget):
+    """qzv(s::ParameterNState{Continuous, Multivariate}) (zv.jl:84): (corrected series (n x D), a (K x D))."""
+    return qzv(np.asarray(value).T, np.asarray(gradlogtarget).T)
