@@ -31,7 +31,7 @@ module KlaraHIP
 import Klara
 import Klara: output, MCJob, MH, MALA, SMMALA, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
               BasicContMuvParameterState, BasicContMuvParameterNState, erf_rate_score, logistic_rate_score,
-              Parameter, GenericModel, VariableState, VariableStateVector
+              Parameter, GenericModel, VariableState, VariableStateVector, DiffOptions
 import Distributions
 import Distributions: Continuous, Multivariate
 import Base: run, reset, show
@@ -132,8 +132,21 @@ end
 struct HierNormalTarget <: HIPTarget         # BUGS "Rats" model on data/rats/*.csv (include/klara_hip.h KLARA_TARGET_HIER_NORMAL)
     Y::Matrix{Float64}; xc::Vector{Float64}; prior_prec::Float64; gamma_a::Float64; gamma_b::Float64
 end
+# diffopts=DiffOptions(mode=:forward[, order=2][, chunksize=n]) (Klara's own, autodiff/autodiff.jl:55-76): the source defines no gradient, only the generic
+# klara_user_logtarget_ad (klara.jl_amd/csrc/klara_autodiff.h), and is differentiated on the device by forward-mode dual numbers; order = 2 also gives SMMALA
+# its metric, minus the Hessian (autodiff/forward.jl:11-16).  Reverse mode needs tapes, which do not exist on the device.
+function autodiff_source(src::AbstractString, diffopts::DiffOptions)
+    diffopts.mode == :forward || error("DiffOptions(mode=:reverse): reverse-mode tapes do not exist on the device; use mode=:forward")
+    head = string("#define KLARA_USER_AUTODIFF ", Int(diffopts.order), "\n")
+    if diffopts.chunksize > 0
+        head = string(head, "#define KLARA_USER_AUTODIFF_CHUNK ", Int(diffopts.chunksize), "\n")
+    end
+    string(head, src)
+end
 struct CustomTarget <: HIPTarget             # C text of klara_user_logtarget / klara_user_gradlogtarget (or the likelihood + prior form)
     ndims::Int; src::String; data::Vector{Float64}
+    CustomTarget(ndims::Integer, src::AbstractString, data::Vector{Float64}=Float64[]; diffopts=nothing) =
+        new(ndims, diffopts === nothing ? src : autodiff_source(src, diffopts), data)
 end
 ndims_of(t::GaussDiagTarget) = t.ndims
 ndims_of(t::GaussDenseTarget) = size(t.P, 1)
@@ -153,8 +166,11 @@ mutable struct HIPParameter <: Parameter{Continuous, Multivariate}
 end
 HIPParameter(key::Symbol, target::HIPTarget; index::Integer=0, states::VariableStateVector=VariableState[]) = HIPParameter(key, index, target, states)
 # keyword form, mirroring BasicContMuvParameter(key; logtarget=...) (BasicContMuvParameter.jl:383-411): the "closure" is a device target
+# (diffopts=DiffOptions(mode=:forward), as in doc/examples/swiss/MALA/forwarddiff.jl: the CustomTarget's text is the generic log-target alone)
+with_diffopts(t::HIPTarget, diffopts) = diffopts === nothing ? t :
+    isa(t, CustomTarget) ? CustomTarget(t.ndims, t.src, t.data, diffopts=diffopts) : error("HIPParameter: diffopts goes with a CustomTarget")
 HIPParameter(key::Symbol; logtarget::HIPTarget=error("HIPParameter: logtarget=<a device target family, e.g. GaussDiagTarget(D)> is required"),
-             index::Integer=0, states::VariableStateVector=VariableState[]) = HIPParameter(key, index, logtarget, states)
+             diffopts=nothing, index::Integer=0, states::VariableStateVector=VariableState[]) = HIPParameter(key, index, with_diffopts(logtarget, diffopts), states)
 
 # ---------------------------------------------------------------- the job
 mutable struct HIPMCJob <: MCJob   # stands for N BasicMCJobs of one model (run(jobs::Vector) = map(run, jobs), jobs.jl:212)

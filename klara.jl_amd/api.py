@@ -175,6 +175,31 @@ class DualAveragingMCTuner(MCTuner):
 
 
 # ------------------------------------------------------------------ parameter / model
+class DiffOptions:
+    """DiffOptions(mode=:reverse, order=1, targets=fill(false, 3), chunksize=0, compiled=true) — src/autodiff/autodiff.jl:55-76, with
+    its four assertions.  On the device only forward mode exists (klara_autodiff.h: dual numbers swept through the user's generic
+    log-target; there are no tapes): `mode="reverse"` is accepted here as in the reference, and refused where a parameter is built
+    with it.  `order=2` also gives the SMMALA sampler its metric, minus the Hessian (forward.jl:11-16); `chunksize` is the number of
+    directions per sweep (0: the library's choice); `targets` and `compiled` are kept and have no meaning on the device."""
+
+    def __init__(self, mode="reverse", order: int = 1, targets=None, chunksize: int = 0, compiled: bool = True):
+        mode = str(mode).lstrip(":")
+        targets = [False, False, False] if targets is None else [bool(t) for t in targets]
+        assert mode in ("reverse", "forward"), f"Mode of automatic differentation must be :reverse or :forward, got {mode}"
+        assert order in (1, 2), f"Order of differentiation must be 1 or 2, got order={order}"
+        assert len(targets) == 3, f"Length of targets must be 3, got {len(targets)}-length vector"
+        assert chunksize >= 0, f"chunksize can not be negative, got chunksize={chunksize}"
+        self.mode, self.order, self.targets, self.chunksize, self.compiled = mode, int(order), targets, int(chunksize), bool(compiled)
+
+    def __repr__(self):
+        return f"DiffOptions(mode=:{self.mode}, order={self.order}, targets={self.targets}, chunksize={self.chunksize}, compiled={self.compiled})"
+
+    def require_forward(self) -> None:
+        if self.mode != "forward":
+            raise NotImplementedError("DiffOptions(mode=:reverse): reverse-mode tapes do not exist on the device; use mode=:forward "
+                                      "(forward-mode dual numbers, klara_autodiff.h)")
+
+
 class BasicContMuvParameter:
     """BasicContMuvParameter(key; logtarget=...) — BasicContMuvParameter.jl:383-411.
 
@@ -184,9 +209,26 @@ class BasicContMuvParameter:
 
     def __init__(self, key: str, logtarget=None, loglikelihood: Optional[str] = None, logprior: Optional[str] = None,
                  gradloglikelihood: Optional[str] = None, gradlogprior: Optional[str] = None, ndims: Optional[int] = None, data=None,
-                 **unsupported):
+                 diffopts: Optional[DiffOptions] = None, **unsupported):
         if unsupported:
             raise NotImplementedError(f"closure fields not available on device: {sorted(unsupported)}")
+        if diffopts is not None:
+            # diffopts=DiffOptions(mode=:forward) (doc/examples/swiss/MALA/forwarddiff.jl): the closures are generic C++ text without gradients
+            # (klara_user_logtarget_ad, or klara_user_loglikelihood_ad + klara_user_logprior_ad), differentiated on the device
+            diffopts.require_forward()
+            if gradloglikelihood is not None or gradlogprior is not None:
+                raise ValueError("diffopts and gradient closures are alternatives")
+            if ndims is None:
+                raise ValueError("ndims is required with diffopts")
+            if isinstance(logtarget, str):
+                if loglikelihood is not None or logprior is not None:
+                    raise ValueError("logtarget and loglikelihood / logprior are alternatives")
+                src = logtarget
+            elif logtarget is None and loglikelihood is not None and logprior is not None:
+                src = "#define KLARA_USER_LIKELIHOOD_PRIOR 1\n" + loglikelihood + "\n" + logprior
+            else:
+                raise ValueError("diffopts goes with logtarget (C++ source text) or with both loglikelihood and logprior")
+            logtarget, loglikelihood, logprior = CustomTarget.autodiff(ndims, src, data, order=diffopts.order, chunksize=diffopts.chunksize), None, None
         if logtarget is None:
             # likelihood + prior closures (BasicContMuvParameter.jl:174-201): C text for each, composed on device as
             # logtarget = loglikelihood + logprior, gradlogtarget = gradloglikelihood + gradlogprior

@@ -20,6 +20,9 @@
 //    gradient is written to a second row and each lane picks up its own elements.  The sums of the samplers run in the group layout's
 //    order (klara_get_layout: kind 0, G, E), the target's value is the user's own.
 //
+// A source that starts with `#define KLARA_USER_AUTODIFF 1` defines klara_user_logtarget_ad, generic in its scalar type, instead, and no gradient
+// (klara_autodiff.h, whose glue is compiled between the user's text and this file and supplies the closures above by forward-mode sweeps).
+//
 // This file is only ever compiled by the run-time compiler, after klara_kernels.h and the user's source.
 #pragma once
 #include "klara_custom_compose.h"       // likelihood + prior form (KLARA_USER_LIKELIHOOD_PRIOR): lt = ll + lp, grad = gll + glp
@@ -84,6 +87,35 @@ KLARA_PRAGMA_UNROLL_E
         ll = 0.0; lp = 0.0;
 #endif
     }
+#if defined(KLARA_USER_AUTODIFF) && !defined(KLARA_CUSTOM_NOGRAD)
+    // Forward-mode autodiff (klara_autodiff.h), STAGED: the G lanes of a chain evaluate the user's generic function on the chain's row as they do its
+    // double form, but each lane seeds the directions i0 .. i0 + E - 1 of its own elements: the G evaluations are the direction sweep, and the gradient
+    // arrives in the lane layout (no gradient row is written or read).  ADC directions per evaluation: the source's KLARA_USER_AUTODIFF_CHUNK, else 4 —
+    // HMC on the quartic chain at D = 100 (E = 14), 65,536 chains: 908 ms per 320 transitions at 4, 925 at 8, 1059 at 14 (one evaluation), 1192 at 2, 1378 at 1
+    // (profiles/autodiff.txt).  The value is the one the duals carry (A1: the bits of the double instantiation).
+    static constexpr int ADC = (KLARA_AD_USER_CHUNK) > 0 ? ((KLARA_AD_USER_CHUNK) < E ? (KLARA_AD_USER_CHUNK) : E) : (E < 4 ? E : 4);
+    template <bool WANT_LT>
+    __device__ __forceinline__ void ad_staged(const LaneCtx<E>& cx, double (&g)[E]) const
+    {
+        typedef klara_dual<double, ADC> dual;
+#pragma unroll
+        for (int c0 = 0; c0 < E; c0 += ADC) {
+            const klara_ad_view<ADC> view = { xs, cx.i0 + c0 };
+#ifdef KLARA_USER_LIKELIHOOD_PRIOR
+            const dual rl = klara_user_loglikelihood_ad<dual>(view, D, data, ndata);
+            const dual rp = klara_user_logprior_ad<dual>(view, D, data, ndata);
+            if (WANT_LT && c0 == 0) lt_full = rl.v + rp.v;
+#pragma unroll
+            for (int k = 0; k < ADC; ++k) if (c0 + k < E) g[c0 + k] = cx.i0 + c0 + k < D ? rl.d[k] + rp.d[k] : 0.0;     // (klara_custom_compose.h: one addition per element)
+#else
+            const dual r = klara_user_logtarget_ad<dual>(view, D, data, ndata);
+            if (WANT_LT && c0 == 0) lt_full = r.v;
+#pragma unroll
+            for (int k = 0; k < ADC; ++k) if (c0 + k < E) g[c0 + k] = cx.i0 + c0 + k < D ? r.d[k] : 0.0;
+#endif
+        }
+    }
+#endif
     // NTRI > 0 (the SMMALA sampler, one chain per lane, D <= 8): gm[] receives the upper triangle of the user's tensor (a row-major D x D
     // matrix filled by klara_user_tensorlogtarget, the tensorlogtarget closure of BasicContMuvParameter), packed as in klara_kernels.h ktri
     template <bool WANT_LT, bool WANT_GRAD, int NTRI = 0>
@@ -102,6 +134,14 @@ KLARA_PRAGMA_UNROLL_E
 #endif
         if (staged) {
             stage(cx, x);
+#if defined(KLARA_USER_AUTODIFF) && !defined(KLARA_CUSTOM_NOGRAD)
+            if (WANT_GRAD) {                 // (klara_autodiff.h; a value alone is the double instantiation below)
+                ad_staged<WANT_LT>(cx, g);
+                if (WANT_LT) ltpart = 0.0;
+                stage_fence();
+                return;
+            }
+#endif
             if (WANT_LT) { lt_full = klara_user_logtarget(xs, D, data, ndata); ltpart = 0.0; }
             if (WANT_GRAD) {
 #ifdef KLARA_CUSTOM_NOGRAD

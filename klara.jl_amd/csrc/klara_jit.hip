@@ -235,7 +235,20 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
     }
     const bool needgrad = sampler == KLARA_SAMPLER_MALA || sampler == KLARA_SAMPLER_HMC || sampler == KLARA_SAMPLER_SMMALA;
     // SMMALA: the metric is the user's klara_user_tensorlogtarget (klara_custom.h); a source without it cannot run the sampler
-    if (sampler == KLARA_SAMPLER_SMMALA && !pf && strstr(src, "klara_user_tensorlogtarget") == nullptr) {
+    // forward-mode autodiff (klara_autodiff.h): the marker's value; the generic function it promises has to be there
+    const int ad = pf ? 0 : klara_autodiff_order(src);
+    if (ad > 0) {
+        const bool parts = strstr(src, "KLARA_USER_LIKELIHOOD_PRIOR") != nullptr;
+        const char* need[2] = { parts ? "klara_user_loglikelihood_ad" : "klara_user_logtarget_ad", parts ? "klara_user_logprior_ad" : nullptr };
+        for (const char* fn : need) {
+            if (fn && strstr(src, fn) == nullptr) {
+                g_log = std::string("a source with KLARA_USER_AUTODIFF needs template <class T, class V> KLARA_USER_FN T ") + fn +
+                        "(const V& x, int D, const double* data, long long ndata)";
+                return KLARA_ERR_COMPILE;
+            }
+        }
+    }
+    if (sampler == KLARA_SAMPLER_SMMALA && !pf && ad < 2 && strstr(src, "klara_user_tensorlogtarget") == nullptr) {
         g_log = "the SMMALA sampler needs klara_user_tensorlogtarget(const double* x, int D, const double* data, long long ndata, double* G)";
         return KLARA_ERR_COMPILE;
     }
@@ -252,9 +265,11 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
           "typedef int int32_t; typedef unsigned int uint32_t; typedef long long int64_t; typedef unsigned long long uint64_t;\n";
     if (pf) tu += "#ifndef KLARA_USER_PAIR_TARGET\n#define KLARA_USER_PAIR_TARGET 1\n#endif\n";
     tu += "#include \"klara_kernels.h\"\n"
-          "#define KLARA_USER_FN static __device__ __forceinline__\n"
-          "#line 1 \"klara_user_target\"\n";
+          "#define KLARA_USER_FN static __device__ __forceinline__\n";
+    if (ad > 0) tu += "#include \"klara_autodiff.h\"\n";                  // the dual arithmetic, before the user's text
+    tu += "#line 1 \"klara_user_target\"\n";
     tu += src;
+    if (ad > 0) tu += "\n#line 1 \"klara_autodiff_glue\"\n#define KLARA_AUTODIFF_GLUE 1\n#include \"klara_autodiff.h\"\n";     // ... and its glue, after it
     // the glue: whole-vector closures instantiate the group-layout kernels on CustomTarget (klara_custom.h); a pair closure is
     // declared by now, so klara_diagt.h's USERPAIR branches can call it
     tu += pf ? "\n#line 1 \"klara_custom_pair_glue\"\n#include \"klara_diagt.h\"\n" : "\n#line 1 \"klara_custom_glue\"\n#include \"klara_custom.h\"\n";

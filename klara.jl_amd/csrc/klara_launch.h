@@ -1,6 +1,7 @@
 // klara_launch.h — launcher prototypes implemented by the per-sampler translation units
 #pragma once
 #include <stdlib.h>
+#include <string.h>
 #include "klara_kernels.h"
 #include "klara_diagt.h"
 
@@ -14,6 +15,20 @@ static inline hipError_t klara_go(void (*kern)(KArgs...), dim3 grid, dim3 blk, s
     if (klara_attr_query != nullptr) return hipFuncGetAttributes(klara_attr_query, (const void*)kern);
     hipLaunchKernelGGL(kern, grid, blk, lds, st, args...);
     return hipGetLastError();
+}
+
+// Forward-mode autodiff of a user-defined target (klara_autodiff.h): the value of the source's `#define KLARA_USER_AUTODIFF n` marker — 1: the gradient,
+// 2: also the SMMALA metric (minus the Hessian) — or 0 for a source without it.  (KLARA_USER_AUTODIFF_CHUNK is another name.)
+static inline int klara_autodiff_order(const char* src)
+{
+    static const char name[] = "KLARA_USER_AUTODIFF";
+    for (const char* s = src ? strstr(src, name) : nullptr; s != nullptr; s = strstr(s + 1, name)) {
+        const char* t = s + sizeof(name) - 1;
+        if (*t != ' ' && *t != '\t') continue;
+        while (*t == ' ' || *t == '\t') ++t;
+        return *t == '2' ? 2 : 1;
+    }
+    return 0;
 }
 
 // group-layout transition kernels; target in {GAUSS_DIAG, LOGISTIC}; E in {2,4,8}; G = lanes per chain

@@ -125,6 +125,9 @@ static bool pair_as_whole(const klara_desc& d, const KlaraOverrides& o)
     return pair_form(d) && (d.ndims < 17 || (d.sampler == KLARA_SAMPLER_SLICE && o.pair_slice_as_whole));
 }
 static bool custom_lik_prior(const char* src) { return src != nullptr && strstr(src, "KLARA_USER_LIKELIHOOD_PRIOR") != nullptr; }
+// forward-mode autodiff (klara_autodiff.h): the source's marker.  Pair closures are not differentiated; second order (the SMMALA metric as minus the
+// Hessian) is the plain whole-vector form's within smmala_eligible's limits, and with any other sampler the marker's 2 means 1.
+static int custom_autodiff(const klara_desc& d) { return d.target == KLARA_TARGET_CUSTOM ? klara_autodiff_order(d.custom_src) : 0; }
 
 // Whole-vector closures (klara_custom.h).  Up to 32 dimensions a lane keeps the whole vector in registers (one chain per lane); beyond,
 // the chain is spread over G lanes with E = 2 ceil(D / 2G) <= 16 elements each and evaluations read the vector from the chain's row of
@@ -280,6 +283,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     p.steps_per_launch = d.steps_per_launch > 0 ? d.steps_per_launch : p.slice_free ? KLARA_DEFAULT_STEPS_PER_LAUNCH_SLICE : KLARA_DEFAULT_STEPS_PER_LAUNCH;
 
     if (d.sampler == KLARA_SAMPLER_SMMALA && !smmala_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
+    if (custom_autodiff(d) > 0 && d.custom_src != nullptr && strstr(d.custom_src, "KLARA_USER_PAIR_TARGET") != nullptr) return KLARA_ERR_UNSUPPORTED;
     if (d.target == KLARA_TARGET_LOGISTIC && !logit_mfma_eligible(d, o) && logit_beyond_rowsplit(d)) p.rewrite = KLARA_REWRITE_LOGIT_WIDE;
     else if (pair_as_whole(d, o)) p.rewrite = KLARA_REWRITE_PAIR_AS_WHOLE;
     else if (d.target == KLARA_TARGET_GAUSS_DENSE && D > 128 && !dense_streamed(d, o) && !dense_split(d, o)) p.rewrite = KLARA_REWRITE_DENSE_WIDE;

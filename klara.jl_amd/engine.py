@@ -6,6 +6,7 @@ libklara_hip.so (see include/klara_hip.h for the reference lines each entry poin
 from __future__ import annotations
 
 import ctypes as C
+import re
 from dataclasses import dataclass
 from typing import Optional
 
@@ -148,6 +149,34 @@ class CustomTarget:
         the library sums the pairs' terms itself and runs the whole-vector form (D <= 1024); the slice sampler runs on them too (round 6: a probe compares the pair's own term)."""
         return cls(ndims, "#define KLARA_USER_PAIR_TARGET 1\n" + pair_source, data)
 
+    @classmethod
+    def autodiff(cls, ndims: int, source: str, data=None, order: int = 1, chunksize: int = 0) -> "CustomTarget":
+        """Forward-mode automatic differentiation, the device form of `diffopts=DiffOptions(mode=:forward)` (src/autodiff/forward.jl,
+        BasicContMuvParameter.jl:627-694): `source` defines no gradient, only the log-target, generic in its scalar type,
+
+            template <class T, class V>
+            KLARA_USER_FN T klara_user_logtarget_ad(const V& x, int D, const double* data, long long ndata);
+
+        where x[i] yields a T (a source in the likelihood + prior form — `#define KLARA_USER_LIKELIHOOD_PRIOR 1` — defines klara_user_loglikelihood_ad and
+        klara_user_logprior_ad of the same shape instead).  The functions may use + - * / and comparisons between T and double, sqrt, fabs, kd_fma,
+        kd_exp, kd_log, kd_erf and kd_softplus_logistic_rows.  `order=2` also forms the metric of the SMMALA sampler as minus the Hessian (D <= 8, not
+        the likelihood + prior form); `chunksize` is DiffOptions.chunksize: the directions per sweep, 0 for the library's choice.  This prepends
+        `#define KLARA_USER_AUTODIFF order` (and KLARA_USER_AUTODIFF_CHUNK) to the source (include/klara_hip.h)."""
+        if int(order) not in (1, 2):
+            raise ValueError("order must be 1 or 2")
+        if int(chunksize) < 0:
+            raise ValueError("chunksize can not be negative")
+        head = f"#define KLARA_USER_AUTODIFF {int(order)}\n"
+        if int(chunksize) > 0:
+            head += f"#define KLARA_USER_AUTODIFF_CHUNK {int(chunksize)}\n"
+        return cls(ndims, head + source, data)
+
+    @property
+    def autodiff_order(self) -> int:
+        """value of the source's KLARA_USER_AUTODIFF marker (0: a source with hand-written gradients)"""
+        m = re.search(r"KLARA_USER_AUTODIFF[ \t]+(\d)", self.source)
+        return 0 if m is None else (2 if m.group(1) == "2" else 1)
+
     @property
     def has_parts(self) -> bool:
         return "KLARA_USER_LIKELIHOOD_PRIOR" in self.source
@@ -158,8 +187,8 @@ class CustomTarget:
 
     @property
     def has_tensor(self) -> bool:
-        """the source defines klara_user_tensorlogtarget (what the SMMALA sampler needs)"""
-        return "klara_user_tensorlogtarget" in self.source
+        """the source defines klara_user_tensorlogtarget, or asks for second-order autodiff (what the SMMALA sampler needs)"""
+        return "klara_user_tensorlogtarget" in self.source or self.autodiff_order == 2
 
     def check(self, sampler: int) -> None:
         """Compile only (no GPU needed); raises KlaraError with the compiler's log on failure (for SMMALA also when the source has no
