@@ -73,7 +73,7 @@ typedef enum klara_sampler {
     KLARA_SAMPLER_MALA = 1,    /* MALA(driftstep), MALA.jl:61-70                                   */
     KLARA_SAMPLER_HMC = 2,     /* HMC(leapstep, nleaps), HMC.jl:89-100                             */
     KLARA_SAMPLER_SLICE = 3,   /* SliceSampler(widths, stepout), SliceSampler.jl:22-34             */
-    /* SMMALA(driftstep) (transform = nothing), SMMALA.jl:127-137: MALA with the position-dependent metric G(x) of the target —
+    /* SMMALA(driftstep) (transform = nothing; klara_desc.smmala_softabs for SMMALA(driftstep, H -> softabs(H, a))), SMMALA.jl:127-137: MALA with the position-dependent metric G(x) of the target —
      * for KLARA_TARGET_LOGISTIC with D <= 8 on the row-split kernels, G = X' diag(r (1 - r)) X + I / lambda
      * (doc/examples/swiss/SMMALA/analytical.jl:20-23).  Draws exactly what MALA draws (D normals and one accept uniform per
      * transition); C = L^-T with G = L L' in place of chol(inv(G))', and a proposal whose metric is not positive definite is
@@ -262,6 +262,14 @@ typedef struct klara_desc {
                                     registers (flat cost at any acceptance).  0 (default): the library decides launch by launch, on the device,
                                     from the accepted proposals of the previous launch (klara_get_launch_modes reports what ran); 1: always the
                                     4-lane kernels; 2: always the 8-lane kernels.  Results never depend on this field. */
+    double   smmala_softabs;     /* SMMALA: 0 = no transform of the metric (SMMALA(driftstep), transform = nothing); a > 0: the metric of every chain, at the
+                                    start state and at every proposal, is softabs(G, a) = Q diag(lambda ./ tanh(a lambda)) Q' (stats/metrics.jl:1-4), i.e.
+                                    SMMALA(driftstep, H -> softabs(H, a)), formed on the device in the lane's registers (klara_softabs.h, DESIGN.md section 2
+                                    T1-T5).  KLARA_TARGET_CUSTOM only (the plain whole-vector form, D <= 8: a klara_user_tensorlogtarget or
+                                    KLARA_USER_AUTODIFF 2, whose minus-Hessian is indefinite wherever the target is not log-concave).
+                                    KLARA_TARGET_LOGISTIC with a > 0 is KLARA_ERR_UNSUPPORTED: its metric X' diag(r (1 - r)) X + I / lambda is positive
+                                    definite by construction and has no use for the transform.  Negative or non-finite, or a > 0 with another sampler:
+                                    KLARA_ERR_INVALID_ARG. */
 
     uint64_t seed;               /* Philox key                                                       */
     uint32_t monitor;            /* KLARA_MON_* bits                                                 */
@@ -514,6 +522,10 @@ klara_status klara_selftest_plan(const klara_desc* desc, int32_t nruns, const in
 /* CUSTOM target: compile `src` for gfx950 exactly as klara_create would for this sampler and dimension, without creating
  * a handle and without needing a GPU (a user checks a closure before submitting a job).  KLARA_OK or KLARA_ERR_COMPILE. */
 klara_status klara_check_custom_target(const char* src, int32_t sampler, int32_t ndims);
+/* The same for the SMMALA kernels with the softabs transform of the metric (klara_desc.smmala_softabs > 0): the variant klara_create compiles
+ * for such a job.  ndims >= 9 is KLARA_ERR_UNSUPPORTED; a source without a metric (klara_user_tensorlogtarget or KLARA_USER_AUTODIFF 2)
+ * KLARA_ERR_COMPILE. */
+klara_status klara_check_custom_target_softabs(const char* src, int32_t ndims);
 /* Compiler output of the calling thread's last klara_create / klara_check_custom_target that compiled a CUSTOM target
  * ("" if none); valid until the thread's next such call. */
 const char* klara_compile_log(void);

@@ -37,6 +37,7 @@ import Distributions: Continuous, Multivariate
 import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
+       check_custom_target_softabs, SoftAbs,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
@@ -53,7 +54,7 @@ end
 # ---------------------------------------------------------------- constants of include/klara_hip.h
 const KLARA_ABI_VERSION = UInt32(6)
 const SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE = Int32(0), Int32(1), Int32(2), Int32(3)
-const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothing; the logistic target with D <= 8
+const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothing or SoftAbs(a); the logistic target or a CustomTarget's tensor, D <= 8
 const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
@@ -76,6 +77,7 @@ struct KlaraDesc
     hier_prior_prec::Float64; hier_gamma_a::Float64; hier_gamma_b::Float64
     custom_src::Cstring; custom_data::Ptr{Float64}; custom_ndata::Int64; bm_batchlen::Int64
     hist_ring_cols::Int64; acov_maxlag::Int32; sparse_moves::Int32
+    smmala_softabs::Float64
     seed::UInt64; monitor::UInt32; steps_per_launch::Int32; stream::Ptr{Cvoid}
 end
 
@@ -92,7 +94,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
                     hier_Y=Ptr{Float64}(C_NULL), hier_xc=Ptr{Float64}(C_NULL), hier_nunits=0, hier_ntimes=0,
                     hier_prior_prec=1e-4, hier_gamma_a=1e-3, hier_gamma_b=1e-3,
                     custom_src=Cstring(C_NULL), custom_data=Ptr{Float64}(C_NULL), custom_ndata=0, bm_batchlen=0,
-                    hist_ring_cols=0, acov_maxlag=0, sparse_moves=0,
+                    hist_ring_cols=0, acov_maxlag=0, sparse_moves=0, smmala_softabs=0.0,
                     seed=UInt64(0), monitor=UInt32(0), steps_per_launch=0, stream=C_NULL)
     KlaraDesc(UInt32(sizeof(KlaraDesc)), KLARA_ABI_VERSION,
               sampler, target, tuner, tuner_mode,
@@ -108,9 +110,15 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               hier_Y, hier_xc, hier_nunits, hier_ntimes,
               hier_prior_prec, hier_gamma_a, hier_gamma_b,
               custom_src, custom_data, custom_ndata, bm_batchlen,
-              hist_ring_cols, acov_maxlag, sparse_moves,
+              hist_ring_cols, acov_maxlag, sparse_moves, smmala_softabs,
               seed, monitor, steps_per_launch, stream)
 end
+
+# H -> softabs(H, a) (stats/metrics.jl:1-4) as a callable the device path can recognise: SMMALA(1.25, SoftAbs(1000.)) is Klara's own sampler — it
+# runs on the CPU through Klara unchanged — and HIPMCJob maps it to klara_desc.smmala_softabs = a (an anonymous closure H -> softabs(H, a) cannot be
+# recognised and stays refused)
+struct SoftAbs <: Function; a::Float64; end
+(s::SoftAbs)(H) = Klara.softabs(H, s.a)
 
 check(st::Cint, what) = st == 0 || error(what, ": ", unsafe_string(ccall((:klara_strerror, lib), Cstring, (Cint,), st)))
 
@@ -184,7 +192,7 @@ rowmajor(A::Matrix{Float64}) = collect(transpose(A))       # Julia is column-maj
 
 # Klara's structs -> klara_desc.  Field names read from Klara (file:line in /root/reference/src):
 #   MALA.driftstep                         samplers/MALA.jl:61-70
-#   SMMALA.driftstep (transform = nothing) samplers/SMMALA.jl:127-137
+#   SMMALA.driftstep, .transform (nothing or SoftAbs(a)) samplers/SMMALA.jl:127-137
 #   HMC.leapstep, HMC.nleaps               samplers/HMC.jl:89-100
 #   SliceSampler.widths, .stepout          samplers/SliceSampler.jl:22-34
 #   MH.setproposal (sigma is inside the closure: MH(sigma) = MH(x -> MvNormal(x, sigma)))   samplers/MH.jl:46-66
@@ -232,9 +240,11 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
                            :steps_per_launch => steps_per_launch, :bm_batchlen => bm_batchlen,
                            :nsteps => mcrange.nsteps, :burnin => mcrange.burnin, :thinning => mcrange.thinning)
     # --- sampler
-    if isa(sampler, SMMALA)                                 # samplers/SMMALA.jl:127-137; the metric is the target's (LogisticTarget)
-        sampler.transform === nothing || error("SMMALA: a transform of the metric (e.g. softabs) is not run on the device")
+    if isa(sampler, SMMALA)                                 # samplers/SMMALA.jl:127-137; the metric is the target's (LogisticTarget, or a CustomTarget's tensor)
+        tr = sampler.transform                              # nothing, or SoftAbs(a): softabs(G, a) of every metric on the device (CustomTarget only)
+        (tr === nothing || isa(tr, SoftAbs)) || error("SMMALA: the only transform of the metric that runs on the device is SoftAbs(a), as in SMMALA(1.25, SoftAbs(1000.)); a closure cannot be recognised")
         kw[:sampler] = SAMPLER_SMMALA; kw[:driftstep] = Float64(sampler.driftstep)
+        kw[:smmala_softabs] = tr === nothing ? 0.0 : tr.a
     elseif isa(sampler, MALA)
         kw[:sampler] = SAMPLER_MALA; kw[:driftstep] = Float64(sampler.driftstep)
     elseif isa(sampler, HMC)
@@ -463,6 +473,13 @@ end
 # user-defined target: compile the closures' C text without a GPU; the compiler's message on failure
 function check_custom_target(src::String, sampler::Integer, ndims::Integer)
     st = ccall((:klara_check_custom_target, lib), Cint, (Cstring, Cint, Cint), src, sampler, ndims)
+    st == 0 || error(unsafe_string(ccall((:klara_compile_log, lib), Cstring, ())))
+    true
+end
+
+# ... and for the SMMALA kernels with the softabs transform of the metric (SMMALA(h, SoftAbs(a)))
+function check_custom_target_softabs(src::String, ndims::Integer)
+    st = ccall((:klara_check_custom_target_softabs, lib), Cint, (Cstring, Cint), src, ndims)
     st == 0 || error(unsafe_string(ccall((:klara_compile_log, lib), Cstring, ())))
     true
 end

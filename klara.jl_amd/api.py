@@ -70,17 +70,38 @@ class MALA(MCSampler):
         self.driftstep = float(driftstep)
 
 
+class SoftAbs:
+    """H -> softabs(H, a) (stats/metrics.jl:1-4) as an object the device path can recognise: SMMALA(1.25, SoftAbs(1000.)) is the
+    reference's SMMALA(1.25, H -> softabs(H, 1000.)) (doc/examples/BivariateNormal/SMMALA/analytical.jl:16).  Calling it gives
+    klara_jl_amd.stats.softabs(H, a), the NumPy restatement; the job applies the transform on the device (klara_desc.smmala_softabs)."""
+
+    def __init__(self, a: float = 1000.0):
+        a = float(a)
+        if not (a > 0.0 and np.isfinite(a)):
+            raise ValueError("SoftAbs: a must be a positive finite number")
+        self.a = a
+
+    def __call__(self, H):
+        from .stats import softabs
+        return softabs(H, self.a)
+
+    def __repr__(self):
+        return f"SoftAbs({self.a!r})"
+
+
 class SMMALA(MCSampler):
     """SMMALA(driftstep=1., transform=nothing) — SMMALA.jl:127-137.  The metric is the target's tensorlogtarget: on the device the
-    logistic regression with D <= 8 (X' diag(r (1 - r)) X + I / lambda, doc/examples/swiss/SMMALA/analytical.jl:20-23).  A
-    `transform` of the metric (e.g. softabs) is not run on the device and is refused."""
+    logistic regression with D <= 8 (X' diag(r (1 - r)) X + I / lambda, doc/examples/swiss/SMMALA/analytical.jl:20-23) or a user-defined
+    target's tensor / minus-Hessian.  `transform` is None or a SoftAbs (user-defined targets only: the transform runs on the device);
+    any other callable is a closure the device cannot run and is refused."""
     kind = L.SAMPLER_SMMALA
 
     def __init__(self, driftstep: float = 1.0, transform=None):
         assert driftstep > 0, "Drift step is not positive"
-        if transform is not None:
-            raise NotImplementedError("SMMALA: a transform of the metric (e.g. softabs) is not supported on the device")
-        self.driftstep, self.transform = float(driftstep), None
+        if transform is not None and not isinstance(transform, SoftAbs):
+            raise NotImplementedError("SMMALA: the only transform of the metric that runs on the device is SoftAbs(a) "
+                                      "(H -> softabs(H, a)); an arbitrary closure is not supported")
+        self.driftstep, self.transform = float(driftstep), transform
 
 
 class HMC(MCSampler):
@@ -526,6 +547,10 @@ class BasicMCJob:
             kw["mh_sigma"] = sampler.sigma
         elif isinstance(sampler, (MALA, SMMALA)):
             kw["driftstep"] = sampler.driftstep
+            if isinstance(sampler, SMMALA) and sampler.transform is not None:          # SMMALA.jl:167-168, iterate/SMMALA.jl:117-118
+                if isinstance(self.parameter.target, LogisticTarget):
+                    raise ValueError("SMMALA: SoftAbs is not applied to LogisticTarget, whose metric is positive definite by construction")
+                kw["smmala_softabs"] = sampler.transform.a
         elif isinstance(sampler, HMC):
             kw["leapstep"], kw["nleaps"] = sampler.leapstep, sampler.nleaps
         elif isinstance(sampler, SliceSampler):

@@ -135,6 +135,11 @@ static klara_status validate(const klara_desc* d)
         return KLARA_ERR_INVALID_ARG;
     if (d->hist_ring_cols < 0 || d->acov_maxlag < 0 || d->acov_maxlag > 127 || d->sparse_moves < 0 || d->sparse_moves > 2) return KLARA_ERR_INVALID_ARG;
     if (d->bm_batchlen < 0 || (d->bm_batchlen > 0 && !(d->monitor & KLARA_MON_SUMMARIES))) return KLARA_ERR_INVALID_ARG;
+    // softabs(G, a) of the SMMALA metric (samplers/SMMALA.jl:129 transform): a finite a >= 0, 0 = none; the logistic target's metric is positive
+    // definite by construction (X' diag(r (1 - r)) X + I / lambda) and is not transformed
+    if (!(d->smmala_softabs >= 0.0) || !std::isfinite(d->smmala_softabs)) return KLARA_ERR_INVALID_ARG;
+    if (d->smmala_softabs > 0.0 && d->sampler != KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
+    if (d->smmala_softabs > 0.0 && d->target != KLARA_TARGET_CUSTOM) return KLARA_ERR_UNSUPPORTED;
     if (d->steps_per_launch < 0 || d->tuner_score < 0 || d->tuner_score > 1) return KLARA_ERR_INVALID_ARG;   // (int32: a launch length always fits KLaunch::nsteps)
     return KLARA_OK;
 }
@@ -417,7 +422,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
             const int modes[2] = { 0, 1 };
             CK(klara_jit_create_pair(desc->custom_src, desc->sampler, desc->ndims, E / 2, G, mon_, tune_, da_, modes, (!mon_ && !tune_ && desc->sampler != KLARA_SAMPLER_SLICE) ? 2 : 1, true, &h->jit));
         } else {
-            CK(klara_jit_create(desc->custom_src, desc->sampler, desc->ndims, E, G, plan.modes, plan.nmodes, true, &h->jit));
+            CK(klara_jit_create(desc->custom_src, desc->sampler, desc->ndims, E, G, plan.modes, plan.nmodes, true, &h->jit, desc->smmala_softabs > 0.0));
         }
     } else if (desc->target == KLARA_TARGET_LOGISTIC && kind == 5) {
         // the A fragments of both MFMA passes in the order of consumption (klara_logit_mfma.h logitm_eval), zero beyond the n rows / D columns:
@@ -570,6 +575,7 @@ static KParams make_params(klara_handle* h)
     p.ha0 = d.hier_gamma_a; p.hb0 = d.hier_gamma_b;
     p.cdata = (decltype(p.cdata))h->cdata; p.cndata = d.custom_ndata;
     p.clock_probe = (decltype(p.clock_probe))h->clock_probe;
+    p.smmala_softabs = d.smmala_softabs;
     return p;
 }
 
@@ -2363,6 +2369,20 @@ extern "C" klara_status klara_check_custom_target(const char* src, int32_t sampl
     if (plan.jit_pair) return klara_jit_create_pair(src, sampler, ndims, plan.E / 2, plan.G, false, false, false, modes, 1, false, nullptr);
     const std::string whole = plan.rewrite == KLARA_REWRITE_PAIR_AS_WHOLE ? pair_as_whole_source(src) : std::string(src);
     return klara_jit_create(whole.c_str(), sampler, ndims, plan.E, plan.G, modes, 1, false, nullptr);
+}
+
+// ... and the SMMALA kernels with the softabs transform of the metric (klara_desc.smmala_softabs > 0): the variant klara_create compiles for such a job
+extern "C" klara_status klara_check_custom_target_softabs(const char* src, int32_t ndims)
+{
+    if (!src || ndims <= 0) return KLARA_ERR_INVALID_ARG;
+    klara_desc d;
+    memset(&d, 0, sizeof(d));
+    d.sampler = KLARA_SAMPLER_SMMALA; d.target = KLARA_TARGET_CUSTOM; d.ndims = ndims; d.nchains = 1; d.custom_src = src; d.smmala_softabs = 1.0;
+    KlaraPlan plan;
+    const klara_status st = klara_plan_job(d, klara_read_overrides(), &plan);
+    if (st != KLARA_OK) return st;
+    const int modes[1] = { 0 };
+    return klara_jit_create(src, KLARA_SAMPLER_SMMALA, ndims, plan.E, plan.G, modes, 1, false, nullptr, true);
 }
 
 extern "C" const char* klara_compile_log(void) { return klara_jit_log(); }

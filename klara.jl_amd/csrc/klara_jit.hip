@@ -200,7 +200,8 @@ std::string init_expr(int sampler, int E, int G)
 }
 
 // compile (or fetch) the code object of one (source, sampler, D, modes) combination
-klara_status compile(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, const CodeObject** out, const PairForm* pf = nullptr)
+klara_status compile(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, const CodeObject** out, const PairForm* pf = nullptr,
+                     bool softabs = false)
 {
     g_log.clear();
     Rtc* r = rtc();
@@ -208,6 +209,7 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
     std::string key = std::to_string(sampler) + "/" + std::to_string(D) + "/" + std::to_string(E) + "x" + std::to_string(G) + "/";
     if (pf) key += "pair/" + std::to_string(pf->NP) + "/" + std::to_string(pf->Q) + "/" + std::to_string((int)pf->mon) + std::to_string((int)pf->tune) + std::to_string((int)pf->da) + "/";
     for (int i = 0; i < nmodes; ++i) key += std::to_string(modes[i]) + ",";
+    if (softabs) key += "softabs/";
     key += (getenv("KLARA_JIT_UNROLL_MAX_E") ? getenv("KLARA_JIT_UNROLL_MAX_E") : ""); key += "\n"; key += src;
     {
         std::lock_guard<std::mutex> lk(g_cache_mutex);
@@ -256,6 +258,7 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
     tu += "#define KLARA_D " + std::to_string(D) + "\n";
     if (!needgrad) tu += "#define KLARA_CUSTOM_NOGRAD 1\n";
     if (sampler == KLARA_SAMPLER_SMMALA) tu += "#define KLARA_SMMALA 1\n";
+    if (sampler == KLARA_SAMPLER_SMMALA && softabs) tu += "#define KLARA_SMMALA_SOFTABS 1\n";      // klara_desc.smmala_softabs > 0 (klara_kernels.h, klara_softabs.h)
     int unroll_max = KLARA_JIT_UNROLL_MAX_E;
     if (const char* s = getenv("KLARA_JIT_UNROLL_MAX_E")) unroll_max = atoi(s);
     const bool loops = E > unroll_max;                    // element loops over scratch-resident arrays (klara_kernels.h)
@@ -337,10 +340,10 @@ klara_status klara_jit_create_pair(const char* src, int sampler, int D, int NP, 
     return KLARA_OK;
 }
 
-klara_status klara_jit_create(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, bool load, KlaraJit** out)
+klara_status klara_jit_create(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, bool load, KlaraJit** out, bool softabs)
 {
     const CodeObject* co = nullptr;
-    klara_status st = compile(src, sampler, D, E, G, modes, nmodes, &co);
+    klara_status st = compile(src, sampler, D, E, G, modes, nmodes, &co, nullptr, softabs);
     if (st != KLARA_OK || !load) return st;
     KlaraJit* j = new (std::nothrow) KlaraJit();
     if (!j) return KLARA_ERR_NOMEM;

@@ -73,6 +73,11 @@ __host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { re
 #ifndef KLARA_E4_WAVES_PLAIN
 #define KLARA_E4_WAVES_PLAIN 3   // the specialised (no tuner, no monitor) E=4 kernels fit 168 VGPRs
 #endif
+#ifdef KLARA_SMMALA_SOFTABS        // the SMMALA kernels with the softabs transform of the metric (run-time compiled only): see k_transitions' launch bounds
+#define KLARA_SMMALA_SOFTABS_E4_ONE_WAVE 1
+#else
+#define KLARA_SMMALA_SOFTABS_E4_ONE_WAVE 0
+#endif
 #define KLARA_SLICE_ATT_BITS 14
 #define KLARA_SLICE_MAX_ATT ((1 << KLARA_SLICE_ATT_BITS) - 1)
 #define KLARA_INIT_TRANSITION ((((uint64_t)1) << 40) - 1)
@@ -138,6 +143,7 @@ struct KParams {
     // shader-clock probe of the pair-transposed kernels (klara_get_shader_clock): one workgroup in the middle of the grid writes
     // (s_memtime, s_memrealtime) when it starts [2], [3] and when it ends [0], [1] — stores only, nothing kept in registers
     gulong* clock_probe;
+    double smmala_softabs;                     // SMMALA: the a of softabs(G, a) applied to every metric (klara_softabs.h), 0 = no transform
 };
 
 // Per-launch values, passed by value.  Everything else (KParams) is static for a handle and lives in device memory:
@@ -997,6 +1003,37 @@ KLARA_PRAGMA_UNROLL_E
     }
     return q;
 }
+#ifdef KLARA_SMMALA_SOFTABS
+// klara_desc.smmala_softabs > 0 (run-time compiled kernels only: klara_jit.hip defines KLARA_SMMALA_SOFTABS next to KLARA_SMMALA): the metric, with T::metric_diag
+// added, becomes softabs(G, a) in the lane's registers (klara_softabs.h; KLARA_D is the job's dimension, so every loop unrolls) before it is factored.  The
+// factorisation then has nothing left to add to the diagonal: the value returned is what it is handed as `diag`.
+// The eigenvectors (D^2 doubles a lane) are registers up to D = 4, where the kernels then take one wavefront per SIMD (k_transitions' launch bounds: at two, the
+// 256 registers spill 20-120 B; in LDS they spilled more, 68-336 B).  From D = 5 on (E = 8) they live in the workgroup's LDS, entry by entry interleaved over its 256
+// lanes (a wavefront's access is 64 consecutive doubles: no bank conflict): 128 registers on top of a kernel that already fills the 512 of one wavefront per
+// SIMD — 1,000-1,180 B of scratch a lane with them in registers, 280-430 B with them in LDS (128 KB at D = 8, which that occupancy leaves free: one workgroup per
+// compute unit).  A lane reads and writes its own entries only: no barrier.
+#include "klara_softabs.h"
+#ifndef KLARA_SOFTABS_LDS_MIN_D
+#define KLARA_SOFTABS_LDS_MIN_D 5
+#endif
+#if KLARA_D >= KLARA_SOFTABS_LDS_MIN_D
+__shared__ double klara_softabs_q[KLARA_D * KLARA_D * 256];
+#endif
+template <class T, int E>
+__device__ __forceinline__ double smmala_softabs_metric(const KParams& p, double* gm)
+{
+    const double diag = T::metric_diag(p);
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < KLARA_D; ++j) gm[ktri(j, j, E)] = gm[ktri(j, j, E)] + diag;
+#if KLARA_D >= KLARA_SOFTABS_LDS_MIN_D
+    ksa_softabs_tri(gm, KLARA_D, E, p.smmala_softabs, klara_softabs_q + threadIdx.x, 256);
+#else
+    double q[KLARA_D * KLARA_D];
+    ksa_softabs_tri(gm, KLARA_D, E, p.smmala_softabs, q, 1);
+#endif
+    return 0.0;
+}
+#endif
 // the metric, its factor and the drift at x with gradient g (the launch start of a chain group and the SMMALA start-state check)
 template <class T, int E>
 __device__ __forceinline__ bool smmala_state_at(const KParams& p, const T& tg, const LaneCtx<E>& cx, const double (&x)[E], const double (&g)[E],
@@ -1004,7 +1041,11 @@ __device__ __forceinline__ bool smmala_state_at(const KParams& p, const T& tg, c
 {
     double gm[SmmalaRegs<E>::NT], dummy, gd[E];
     tg.template eval<false, false, SmmalaRegs<E>::NT>(cx, x, dummy, gd, gm);
+#ifdef KLARA_SMMALA_SOFTABS
+    const bool pd = smmala_factor<E>(gm, p.D, smmala_softabs_metric<T, E>(p, gm), s);
+#else
     const bool pd = smmala_factor<E>(gm, p.D, T::metric_diag(p), s);
+#endif
     smmala_drift<E>(s, g);
     return pd;
 }
@@ -1034,7 +1075,11 @@ KLARA_PRAGMA_UNROLL_E
     group_allreduce<1>(red, cx.G, cx.lane);
     const double ltp = tg.finalize(red[0]);
     SmmalaRegs<E> sn;
+#ifdef KLARA_SMMALA_SOFTABS
+    const bool pd = smmala_factor<E>(gm, p.D, smmala_softabs_metric<T, E>(p, gm), sn);   // :117-118 (the transform), :133
+#else
     const bool pd = smmala_factor<E>(gm, p.D, T::metric_diag(p), sn);               // :133 (the factor instead of inv)
+#endif
     smmala_drift<E>(sn, gp);                                                        // :135
 KLARA_PRAGMA_UNROLL_E
     for (int e = 0; e < E; ++e) dd[e] = x[e] - (xp[e] + halfh * sn.f[e]);           // :137
@@ -1384,8 +1429,9 @@ template <int SAMPLER, int TARGET, int E, int GT, int MODE>
 // (MALA and HMC on the logistic target at E = 4 — cfg 4 — ask for 4 wavefronts per SIMD: its row loop is a chain of exp / log / division latencies that two
 //  wavefronts cannot cover; the 128-register budget spills 156-272 B outside the row loop and still measured 1.01e9 against 8.1e8
 //  transitions/s with running sums, 1.05e9 against 9.4e8 without, same box)
-__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && !(MODE & 1)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
-                                                                                                  metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2) */ :
+__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
+                                                                                                  metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2; with the
+                                                                                                  softabs transform's eigenvectors: 20-120 B in every mode) */ :
                                    TARGET == KLARA_TARGET_CUSTOM && GT > 1 ? 2 /* staged closures: two workgroups' rows fit a CU's LDS */ :
                                    E == 2 ? (TARGET == KLARA_TARGET_GAUSS_DIAG ? KLARA_E2_DIAG_WAVES : 3) : (E == 4 ? (TARGET == KLARA_TARGET_LOGISTIC && SAMPLER == KLARA_SAMPLER_MALA ? KLARA_E4_WAVES_LOGISTIC
                                                                   : TARGET == KLARA_TARGET_LOGISTIC && SAMPLER == KLARA_SAMPLER_HMC ? KLARA_E4_WAVES_LOGISTIC_HMC
@@ -1650,7 +1696,11 @@ __global__ __launch_bounds__(256) void k_init_smmala(const KParams p, int needgr
     group_allreduce<1>(red, cx.G, cx.lane);
     const double lt = tg.finalize(red[0]);
     SmmalaRegs<E> s;
+#ifdef KLARA_SMMALA_SOFTABS
+    const bool pd = smmala_factor<E>(gm, p.D, smmala_softabs_metric<T, E>(p, gm), s);    // SMMALA.jl:167-168
+#else
     const bool pd = smmala_factor<E>(gm, p.D, T::metric_diag(p), s);
+#endif
     bool bad = cx.chain_ok && (!kfinite(lt) || !pd);
     store_vec<E>(cx, p.GR, p.D, g);
 KLARA_PRAGMA_UNROLL_E

@@ -166,9 +166,11 @@ hipError_t klara_launch_hiert(const KParams* p, const KLaunch& kl, int sampler, 
 hipError_t klara_launch_hiert_init(const KParams& p, int RPL, int NT, int needgrad, dim3 grid, hipStream_t st);
 
 // user-defined targets (KLARA_TARGET_CUSTOM): run-time compiled instantiations of k_init / k_transitions (klara_jit.hip);
-// `modes` are the k_transitions MODE values the job can launch; load = false only compiles (no GPU needed)
+// `modes` are the k_transitions MODE values the job can launch; load = false only compiles (no GPU needed); softabs: the SMMALA kernels with
+// the softabs transform of the metric (klara_desc.smmala_softabs > 0, klara_softabs.h) — a code object of its own
 struct KlaraJit;
-klara_status klara_jit_create(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, bool load, KlaraJit** out);
+klara_status klara_jit_create(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, bool load, KlaraJit** out,
+                              bool softabs = false);
 // pair closures (`#define KLARA_USER_PAIR_TARGET 1` + klara_user_pair, klara_diagt.h USERPAIR): k_diagt_init / k_diagt instantiated
 // for the job's NP pairs per lane, Q lanes per chain and monitor / tuner flags; modes: 0 = fused launches, 1 = one transition per launch
 klara_status klara_jit_create_pair(const char* src, int sampler, int D, int NP, int Q, bool mon, bool tune, bool da, const int* modes, int nmodes,

@@ -197,6 +197,12 @@ class CustomTarget:
             raise L.KlaraError(L.ERR_COMPILE, "klara_check_custom_target: the SMMALA sampler needs klara_user_tensorlogtarget")
         L.check(L.load().klara_check_custom_target(self.source.encode(), int(sampler), self.ndims), "klara_check_custom_target")
 
+    def check_softabs(self) -> None:
+        """check(SAMPLER_SMMALA) for the kernels with the softabs transform of the metric (Engine(..., smmala_softabs=a), SMMALA(h, SoftAbs(a)))"""
+        if not self.has_tensor:
+            raise L.KlaraError(L.ERR_COMPILE, "klara_check_custom_target_softabs: the SMMALA sampler needs klara_user_tensorlogtarget")
+        L.check(L.load().klara_check_custom_target_softabs(self.source.encode(), self.ndims), "klara_check_custom_target_softabs")
+
 
 @dataclass
 class HierNormalTarget:
@@ -252,7 +258,7 @@ class Engine:
                  da_t0: int = 10, da_kappa: float = 0.75,
                  seed: int = 20260927, chain_offset: int = 0, device: int = 0, monitor: int = 0,
                  steps_per_launch: int = 0, stream: int = 0, nstreams: int = 0, bm_batchlen: int = 0, hist_ring_cols: int = 0,
-                 acov_maxlag: int = 0, sparse_moves: int = 0):
+                 acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0):
         self._lib = L.load()
         self.target = target
         self.ndims = int(target.ndims)
@@ -306,6 +312,10 @@ class Engine:
         d.nstreams = int(nstreams)
         d.bm_batchlen = int(bm_batchlen)
         d.hist_ring_cols, d.acov_maxlag, d.sparse_moves = int(hist_ring_cols), int(acov_maxlag), int(sparse_moves)
+        # SMMALA(driftstep, H -> softabs(H, a)): the a of the metric's transform, 0 = none (klara_desc.smmala_softabs)
+        if float(smmala_softabs) > 0.0 and isinstance(target, LogisticTarget):
+            raise ValueError("softabs is not applied to the logistic target's metric: X' diag(r (1 - r)) X + I / lambda is positive definite by construction")
+        d.smmala_softabs = float(smmala_softabs)
         d.stream = C.c_void_p(int(stream)) if stream else None
         self._h = C.c_void_p()
         L.check(self._lib.klara_create(C.byref(d), C.byref(self._h)), "klara_create")

@@ -170,3 +170,13 @@ def lzv_chain(value, gradlogtarget):
 def qzv_chain(value, gradlogtarget):
     """qzv(s::ParameterNState{Continuous, Multivariate}) (zv.jl:84): (corrected series (n x D), a (K x D))."""
     return qzv(np.asarray(value).T, np.asarray(gradlogtarget).T)
+
+
+# ---------------------------------------------------------------- src/stats/metrics.jl
+def softabs(H, a: float = 1000.0) -> np.ndarray:
+    """softabs(hessian, a) of src/stats/metrics.jl:1-4, literally: `lambda, Q = eig(hessian); Q * diagm(lambda ./ tanh(a * lambda)) * Q'`.
+    LAPACK's symmetric eigen-decomposition (what Julia's `eig` takes for a symmetric matrix) and libm's tanh; a zero eigenvalue gives 0 / 0 as
+    in the reference.  The device form (klara.jl_amd/csrc/klara_softabs.h, klara_desc.smmala_softabs) is tested against this."""
+    H = np.asarray(H, dtype=np.float64)
+    lam, Q = np.linalg.eigh(H)
+    return (Q * (lam / np.tanh(float(a) * lam))) @ Q.T
