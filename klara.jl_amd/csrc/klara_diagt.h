@@ -684,16 +684,21 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
             } else if (SAMPLER == KLARA_SAMPLER_MALA) {                            // iterate/MALA.jl:78-128
                 const double h_ = tn.step, halfh = 0.5 * h_, sq = KCNT ? __builtin_sqrt(h_) : p.sqrt_step0;
                 const double half_inv_h = 0.5 * (KCNT ? 1.0 / h_ : p.inv_step0);
+                // UNITW: the gradient -2.0 * x is an exact scaling, so halfh * (-2.0 * x) and (-h) * x are one real number, rounded once
+                // either way: the same bits and one instruction less per mean (still a multiply and an add, never an fma).  It needs h to
+                // be a normal number (0.5 * h is exact) and -2 x not to overflow (|x| <= DBL_MAX / 2; lt is -inf from |x| ~ 1e154 on).
+                // Other weights keep halfh * (m2w * dd): halfh * m2w would round on its own.  The gradient that is stored stays -2.0 * x.
+                const double neg_h = -h_;
                 const auto mala_elem = [&](int e, double ze, int r) -> double {
-                    double term, ge, gpe;
-                    diag_elem<UNITW>(x[e], wv(e), m2wv(e), mv(e), term, ge);        // (the current gradient, re-formed)
-                    const double m_ = x[e] + halfh * ge;                                       // :83
+                    double term, ge = 0.0, gpe;
+                    if constexpr (!UNITW) diag_elem<UNITW>(x[e], wv(e), m2wv(e), mv(e), term, ge);   // (the current gradient, re-formed)
+                    const double m_ = UNITW ? x[e] + neg_h * x[e] : x[e] + halfh * ge;         // :83
                     const double xe = m_ + sq * ze;                                            // :84
                     diag_elem<UNITW>(xe, wv(e), m2wv(e), mv(e), term, gpe);         // :86
                     red[r] = red[r] + term;
                     const double q1 = m_ - xe;
                     red[r + 1] = red[r + 1] + (q1 * q1) * half_inv_h;                          // :90
-                    const double mup = xe + halfh * gpe;                                       // :91
+                    const double mup = UNITW ? xe + neg_h * xe : xe + halfh * gpe;             // :91
                     const double q2 = mup - x[e];
                     red[r + 2] = red[r + 2] + (q2 * q2) * half_inv_h;                          // :92
                     return xe;
@@ -751,16 +756,24 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 const double H0 = lt - 0.5 * k0[0];                                            // :137
 #pragma unroll
                 for (int e = 0; e < E; ++e) xp[e] = x[e];                                      // :139
-                grad_of(x, gp);                                                                // :140 (re-formed)
+                // UNITW diagonal: the gradient -2.0 * x is an exact scaling, so fma(kf, -2.0 * x, m) and fma(-2.0 * kf, x, m) round one
+                // real number once: the same bits without the gradient instruction and without gp (-2 * halfe = -eps exactly: eps is a
+                // normal number; -2 x does not overflow, see the MALA branch).  A finished chain (DA, !go) keeps xp and mom as before.
+                constexpr bool KFOLD = UNITW && !USERPAIR;
+                if constexpr (!KFOLD) grad_of(x, gp);                                          // :140 (re-formed)
                 const int nl = DA ? (chain_ok ? da_nleaps(p, eps) : 1) : p.nleaps;             // :142-144 (padding lanes: 1)
                 // leapfrog! nl times (:146-155, samplers.jl:122-134) in its merged form (deliberate deviation (7),
                 // mirrored by the oracle): adjacent half-kicks are one update, every update is one fma
 #pragma unroll
-                for (int e = 0; e < E; ++e) mom[e] = kd_fma(halfe, gp[e], mom[e]);
+                for (int e = 0; e < E; ++e) {
+                    if constexpr (KFOLD) mom[e] = kd_fma(-eps, x[e], mom[e]);
+                    else mom[e] = kd_fma(halfe, gp[e], mom[e]);
+                }
                 const int nlmax = DA ? wave_max_int(nl) : nl;
                 for (int l = 0; l < nlmax; ++l) {
                     const bool go = !DA || l < nl;
                     const double kf = l + 1 < nl ? eps : halfe;
+                    const double nkf2 = -2.0 * kf;
                     if constexpr (USERPAIR) {
 #pragma unroll
                         for (int pi = 0; pi < NP; ++pi) {
@@ -777,11 +790,16 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                         for (int e = 0; e < E; ++e) {
                             const double x1 = kd_fma(eps, mom[e], xp[e]);
                             xp[e] = go ? x1 : xp[e];
-                            double term, g1;
-                            diag_elem<UNITW>(xp[e], 1.0, m2wvl(e), mvl(e), term, g1);       // (term unused in the leapfrog)
-                            gp[e] = go ? g1 : gp[e];
-                            const double m2 = kd_fma(kf, gp[e], mom[e]);
-                            mom[e] = go ? m2 : mom[e];
+                            if constexpr (KFOLD) {
+                                const double m2 = kd_fma(nkf2, xp[e], mom[e]);
+                                mom[e] = go ? m2 : mom[e];
+                            } else {
+                                double term, g1;
+                                diag_elem<UNITW>(xp[e], 1.0, m2wvl(e), mvl(e), term, g1);   // (term unused in the leapfrog)
+                                gp[e] = go ? g1 : gp[e];
+                                const double m2 = kd_fma(kf, gp[e], mom[e]);
+                                mom[e] = go ? m2 : mom[e];
+                            }
                         }
                     }
                 }
