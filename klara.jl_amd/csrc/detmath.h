@@ -504,22 +504,33 @@ KD_FN_COLD double kd_erf(double x)
  * y = 2 pi (t + 2^-53), |y| <= 0.0123, is rotated onto the table entry:
  *   cos(a + y) = C cos y - S sin y,  sin(a + y) = S cos y + C sin y,  sin y / cos y - 1 by short Taylor polynomials
  * (dropped terms < 2e-20).  Absolute error < 2^-52; no quadrant logic, no division. */
-KD_FN void kd_sincos2pi_bits(uint64_t uu_bits, double* sn, double* cs)
+/* The evaluation is split where the table entry comes in: kd_sincos_rem forms sin y and cos y - 1 of the remainder (they depend on the bits
+ * below j alone), kd_sincos_rotate reads (C, S) and rotates.  kd_sincos2pi_bits is the two in sequence, so every caller computes the same
+ * bits; a caller whose remainder takes few distinct values may keep kd_sincos_rem's results in a table (kd_sincos2pi_tab20 below). */
+KD_FN void kd_sincos_rem(uint64_t uu_bits, double* sy_out, double* dc_out)
 {
     const double S1 = -0x1.5555555555555p-3, S2 = 0x1.1111111111111p-7, S3 = -0x1.a01a01a01a01ap-13;
     const double C2 = 0x1.5555555555555p-5, C3 = -0x1.6c16c16c16c17p-10;
     const uint32_t uh = (uint32_t)(uu_bits >> 32);
-    const uint32_t j = (uh >> 12) & 255u;
     const double uu = kd_u2d(uu_bits);
     const double cc = kd_u2d((uint64_t)((uh & 0xfffff000u) | 0x00000800u) << 32);
     const double t = uu - cc;
     const double y = kd_fma(t, KD_TWOPI_HI, kd_fma(t, KD_TWOPI_LO, KD_TWOPI_2M53));
     const double z = y * y;
-    const double sy = kd_fma(y * z, kd_fma(z, kd_fma(z, S3, S2), S1), y);       /* sin y */
-    const double dc = z * kd_fma(z, kd_fma(z, C3, C2), -0.5);                   /* cos y - 1 */
+    *sy_out = kd_fma(y * z, kd_fma(z, kd_fma(z, S3, S2), S1), y);               /* sin y */
+    *dc_out = z * kd_fma(z, kd_fma(z, C3, C2), -0.5);                           /* cos y - 1 */
+}
+KD_FN void kd_sincos_rotate(uint32_t j, double sy, double dc, double* sn, double* cs)
+{
     const double C = KD_SCTAB(2 * j), S = KD_SCTAB(2 * j + 1);
     *cs = kd_fma(-S, sy, kd_fma(C, dc, C));
     *sn = kd_fma(C, sy, kd_fma(S, dc, S));
+}
+KD_FN void kd_sincos2pi_bits(uint64_t uu_bits, double* sn, double* cs)
+{
+    double sy, dc;
+    kd_sincos_rem(uu_bits, &sy, &dc);
+    kd_sincos_rotate((uint32_t)(uu_bits >> 44) & 255u, sy, dc, sn, cs);
 }
 /* double-argument form for u in [0,1): u + (1 - 2^-53) is exact for every kd_u52 value (rounded otherwise) */
 KD_FN void kd_sincos2pi(double u, double* sn, double* cs)
@@ -571,18 +582,66 @@ KD_FN uint64_t kd_angle_bits20(uint32_t wb)              /* bits of 1 + (k + 1/2
     return ((uint64_t)(0x3ff00000u | (wb >> 12)) << 32) | 0x80000000ull;
 #endif
 }
+/* The 20-bit angle through a table of remainders.  With k = wb >> 12 the angle's bits are those of 1 + (k + 1/2) 2^-20: j = k >> 12 picks
+ * (C, S) and t = ((k & 0xfff) + 1/2 - 2048) 2^-20 depends on m = k & 0xfff alone, so (sin y, cos y - 1) take 4,096 distinct values.
+ * kd_sincos_rem_entry(m) is the pair of remainder m, formed by kd_sincos_rem on the bits kd_angle_bits20 forms: a table T[m] of them holds the
+ * bits the arithmetic form computes, and kd_sincos_rotate(j, T[m]) is kd_sincos2pi_bits(kd_angle_bits20(wb)) bit for bit
+ * (tests/test_sincos_table_host.py, all 2^20 angles).  On the GPU the table is 64 KB of dynamic LDS, filled by the kernel that uses it
+ * (kd_sincos_rem_to_lds: 16 entries per thread of a 256-thread workgroup) — 11 FP64 instructions per pair become one 16-byte LDS read. */
+#define KD_SCREM_ENTRIES 4096
+#define KD_SCREM_BYTES (KD_SCREM_ENTRIES * 16)
+KD_FN void kd_sincos_rem_entry(uint32_t m, double* sy_out, double* dc_out)
+{
+    kd_sincos_rem(kd_angle_bits20(m << 12), sy_out, dc_out);            /* (j = 0: the remainder does not depend on j) */
+}
+#if defined(__HIPCC__)
+typedef double kd_screm_t __attribute__((ext_vector_type(2)));
+/* the workgroup's dynamic LDS (KD_SCREM_BYTES of it); call before kd_tables_to_lds(), whose barrier publishes both */
+extern __shared__ __attribute__((aligned(16))) kd_screm_t kd_screm_lds[];
+__device__ __forceinline__ void kd_sincos_rem_to_lds()
+{
+    for (int m = (int)threadIdx.x; m < KD_SCREM_ENTRIES; m += (int)blockDim.x) {
+        double sy, dc;
+        kd_sincos_rem_entry((uint32_t)m, &sy, &dc);
+        kd_screm_lds[m] = kd_screm_t{ sy, dc };
+    }
+}
+__device__ __forceinline__ void kd_sincos2pi_tab20(uint32_t wb, double* sn, double* cs)
+{
+    const uint32_t k = wb >> 12;
+    const kd_screm_t r = kd_screm_lds[k & (KD_SCREM_ENTRIES - 1u)];
+    kd_sincos_rotate(k >> 12, r.x, r.y, sn, cs);
+}
+#endif
+/* (the transition kernels of klara_diagt.h that run many transitions per launch take the table form of the angle above — kd_normal_pair_w_t<true> —
+ * where the instruction count and the clock both fall: DESIGN.md section 4, profiles/ab_sincos_table.txt) */
+#if defined(__HIPCC__)
+template <bool TAB>                                      /* TAB: the angle through the workgroup's remainder table (device only) */
+KD_FN void kd_normal_pair_w_t(uint32_t wa, uint32_t wb, double* z0, double* z1, double* u1_out, double* logu1_out)
+#else
 KD_FN void kd_normal_pair_w(uint32_t wa, uint32_t wb, double* z0, double* z1, double* u1_out, double* logu1_out)
+#endif
 {
     const double u1 = kd_u44(wa, wb);
     const double lg = kd_log_u01(u1);
     const double rad = kd_sqrt_radicand(-2.0 * lg);
     double sn, cs;
+#if defined(__HIPCC__)
+    if constexpr (TAB) kd_sincos2pi_tab20(wb, &sn, &cs);
+    else
+#endif
     kd_sincos2pi_bits(kd_angle_bits20(wb), &sn, &cs);
     *z0 = rad * cs;
     *z1 = rad * sn;
     *u1_out = u1;
     *logu1_out = lg;
 }
+#if defined(__HIPCC__)
+KD_FN void kd_normal_pair_w(uint32_t wa, uint32_t wb, double* z0, double* z1, double* u1_out, double* logu1_out)
+{
+    kd_normal_pair_w_t<false>(wa, wb, z0, z1, u1_out, logu1_out);
+}
+#endif
 
 /* Which 64 bits: element pair p (elements 2p, 2p + 1 of a D-vector, p < ceil(D/2)) takes half (p >> 3) & 1 — words (x, y) or (z, w) —
  * of block slot (p & 7) + 8 (p >> 4): pairs p and p + 8 share a block.  Both sit in the same lane in every pair-transposed layout

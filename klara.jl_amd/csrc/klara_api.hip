@@ -2201,8 +2201,24 @@ __global__ void k_math(int op, long long n, const double* in, const double* in2,
     case 10: kd_softplus_logistic(in[i], &s, &c); out[i] = s; break;
     case 11: kd_softplus_logistic(in[i], &s, &c); out[i] = c; break;
     case 12: out[i] = kd_log12(in[i]); break;
+    // the 20-bit angle of kd_normal_pair_w at index k = in[i] (0 <= k < 2^20), arithmetic form: sin, cos  (ops 13 / 14 are its table form, k_math_sctab)
+    case 15: kd_sincos2pi_bits(kd_angle_bits20((uint32_t)in[i] << 12), &s, &c); out[i] = s; break;
+    case 16: kd_sincos2pi_bits(kd_angle_bits20((uint32_t)in[i] << 12), &s, &c); out[i] = c; break;
     default: out[i] = in[i] / in2[i]; break;
     }
+}
+
+// ops 13 / 14: sin / cos of the same angle through the remainder table (kd_sincos2pi_tab20), which every workgroup fills first — as the transition
+// kernels that take the table do (klara_diagt.h SCTAB)
+__global__ __launch_bounds__(256) void k_math_sctab(int op, long long n, const double* in, double* out)
+{
+    kd_sincos_rem_to_lds();
+    kd_tables_to_lds();
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s, c;
+    kd_sincos2pi_tab20((uint32_t)in[i] << 12, &s, &c);
+    out[i] = op == 13 ? s : c;
 }
 
 extern "C" klara_status klara_selftest_math(int32_t device, int32_t op, int64_t n, const double* in,
@@ -2217,8 +2233,14 @@ extern "C" klara_status klara_selftest_math(int32_t device, int32_t op, int64_t 
     if (e == hipSuccess) e = hipMemcpy(di, in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(di2, in2 ? in2 : in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (long long)n, di, di2, dout);
-        e = hipGetLastError();
+        if (op == 13 || op == 14) {
+            e = hipFuncSetAttribute((const void*)k_math_sctab, hipFuncAttributeMaxDynamicSharedMemorySize, KD_SCREM_BYTES);
+            // (4,096 results per workgroup: the fill is a quarter of a workgroup's work, not all of it)
+            if (e == hipSuccess) hipLaunchKernelGGL(k_math_sctab, dim3((unsigned)((n + 255) / 256)), dim3(256), KD_SCREM_BYTES, 0, op, (long long)n, di, dout);
+        } else {
+            hipLaunchKernelGGL(k_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (long long)n, di, di2, dout);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
     (void)dfree(di); (void)dfree(di2); (void)dfree(dout);

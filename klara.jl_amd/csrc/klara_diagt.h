@@ -314,7 +314,8 @@ template <int Q> struct PairShare {
     static constexpr int STEP = Q <= 8 ? 8 / Q : 0;
     static constexpr bool second(int p) { return STEP != 0 && ((p / (STEP ? STEP : 1)) & 1) != 0; }
 };
-template <int NP, int Q>
+// SCTAB: the angle's remainder terms come from the workgroup's table (detmath.h kd_normal_pair_w_t<true>) — the same bits.
+template <int NP, int Q, bool SCTAB = false>
 __device__ __forceinline__ void pair_normals(const PairCtx<NP, Q>& c, unsigned long long seed, unsigned long long gchain,
                                              unsigned long long t, int p, uint32_t (&stash)[4], double& z0, double& z1, double& u1, double& lg1)
 {
@@ -334,7 +335,7 @@ __device__ __forceinline__ void pair_normals(const PairCtx<NP, Q>& c, unsigned l
             wa = hb ? b.z : b.x; wb = hb ? b.w : b.y;
         }
     }
-    kd_normal_pair_w(wa, wb, &z0, &z1, &u1, &lg1);
+    kd_normal_pair_w_t<SCTAB>(wa, wb, &z0, &z1, &u1, &lg1);
     KLARA_PIN(z0); KLARA_PIN(z1);        // formed HERE: left to itself the compiler sinks the transforms of the stashed halves towards their uses (+60 registers)
     if (p == NP - 1 && !c.last_ok) z0 = 0.0;
     if (p == NP - 1 && !c.last_full) z1 = 0.0;
@@ -373,6 +374,25 @@ __host__ __device__ constexpr int diagt_min_waves()       // wavefronts per SIMD
                    : (Q == 4 && NP <= 13 && !TUNE ? (SAMPLER == KLARA_SAMPLER_MALA ? KLARA_Q4_MALA_WF : 2) : 1);
 }
 
+// SCTAB: Box-Muller reads the small-angle terms (sin y, cos y - 1) of its 20-bit angle from a 4,096-entry LDS table that the workgroup fills
+// first (detmath.h kd_sincos_rem_to_lds; 64 KB of dynamic LDS, so the launcher asks for it) instead of forming them per pair: 11 FP64
+// instructions per pair less for one 16-byte LDS read, the same bits.  Taken by the two kernels of the headline job (diagt_sctab(): untuned
+// monitored MALA on the unit diagonal, 13 pairs per lane on 4 lanes and 7 on 8) for launches of KLARA_SCTAB_MIN_STEPS transitions or more
+// (klara_launch.h diagt_go; shorter launches run the arithmetic instantiation).  The threshold is reasoned, not measured: the fill is 16
+// entries x 16 instructions per thread and a transition saves about 165, which leaves out what the 4-lane kernel pays for the table in
+// occupancy; at 8 transitions per launch the table is measured to pay (-4.8 %), with fewer it has not been timed.  With the table a workgroup
+// holds 72 KB of the compute unit's 160: two workgroups of 256 threads, two wavefronts per SIMD — what the 8-lane kernel runs at anyway; the
+// 4-lane kernel gives up its third wavefront for it and still comes out ahead (-5.6 % at 32 transitions per launch).  The other
+// instantiations keep the arithmetic: none of them has been timed with the table.  profiles/ab_sincos_table.txt.
+#ifndef KLARA_SCTAB_MIN_STEPS
+#define KLARA_SCTAB_MIN_STEPS 8
+#endif
+template <int SAMPLER, int NP, int Q, bool ONESTEP, bool UNITW, bool MON, bool TUNE>
+__host__ __device__ constexpr bool diagt_sctab()
+{
+    return SAMPLER == KLARA_SAMPLER_MALA && ((Q == 4 && NP == 13) || (Q == 8 && NP == 7)) && !ONESTEP && UNITW && MON && !TUNE;
+}
+
 // USERPAIR (run-time compiled instantiations only, klara_custom_pair.h): the target is the user's pair closure
 //     lt(x) = sum over element pairs P of klara_user_pair(x[2P], x[2P+1], P, ...)      (it also returns the pair's two partial derivatives)
 // instead of the diagonal Gaussian — the device form of BasicContMuvParameter(:p, logtarget=f, gradlogtarget=g)
@@ -384,7 +404,7 @@ __host__ __device__ constexpr int diagt_min_waves()       // wavefronts per SIMD
 #else
 #define KLARA_PAIR_CALL(a, b, P, g0, g1) 0.0
 #endif
-template <int SAMPLER, int NP, int Q, bool ONESTEP, bool UNITW, bool MON, bool TUNE = false, bool DA = false, bool USERPAIR = false>
+template <int SAMPLER, int NP, int Q, bool ONESTEP, bool UNITW, bool MON, bool TUNE = false, bool DA = false, bool USERPAIR = false, bool SCTAB = false>
 __global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_SLICE && NP <= 8 && !MON && !TUNE ? KLARA_DT_SLICE_WF : diagt_min_waves<SAMPLER, NP, Q, ONESTEP, TUNE>()))
 void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 {
@@ -392,6 +412,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
     static_assert(!USERPAIR, "pair closures exist in run-time compiled translation units only");
 #endif
     static_assert(!USERPAIR || (UNITW && Q >= 8), "pair closures: 8 or more lanes per chain");
+    static_assert(!SCTAB || (!ONESTEP && !USERPAIR && SAMPLER != KLARA_SAMPLER_SLICE), "the remainder table: fused launches of the built-in MH / MALA / HMC kernels");
     if (ka.cell_in != nullptr && *ka.cell_in != ka.my_mode) return;       // (launch-uniform: the sibling kernel runs this launch)
     static_assert(!(ONESTEP && (MON || TUNE)), "monitored / tuned jobs run the committing kernel");
     static_assert(!DA || (TUNE && SAMPLER == KLARA_SAMPLER_HMC), "dual averaging: tuned HMC");
@@ -417,6 +438,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
         }
     }
     auto_begin();
+    if constexpr (SCTAB) kd_sincos_rem_to_lds();
     kd_tables_to_lds();          // (ends with the workgroup barrier)
     if (p.clock_probe != nullptr && blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) {
         p.clock_probe[2] = __builtin_amdgcn_s_memtime(); p.clock_probe[3] = __builtin_amdgcn_s_memrealtime();
@@ -541,7 +563,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
             if (ZFIRST) {
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
-                    pair_normals<NP, Q>(cx, p.seed, gchain, t, pi, nstash, z[2 * pi], z[2 * pi + 1], u_last, lg_last);
+                    pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, z[2 * pi], z[2 * pi + 1], u_last, lg_last);
                     KLARA_DT_PAIR_FENCE(pi);
                 }
             }
@@ -653,7 +675,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
                     double z0 = ZFIRST ? z[(2 * pi) % (ZFIRST ? E : 2)] : 0.0, z1 = ZFIRST ? z[(2 * pi + 1) % (ZFIRST ? E : 2)] : 0.0;
-                    if (!ZFIRST) pair_normals<NP, Q>(cx, p.seed, gchain, t, pi, nstash, z0, z1, u_last, lg_last);
+                    if (!ZFIRST) pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, z0, z1, u_last, lg_last);
                     const int r = (NR == 2 && (pi & 1)) ? 3 : 0;
                     if constexpr (USERPAIR) {
                         const double a = x[2 * pi] + sig[2 * pi] * z0, b = x[2 * pi + 1] + sig[2 * pi + 1] * z1;      // MH.jl:79
@@ -706,7 +728,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
                     double z0 = ZFIRST ? z[(2 * pi) % (ZFIRST ? E : 2)] : 0.0, z1 = ZFIRST ? z[(2 * pi + 1) % (ZFIRST ? E : 2)] : 0.0;
-                    if (!ZFIRST) pair_normals<NP, Q>(cx, p.seed, gchain, t, pi, nstash, z0, z1, u_last, lg_last);
+                    if (!ZFIRST) pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, z0, z1, u_last, lg_last);
                     const int r = (NR == 2 && (pi & 1)) ? 3 : 0;
                     if constexpr (USERPAIR) {
                         double nt, ge0, ge1, gp0, gp1;
@@ -746,7 +768,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 double k0[NR] = {};
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
-                    pair_normals<NP, Q>(cx, p.seed, gchain, t, pi, nstash, mom[2 * pi], mom[2 * pi + 1], u_last, lg_last);   // :135
+                    pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, mom[2 * pi], mom[2 * pi + 1], u_last, lg_last);   // :135
                     const int r = (NR == 2 && (pi & 1)) ? 1 : 0;
                     k0[r] = k0[r] + mom[2 * pi] * mom[2 * pi];
                     k0[r] = k0[r] + mom[2 * pi + 1] * mom[2 * pi + 1];

@@ -114,11 +114,23 @@ hipError_t klara_launch_diagt_init_q4(const KParams& p, int NP, int needgrad, di
 #endif
 #define KLARA_DIAGT_NP_MAX 8
 
-// one launch of a pair-transposed kernel over `nwaves` chain groups: one wavefront each, four per workgroup
+// one launch of a pair-transposed kernel over `nwaves` chain groups: one wavefront each, four per workgroup.  The kernels that read the angle's
+// remainder terms from an LDS table (klara_diagt.h SCTAB) get the table's 64 KB of dynamic LDS; a launch too short to amortise the fill
+// runs the arithmetic instantiation (the same bits).
 template <int S, int NP_, int Q_, bool ONESTEP, bool UNITW, bool MON, bool TUNE = false, bool DA = false>
 static hipError_t diagt_go(const KParams* p, const KLaunch& kl, const KAuto& ka, long long nwaves, hipStream_t st)
 {
-    return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA>, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, st, p, kl, ka);
+    const dim3 grid((unsigned)((nwaves + 3) / 4)), blk(256);
+    if constexpr (diagt_sctab<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE>()) {
+        if (kl.nsteps >= KLARA_SCTAB_MIN_STEPS) {
+            const auto kern = k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA, false, true>;
+            // a launch gets 64 KB of LDS without asking (8 KB of math tables + the table is more): asked for before the launch, like every launcher here
+            const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, KD_SCREM_BYTES);
+            if (e != hipSuccess) return e;
+            return klara_go(kern, grid, blk, (size_t)KD_SCREM_BYTES, st, p, kl, ka);
+        }
+    }
+    return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA>, grid, blk, 0, st, p, kl, ka);
 }
 
 #if KLARA_DIAGT_Q == 4     // (no tuned / dual-averaging instantiations: those jobs take the 8-lane form)
