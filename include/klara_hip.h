@@ -67,7 +67,7 @@ typedef enum klara_status {
     KLARA_ERR_COMPILE = 8          /* CUSTOM target: the user's source did not compile (klara_compile_log) */
 } klara_status;
 
-/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA}.jl */
+/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM}.jl */
 typedef enum klara_sampler {
     KLARA_SAMPLER_MH = 0,      /* MH(sigma): symmetric normal random walk, MH.jl:63-66            */
     KLARA_SAMPLER_MALA = 1,    /* MALA(driftstep), MALA.jl:61-70                                   */
@@ -81,7 +81,17 @@ typedef enum klara_sampler {
      * defines KLARA_USER_FN void klara_user_tensorlogtarget(const double* x, int D, const double* data, long long ndata, double* G) (the
      * metric, row-major D x D; a source without it is KLARA_ERR_COMPILE).  Every other target (the likelihood + prior form and pair closures
      * included), and D >= 9, is KLARA_ERR_UNSUPPORTED. */
-    KLARA_SAMPLER_SMMALA = 4
+    KLARA_SAMPLER_SMMALA = 4,
+    /* (5 is reserved: klara_create and klara_check_custom_target refuse it with KLARA_ERR_INVALID_ARG) */
+    /* RAM(S0; targetrate, gamma), RAM.jl:94-111, iterate/RAM.jl:65-130 (Vihola 2012): the random walk x' = x + S z whose lower-triangular
+     * factor S every chain adapts by itself — after EVERY transition, accepted or not, S <- chol(S (I + c z z') S')' with
+     * c = min(1, D count^-gamma) (min(1, exp(ratio)) - targetrate) / (z . z).  Draws exactly what MH draws (D normals and one accept
+     * uniform per transition) and needs no gradient.  KLARA_TARGET_LOGISTIC with D <= 8 (layout kinds 0 and 2) and KLARA_TARGET_CUSTOM
+     * whole-vector closures (plain or likelihood + prior form) with D <= 8 at one chain per lane; every other target, pair closures,
+     * more lanes per chain and D >= 9 are KLARA_ERR_UNSUPPORTED.  Only KLARA_TUNER_VANILLA (verbose or not: it counts as for MH);
+     * another tuner is KLARA_ERR_UNSUPPORTED.  S lives on the device per chain (klara_get_ram_factor / klara_set_ram_factor);
+     * klara_set_state and klara_reset put S = klara_desc.ram_S0 and restart the count.  DESIGN.md section 2, R1-R4. */
+    KLARA_SAMPLER_RAM = 6
 } klara_sampler;
 
 /* Target families evaluated on device (stand-ins for the user closures of
@@ -270,6 +280,10 @@ typedef struct klara_desc {
                                     KLARA_TARGET_LOGISTIC with a > 0 is KLARA_ERR_UNSUPPORTED: its metric X' diag(r (1 - r)) X + I / lambda is positive
                                     definite by construction and has no use for the transform.  Negative or non-finite, or a > 0 with another sampler:
                                     KLARA_ERR_INVALID_ARG. */
+    const double* ram_S0;        /* RAM: the initial factor, D x D row-major; the lower triangle is read and its diagonal must be > 0
+                                    (RAM.jl:100).  Required for KLARA_SAMPLER_RAM; NULL for every other sampler (else KLARA_ERR_INVALID_ARG) */
+    double   ram_targetrate;     /* RAM: target acceptance rate, in (0, 1) (RAM.jl:101); 0 for every other sampler */
+    double   ram_gamma;          /* RAM: exponent of the step size eta = min(1, D count^-gamma), in (0.5, 1] (RAM.jl:102); 0 for every other sampler */
 
     uint64_t seed;               /* Philox key                                                       */
     uint32_t monitor;            /* KLARA_MON_* bits                                                 */
@@ -428,6 +442,13 @@ klara_status klara_get_tune(klara_handle* h, double* step, int64_t* accepted, in
                             int64_t* totproposed);
 /* dual-averaging state per chain (DualAveragingMCTune: eps_bar, h_bar); KLARA_TUNER_DUAL_AVERAGING only */
 klara_status klara_get_dual_averaging(klara_handle* h, double* epsbar, double* hbar);
+/* KLARA_SAMPLER_RAM: the chains' current factors, nchains x D x D row-major, lower triangular with zeros above the diagonal, and the
+ * number of factor updates skipped since klara_set_state / klara_reset because a pivot or z . z was not a finite positive number
+ * (0 in exact arithmetic).  Either pointer may be NULL.  KLARA_ERR_INVALID_ARG on a handle of another sampler. */
+klara_status klara_get_ram_factor(klara_handle* h, double* S, int64_t* skipped);
+/* KLARA_SAMPLER_RAM: per-chain factors for a warm start (nchains x D x D row-major, the lower triangles are read); the transition
+ * count is kept.  A diagonal entry that is not a finite positive number: KLARA_ERR_INVALID_ARG; before klara_set_state: KLARA_ERR_STATE. */
+klara_status klara_set_ram_factor(klara_handle* h, const double* S);
 
 /* Measurement: duration (ms, HIP events on the launch stream) and launch count of the transition
  * kernels enqueued by the last klara_run / klara_run_async (after synchronisation). */

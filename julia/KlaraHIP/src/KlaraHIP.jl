@@ -29,7 +29,7 @@
 # `finalizer(f, obj)`): the three differences are confined to the compatibility block below, everything else is common syntax.
 module KlaraHIP
 import Klara
-import Klara: output, MCJob, MH, MALA, SMMALA, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
+import Klara: output, MCJob, MH, MALA, SMMALA, RAM, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
               BasicContMuvParameterState, BasicContMuvParameterNState, erf_rate_score, logistic_rate_score,
               Parameter, GenericModel, VariableState, VariableStateVector, DiffOptions
 import Distributions
@@ -37,7 +37,7 @@ import Distributions: Continuous, Multivariate
 import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
-       check_custom_target_softabs, SoftAbs,
+       check_custom_target_softabs, SoftAbs, ramfactor,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
@@ -55,6 +55,7 @@ end
 const KLARA_ABI_VERSION = UInt32(6)
 const SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE = Int32(0), Int32(1), Int32(2), Int32(3)
 const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothing or SoftAbs(a); the logistic target or a CustomTarget's tensor, D <= 8
+const SAMPLER_RAM = Int32(6)         # RAM(S0; targetrate, γ): the logistic target or a CustomTarget's whole-vector closure, D <= 8 (5 is reserved)
 const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
@@ -78,6 +79,7 @@ struct KlaraDesc
     custom_src::Cstring; custom_data::Ptr{Float64}; custom_ndata::Int64; bm_batchlen::Int64
     hist_ring_cols::Int64; acov_maxlag::Int32; sparse_moves::Int32
     smmala_softabs::Float64
+    ram_S0::Ptr{Float64}; ram_targetrate::Float64; ram_gamma::Float64
     seed::UInt64; monitor::UInt32; steps_per_launch::Int32; stream::Ptr{Cvoid}
 end
 
@@ -95,6 +97,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
                     hier_prior_prec=1e-4, hier_gamma_a=1e-3, hier_gamma_b=1e-3,
                     custom_src=Cstring(C_NULL), custom_data=Ptr{Float64}(C_NULL), custom_ndata=0, bm_batchlen=0,
                     hist_ring_cols=0, acov_maxlag=0, sparse_moves=0, smmala_softabs=0.0,
+                    ram_S0=Ptr{Float64}(C_NULL), ram_targetrate=0.0, ram_gamma=0.0,
                     seed=UInt64(0), monitor=UInt32(0), steps_per_launch=0, stream=C_NULL)
     KlaraDesc(UInt32(sizeof(KlaraDesc)), KLARA_ABI_VERSION,
               sampler, target, tuner, tuner_mode,
@@ -111,6 +114,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               hier_prior_prec, hier_gamma_a, hier_gamma_b,
               custom_src, custom_data, custom_ndata, bm_batchlen,
               hist_ring_cols, acov_maxlag, sparse_moves, smmala_softabs,
+              ram_S0, ram_targetrate, ram_gamma,
               seed, monitor, steps_per_launch, stream)
 end
 
@@ -193,6 +197,7 @@ rowmajor(A::Matrix{Float64}) = collect(transpose(A))       # Julia is column-maj
 # Klara's structs -> klara_desc.  Field names read from Klara (file:line in /root/reference/src):
 #   MALA.driftstep                         samplers/MALA.jl:61-70
 #   SMMALA.driftstep, .transform (nothing or SoftAbs(a)) samplers/SMMALA.jl:127-137
+#   RAM.S0, .targetrate, .γ                samplers/RAM.jl:94-111
 #   HMC.leapstep, HMC.nleaps               samplers/HMC.jl:89-100
 #   SliceSampler.widths, .stepout          samplers/SliceSampler.jl:22-34
 #   MH.setproposal (sigma is inside the closure: MH(sigma) = MH(x -> MvNormal(x, sigma)))   samplers/MH.jl:46-66
@@ -245,6 +250,11 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         (tr === nothing || isa(tr, SoftAbs)) || error("SMMALA: the only transform of the metric that runs on the device is SoftAbs(a), as in SMMALA(1.25, SoftAbs(1000.)); a closure cannot be recognised")
         kw[:sampler] = SAMPLER_SMMALA; kw[:driftstep] = Float64(sampler.driftstep)
         kw[:smmala_softabs] = tr === nothing ? 0.0 : tr.a
+    elseif isa(sampler, RAM)                                # samplers/RAM.jl:94-111: the initial factor (lower triangular), target rate and exponent
+        S0 = rowmajor(convert(Matrix{Float64}, sampler.S0)); push!(keep, S0)
+        size(S0) == (D, D) || error("RAM: S0 must be D x D")
+        kw[:sampler] = SAMPLER_RAM; kw[:ram_S0] = pointer(S0)
+        kw[:ram_targetrate] = Float64(sampler.targetrate); kw[:ram_gamma] = Float64(sampler.γ)
     elseif isa(sampler, MALA)
         kw[:sampler] = SAMPLER_MALA; kw[:driftstep] = Float64(sampler.driftstep)
     elseif isa(sampler, HMC)
@@ -259,7 +269,7 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         sig = sqrt.(Distributions.var(prop)); push!(keep, sig)
         kw[:sampler] = SAMPLER_MH; kw[:mh_sigma] = pointer(sig)
     else
-        error("sampler $(typeof(sampler)) is not on the device path (MH, MALA, SMMALA, HMC, SliceSampler are)")
+        error("sampler $(typeof(sampler)) is not on the device path (MH, RAM, MALA, SMMALA, HMC, SliceSampler are)")
     end
     # --- tuner
     tn = tuner === nothing ? VanillaMCTuner() : tuner
@@ -342,6 +352,15 @@ function HIPMCJob(desc::KlaraDesc, X0::Matrix{Float64}, range)
     on_finalize(job, j -> ccall((:klara_destroy, lib), Cint, (Ptr{Cvoid},), j.handle))
     check(ccall((:klara_set_state, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), job.handle, X0), "klara_set_state")
     job
+end
+
+# ramfactor(job): (S, skipped) of a RAM job — S[:, :, c] is chain c's current lower-triangular factor (sstate.S of iterate/RAM.jl:129), skipped the
+# number of factor updates the device left out because a pivot was not a finite positive number (0 in exact arithmetic)
+function ramfactor(job::HIPMCJob)
+    St = newarray(Float64, job.ndims, job.ndims, job.nchains)       # row-major D x D per chain == the transposes, column-major
+    skipped = Ref{Clonglong}(0)
+    check(ccall((:klara_get_ram_factor, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Clonglong}), job.handle, St, skipped), "klara_get_ram_factor")
+    (permutedims(St, (2, 1, 3)), Int(skipped[]))
 end
 
 # run / reset: methods of Base.run / Base.reset — the generics Klara itself extends (src/Klara.jl:26-27; imported above)

@@ -22,6 +22,7 @@ LOGIT_MAX_LDS_DOUBLES = 18432     # KLARA_LOGIT_MAX_LDS_DOUBLES
 OK, ERR_INVALID_ARG, ERR_NONFINITE_INIT, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ERR_STATE, ERR_SLICE_STUCK, ERR_COMPILE = range(9)
 # klara_sampler
 SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE, SAMPLER_SMMALA = range(5)
+SAMPLER_RAM = 6                   # (5 is reserved: the library refuses it)
 # klara_target
 TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = range(5)
 # klara_tuner / mode
@@ -55,6 +56,7 @@ class KlaraDesc(C.Structure):
         ("custom_src", C.c_char_p), ("custom_data", _dp), ("custom_ndata", C.c_int64), ("bm_batchlen", C.c_int64),
         ("hist_ring_cols", C.c_int64), ("acov_maxlag", C.c_int32), ("sparse_moves", C.c_int32),
         ("smmala_softabs", C.c_double),
+        ("ram_S0", _dp), ("ram_targetrate", C.c_double), ("ram_gamma", C.c_double),
         ("seed", C.c_uint64), ("monitor", C.c_uint32), ("steps_per_launch", C.c_int32),
         ("stream", C.c_void_p),
     ]
@@ -78,7 +80,7 @@ EXPORTS = [
     "klara_create", "klara_destroy", "klara_set_state", "klara_init_state_normal", "klara_run",
     "klara_run_async", "klara_synchronize", "klara_reset", "klara_stream_key", "klara_get_state", "klara_get_accept_mask", "klara_get_accept_rows",
     "klara_get_accept_counts", "klara_get_chain_sums", "klara_get_pooled_summaries", "klara_get_chain",
-    "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
+    "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_get_ram_factor", "klara_set_ram_factor", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
     "klara_selftest_rocrand_blocks", "klara_selftest_math", "klara_selftest_normal_tail", "klara_selftest_transition_normals", "klara_selftest_mfma_f64", "klara_selftest_mfma_f64_4x4x4", "klara_strerror",
     "klara_comm_unique_id", "klara_comm_init", "klara_comm_info", "klara_comm_destroy", "klara_gather_summaries", "klara_gather_moments",
     "klara_check_custom_target", "klara_check_custom_target_softabs", "klara_compile_log", "klara_selftest_plan", "klara_selftest_canary", "klara_abi_version",
@@ -122,6 +124,8 @@ def load() -> C.CDLL:
         "klara_get_chain_mcvar": [H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_get_tune": [H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_get_dual_averaging": [H, C.c_void_p, C.c_void_p],
+        "klara_get_ram_factor": [H, C.c_void_p, i64p],
+        "klara_set_ram_factor": [H, C.c_void_p],
         "klara_last_run_ms": [H, C.POINTER(C.c_double), i64p],
         "klara_device_ptrs": [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
         "klara_get_layout": [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],

@@ -104,6 +104,29 @@ class SMMALA(MCSampler):
         self.driftstep, self.transform = float(driftstep), transform
 
 
+class RAM(MCSampler):
+    """RAM(S0::Matrix) / RAM(S0::Vector) / RAM(S0=1., n=1), keywords targetrate=0.234, gamma=0.7 (the reference's γ) — RAM.jl:94-111:
+    the robust adaptive Metropolis sampler of Vihola (2012).  S0 is the initial lower-triangular factor of the proposal (a matrix: its
+    lower triangle; a vector: its diagonal; a number: that number n times).  On the device for D <= 8: the logistic regression and
+    user-defined whole-vector targets; a correlated Gaussian is run as such a closure.  Every chain adapts its own factor
+    (BasicMCJob.engine.ram_factor())."""
+    kind = L.SAMPLER_RAM
+
+    def __init__(self, S0=1.0, n: int = 1, *, targetrate: float = 0.234, gamma: float = 0.7):
+        a = np.asarray(S0, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(int(n), float(a))                        # RAM(S0::Real=1., n::Integer=1) = RAM(fill(S0, n))
+        if a.ndim == 1:
+            a = np.diag(a)                                       # RAM(S0::RealVector) = RAM(RealLowerTriangular(diagm(S0)))
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("RAM: S0 must be a square matrix, a vector (its diagonal) or a number")
+        a = np.tril(a)                                           # RealLowerTriangular(S0)
+        assert np.all(np.diag(a) > 0), "All diagonal elements of initial adaptation matrix must be positive"
+        assert 0 < targetrate < 1, "Target acceptance rate should be between 0 and 1"
+        assert 0.5 < gamma <= 1, "Exponent of stepsize must be greater than 0.5 and less or equal to 1"
+        self.S0, self.targetrate, self.gamma = a.copy(), float(targetrate), float(gamma)
+
+
 class HMC(MCSampler):
     """HMC(leapstep=0.1, nleaps=10) — HMC.jl:89-100."""
     kind = L.SAMPLER_HMC
@@ -551,6 +574,10 @@ class BasicMCJob:
                 if isinstance(self.parameter.target, LogisticTarget):
                     raise ValueError("SMMALA: SoftAbs is not applied to LogisticTarget, whose metric is positive definite by construction")
                 kw["smmala_softabs"] = sampler.transform.a
+        elif isinstance(sampler, RAM):                                                 # RAM.jl:94-111; the tuner only counts (iterate/RAM.jl:68-69)
+            if not isinstance(self.tuner, VanillaMCTuner):
+                raise NotImplementedError("RAM adapts by itself: only VanillaMCTuner (which counts proposals when verbose) is accepted")
+            kw["ram_S0"], kw["ram_targetrate"], kw["ram_gamma"] = sampler.S0, sampler.targetrate, sampler.gamma
         elif isinstance(sampler, HMC):
             kw["leapstep"], kw["nleaps"] = sampler.leapstep, sampler.nleaps
         elif isinstance(sampler, SliceSampler):

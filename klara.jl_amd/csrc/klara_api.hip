@@ -53,6 +53,8 @@ struct klara_handle {
     double* pooled_out = nullptr;   // 2*D doubles + 1 u64 scratch for pooled summaries
     double* pool_partial = nullptr; // KLARA_POOL_BLOCKS x (2 D doubles + 1 u64): stage-1 partials of the pooled summaries
     double* cdata = nullptr; KlaraJit* jit = nullptr;   // user-defined target: data block, run-time compiled kernels
+    // RAM: the chains' factors (D (D + 1) / 2 planes of nchains doubles, KParams::ram_S), the packed lower triangle of klara_desc.ram_S0 they restart from, the skipped-update counter
+    double *ram_S = nullptr, *ram_S0 = nullptr; unsigned long long* ram_skipped = nullptr;
     // streaming batch means (bm_batchlen > 0): running sum at the last batch boundary, Welford mean / M2 of the batch means
     double *bm_prev = nullptr, *bm_mean = nullptr, *bm_m2 = nullptr; long long bm_count = 0;
     KParams* d_params = nullptr;    // device copy of the handle's static kernel parameters
@@ -89,7 +91,7 @@ static klara_status validate(const klara_desc* d)
     if (!d) return KLARA_ERR_INVALID_ARG;
     if (d->struct_size != sizeof(klara_desc) || d->abi_version != KLARA_ABI_VERSION) return KLARA_ERR_INVALID_ARG;
     if (d->nchains <= 0 || d->ndims <= 0 || d->chain_offset < 0) return KLARA_ERR_INVALID_ARG;
-    if (d->sampler < KLARA_SAMPLER_MH || d->sampler > KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler < KLARA_SAMPLER_MH || (d->sampler > KLARA_SAMPLER_SMMALA && d->sampler != KLARA_SAMPLER_RAM)) return KLARA_ERR_INVALID_ARG;   // (0..4 or 6; 5 is reserved)
     if (d->target < KLARA_TARGET_GAUSS_DIAG || d->target > KLARA_TARGET_CUSTOM) return KLARA_ERR_INVALID_ARG;
     if (d->tuner < KLARA_TUNER_VANILLA || d->tuner > KLARA_TUNER_DUAL_AVERAGING) return KLARA_ERR_INVALID_ARG;
     if (d->tuner == KLARA_TUNER_DUAL_AVERAGING) {                // DualAveragingMCTuner.jl:65-70
@@ -117,6 +119,18 @@ static klara_status validate(const klara_desc* d)
     case KLARA_SAMPLER_HMC:                                      // HMC.jl:94-95
         if (!(d->leapstep > 0.0) || d->nleaps <= 0) return KLARA_ERR_INVALID_ARG;
         break;
+    case KLARA_SAMPLER_RAM:                                      // RAM.jl:100-102
+        if (!d->ram_S0) return KLARA_ERR_INVALID_ARG;
+        if (d->ndims <= 8) {                                     // (beyond: KLARA_ERR_UNSUPPORTED from the planner, whatever the factor)
+            for (int i = 0; i < d->ndims; ++i) {
+                if (!(d->ram_S0[i * d->ndims + i] > 0.0)) return KLARA_ERR_INVALID_ARG;
+                for (int j = 0; j <= i; ++j) if (!std::isfinite(d->ram_S0[i * d->ndims + j])) return KLARA_ERR_INVALID_ARG;
+            }
+        }
+        if (!(d->ram_targetrate > 0.0 && d->ram_targetrate < 1.0) || !(d->ram_gamma > 0.5 && d->ram_gamma <= 1.0)) return KLARA_ERR_INVALID_ARG;
+        // the tuner only counts proposals (iterate/RAM.jl:68-69, 107-121): VanillaMCTuner, per chain
+        if (d->tuner != KLARA_TUNER_VANILLA || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
+        break;
     default:                                                     // SliceSampler.jl:27
         if (!d->slice_widths) return KLARA_ERR_INVALID_ARG;
         for (int i = 0; i < d->ndims; ++i) if (!(d->slice_widths[i] > 0.0)) return KLARA_ERR_INVALID_ARG;
@@ -140,6 +154,7 @@ static klara_status validate(const klara_desc* d)
     if (!(d->smmala_softabs >= 0.0) || !std::isfinite(d->smmala_softabs)) return KLARA_ERR_INVALID_ARG;
     if (d->smmala_softabs > 0.0 && d->sampler != KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
     if (d->smmala_softabs > 0.0 && d->target != KLARA_TARGET_CUSTOM) return KLARA_ERR_UNSUPPORTED;
+    if (d->sampler != KLARA_SAMPLER_RAM && (d->ram_S0 != nullptr || d->ram_targetrate != 0.0 || d->ram_gamma != 0.0)) return KLARA_ERR_INVALID_ARG;
     if (d->steps_per_launch < 0 || d->tuner_score < 0 || d->tuner_score > 1) return KLARA_ERR_INVALID_ARG;   // (int32: a launch length always fits KLaunch::nsteps)
     return KLARA_OK;
 }
@@ -234,6 +249,7 @@ static bool free_all(klara_handle* h)
     ok &= dfree(h->naccept); ok &= dfree(h->sum); ok &= dfree(h->sumsq); ok &= dfree(h->held); ok &= dfree(h->hist); ok &= dfree(h->acov_S); ok &= dfree(h->acov_head); ok &= dfree(h->acov_tail); ok &= dfree(h->acov_total); ok &= dfree(h->acov_near); ok &= dfree(h->hist_lt); ok &= dfree(h->hist_g); ok &= dfree(h->hist_ll); ok &= dfree(h->hist_lp); if (!h->flag_host) ok &= dfree(h->err);
     ok &= dfree(h->vecparam); ok &= dfree(h->gw); ok &= dfree(h->gmu); ok &= dfree(h->lX); ok &= dfree(h->ly); ok &= dfree(h->hY); ok &= dfree(h->hxc);
     ok &= dfree(h->Pfrag); ok &= dfree(h->pooled_out); ok &= dfree(h->pool_partial); ok &= dfree(h->d_params); ok &= dfree(h->cdata);
+    ok &= dfree(h->ram_S); ok &= dfree(h->ram_S0); ok &= dfree(h->ram_skipped);
     ok &= dfree(h->bm_prev); ok &= dfree(h->bm_mean); ok &= dfree(h->bm_m2); ok &= dfree(h->auto_cells); ok &= dfree(h->auto_ctr); ok &= dfree(h->clock_probe);
     if (h->auto_mirror) hipHostFree(h->auto_mirror);
     if (h->flag_host) hipHostFree(h->flag_host);
@@ -406,6 +422,12 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     }
     if (desc->sampler == KLARA_SAMPLER_MH) CK(upload(&h->vecparam, desc->mh_sigma, D));
     if (desc->sampler == KLARA_SAMPLER_SLICE) CK(upload(&h->vecparam, desc->slice_widths, D));
+    if (desc->sampler == KLARA_SAMPLER_RAM) {                    // the packed lower triangle of S0, in the planes' order (ktri(j, i, D))
+        std::vector<double> tri(D * (D + 1) / 2);
+        for (size_t i = 0; i < D; ++i) for (size_t j = 0; j <= i; ++j) tri[(size_t)ktri((int)j, (int)i, (int)D)] = desc->ram_S0[i * D + j];
+        CK(upload(&h->ram_S0, tri.data(), tri.size()));
+        CKH(dalloc(&h->ram_S, tri.size() * N)); CKH(dalloc(&h->ram_skipped, 1));
+    }
     if (desc->target == KLARA_TARGET_GAUSS_DIAG) {
         if (desc->gauss_w) CK(upload(&h->gw, desc->gauss_w, D));
         if (desc->gauss_mu) CK(upload(&h->gmu, desc->gauss_mu, D));
@@ -484,7 +506,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     // the descriptor's host pointers are not retained
     h->d.mh_sigma = nullptr; h->d.slice_widths = nullptr; h->d.gauss_w = nullptr; h->d.gauss_mu = nullptr;
     h->d.gauss_prec = nullptr; h->d.logit_X = nullptr; h->d.logit_y = nullptr; h->d.hier_Y = nullptr; h->d.hier_xc = nullptr; h->d.stream = nullptr;
-    h->d.custom_src = nullptr; h->d.custom_data = nullptr;
+    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr;
     {   // static kernel parameters live in device memory (read with scalar loads at the point of use)
         const KParams hp = make_params(h);
         CKH(dalloc(&h->d_params, 1));
@@ -565,7 +587,7 @@ static KParams make_params(klara_handle* h)
     p.da_kappa = d.da_kappa; p.da_t0 = d.da_t0;
     // sampler_state(..., tuner::DualAveragingMCTuner): lambda = nleaps*leapstep, mu = log(10*step) (HMC.jl:124-133,192-213)
     p.da_lambda = (double)d.nleaps * d.leapstep; p.da_mu = kd_log(10.0 * d.leapstep);
-    p.step0 = d.sampler == KLARA_SAMPLER_MH ? 1.0 : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
+    p.step0 = (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_RAM) ? 1.0 : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
             : d.sampler == KLARA_SAMPLER_HMC ? d.leapstep : (double)NAN;
     p.sqrt_step0 = std::sqrt(p.step0); p.inv_step0 = 1.0 / p.step0;
     p.burnin = d.burnin; p.thinning = d.thinning; p.nsteps_total = d.nsteps;
@@ -576,6 +598,7 @@ static KParams make_params(klara_handle* h)
     p.cdata = (decltype(p.cdata))h->cdata; p.cndata = d.custom_ndata;
     p.clock_probe = (decltype(p.clock_probe))h->clock_probe;
     p.smmala_softabs = d.smmala_softabs;
+    p.ram_S = (decltype(p.ram_S))h->ram_S; p.ram_skipped = (decltype(p.ram_skipped))h->ram_skipped; p.ram_targetrate = d.ram_targetrate; p.ram_gamma = d.ram_gamma;
     return p;
 }
 
@@ -607,6 +630,13 @@ __global__ void k_fill_tune(double* step, long long* acc, long long* prop, long 
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { step[i] = step0; acc[i] = 0; prop[i] = 0; tot[i] = period; }
+}
+
+// RAM: every chain's factor restarts from S0 (RAM.jl:155-162, 201-211): plane k of the factors <- entry k of the packed triangle
+__global__ void k_fill_ram(double* S, const double* tri, long long n, int nplanes)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) for (int k = 0; k < nplanes; ++k) S[(long long)k * n + i] = tri[k];
 }
 
 __global__ void k_fill2(double* a, double* b, long long n, double va, double vb)
@@ -670,7 +700,7 @@ static klara_status init_common(klara_handle* h)
     }
     h->acov_n = 0;
     // tuner_state: samplers.jl:29-45 — step per sampler, accepted = proposed = 0, totproposed = period
-    const double step0 = d.sampler == KLARA_SAMPLER_MH ? 1.0
+    const double step0 = (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_RAM) ? 1.0
                        : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
                        : d.sampler == KLARA_SAMPLER_HMC ? d.leapstep : (double)NAN;
     hipLaunchKernelGGL(k_fill_tune, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, st, h->tune_step,
@@ -680,6 +710,11 @@ static klara_status init_common(klara_handle* h)
         hipLaunchKernelGGL(k_fill2, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, st, h->da_epsbar, h->da_hbar, NT,
                            d.da_eps0bar, d.da_h0bar);
         HIPCHK(hipGetLastError());
+    }
+    if (h->ram_S) {
+        hipLaunchKernelGGL(k_fill_ram, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->ram_S, h->ram_S0, (long long)N, (int)(D * (D + 1) / 2));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(h->ram_skipped, 0, sizeof(unsigned long long), st));
     }
     const int needgrad = d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_HMC || d.sampler == KLARA_SAMPLER_SMMALA;
     KParams p = make_params(h);
@@ -904,6 +939,7 @@ static hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
     case KLARA_SAMPLER_MALA: return klara_launch_mala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     case KLARA_SAMPLER_HMC: return klara_launch_hmc(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    case KLARA_SAMPLER_RAM: return klara_launch_ram(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     default: return klara_launch_slice(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     }
 }
@@ -2088,6 +2124,45 @@ extern "C" klara_status klara_get_dual_averaging(klara_handle* h, double* epsbar
     return KLARA_OK;
 }
 
+extern "C" klara_status klara_get_ram_factor(klara_handle* h, double* S, int64_t* skipped)
+{
+    if (!h || h->d.sampler != KLARA_SAMPLER_RAM) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims, NP = D * (D + 1) / 2;
+    if (S) {
+        std::vector<double> planes(NP * N);
+        HIPCHK(hipMemcpy(planes.data(), h->ram_S, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < N; ++c)
+            for (size_t i = 0; i < D; ++i)
+                for (size_t j = 0; j < D; ++j) S[(c * D + i) * D + j] = j <= i ? planes[(size_t)ktri((int)j, (int)i, (int)D) * N + c] : 0.0;
+    }
+    if (skipped) {
+        unsigned long long k = 0;
+        HIPCHK(hipMemcpy(&k, h->ram_skipped, sizeof(k), hipMemcpyDeviceToHost));
+        *skipped = (int64_t)k;
+    }
+    return KLARA_OK;
+}
+
+extern "C" klara_status klara_set_ram_factor(klara_handle* h, const double* S)
+{
+    if (!h || !S || h->d.sampler != KLARA_SAMPLER_RAM) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims, NP = D * (D + 1) / 2;
+    std::vector<double> planes(NP * N);
+    for (size_t c = 0; c < N; ++c)
+        for (size_t i = 0; i < D; ++i) {
+            if (!(S[(c * D + i) * D + i] > 0.0) || !std::isfinite(S[(c * D + i) * D + i])) return KLARA_ERR_INVALID_ARG;
+            for (size_t j = 0; j <= i; ++j) planes[(size_t)ktri((int)j, (int)i, (int)D) * N + c] = S[(c * D + i) * D + j];
+        }
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(h->ram_S, planes.data(), planes.size() * sizeof(double), hipMemcpyHostToDevice));
+    return KLARA_OK;
+}
+
 extern "C" klara_status klara_device_ptrs(klara_handle* h, void** x, void** logtarget, void** gradlogtarget)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;
@@ -2379,7 +2454,7 @@ extern "C" klara_status klara_selftest_mfma_f64_4x4x4(int32_t device, const doub
 
 extern "C" klara_status klara_check_custom_target(const char* src, int32_t sampler, int32_t ndims)
 {
-    if (!src || sampler < KLARA_SAMPLER_MH || sampler > KLARA_SAMPLER_SMMALA || ndims <= 0) return KLARA_ERR_INVALID_ARG;
+    if (!src || sampler < KLARA_SAMPLER_MH || (sampler > KLARA_SAMPLER_SMMALA && sampler != KLARA_SAMPLER_RAM) || ndims <= 0) return KLARA_ERR_INVALID_ARG;   // (0..4 or 6)
     // the plain fused instantiation of the layout klara_create plans for a job of this target (one chain; zeros: VanillaMCTuner per chain, no monitor)
     klara_desc d;
     memset(&d, 0, sizeof(d));

@@ -78,6 +78,10 @@ __host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { re
 #else
 #define KLARA_SMMALA_SOFTABS_E4_ONE_WAVE 0
 #endif
+// RAM kernels, wavefronts per SIMD asked of the compiler (the reasoning is at k_transitions' launch bounds)
+#ifndef KLARA_RAM_WAVES
+#define KLARA_RAM_WAVES(E, MODE) ((E) == 8 ? 1 : 2)
+#endif
 #define KLARA_SLICE_ATT_BITS 14
 #define KLARA_SLICE_MAX_ATT ((1 << KLARA_SLICE_ATT_BITS) - 1)
 #define KLARA_INIT_TRANSITION ((((uint64_t)1) << 40) - 1)
@@ -144,6 +148,9 @@ struct KParams {
     // (s_memtime, s_memrealtime) when it starts [2], [3] and when it ends [0], [1] — stores only, nothing kept in registers
     gulong* clock_probe;
     double smmala_softabs;                     // SMMALA: the a of softabs(G, a) applied to every metric (klara_softabs.h), 0 = no transform
+    // RAM: the chains' factors, D (D + 1) / 2 planes of nchains doubles (entry S_ij, i >= j, of chain c at [ktri(j, i, D) * nchains + c]: a wavefront's
+    // loads and stores of one entry are contiguous); the handle's counter of skipped updates; RAM.targetrate, RAM.γ
+    gdouble* ram_S; gulong* ram_skipped; double ram_targetrate; double ram_gamma;
 };
 
 // Per-launch values, passed by value.  Everything else (KParams) is static for a handle and lives in device memory:
@@ -1101,6 +1108,124 @@ KLARA_PRAGMA_UNROLL_E
     return acc;
 }
 
+// ---- RAM (src/samplers/RAM.jl, iterate/RAM.jl:65-130, after Vihola 2012): the random walk x' = x + S z whose factor S the chain adapts ----
+// S is the chain's E x E lower factor in the lane's registers, packed like SmmalaRegs::L (S_ij, i >= j, at ktri(j, i, E)); the padding i >= D holds the
+// identity block and z is zero there, so every padded term below is an exact zero and the padded block of the new factor is the identity again,
+// bit for bit (tests/ram_ref.c runs the same loops).  It travels between launches in KParams::ram_S.
+template <int E>
+struct RamRegs {
+    static constexpr int NT = E * (E + 1) / 2;
+    double S[NT];
+    unsigned long long skipped;      // updates of this launch that were skipped
+};
+template <int E>
+__device__ __forceinline__ void ram_load(const KParams& p, const LaneCtx<E>& cx, RamRegs<E>& r)
+{
+    const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's factor and store nothing)
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j; i < E; ++i) {
+            double v = i == j ? 1.0 : 0.0;
+            if (i < p.D) v = p.ram_S[(long long)ktri(j, i, p.D) * p.nchains + c0];
+            r.S[ktri(j, i, E)] = v;
+        }
+    }
+    r.skipped = 0;
+}
+template <int E>
+__device__ __forceinline__ void ram_store(const KParams& p, const LaneCtx<E>& cx, const RamRegs<E>& r)
+{
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j; i < E; ++i)
+            if (i < p.D) p.ram_S[(long long)ktri(j, i, p.D) * p.nchains + cx.chain] = r.S[ktri(j, i, E)];
+    }
+    if (r.skipped != 0) atomicAdd((unsigned long long*)p.ram_skipped, r.skipped);
+}
+// iterate/RAM.jl:123-129: S <- chol(S (I + c z z') S')' with c = eta (min(1, exp(ratio)) - targetrate) / (z . z), formed as S S' + c w w' with w = S z
+// (R2) and factored by smmala_factor's loop nest (R4); false — and S as it was — where z . z or a pivot is not a finite positive number
+template <int E>
+__device__ __forceinline__ bool ram_update(const KParams& p, unsigned long long t, double ratio, double zz, const double (&w)[E], double (&S)[RamRegs<E>::NT])
+{
+    double eta = (double)p.D * kd_exp(-p.ram_gamma * kd_log((double)(t + 1ull)));            // :123 (R3: count^-gamma as da_update forms it)
+    eta = eta < 1.0 ? eta : 1.0;
+    const double ap = ratio >= 0.0 ? 1.0 : (kfinite(ratio) ? kd_exp(ratio) : 0.0);          // min(1, exp(ratio)); -inf / NaN: 0 (R3)
+    const double c = eta * (ap - p.ram_targetrate) / zz;                                    // :124-127
+    bool ok = zz > 0.0 && kfinite(zz);
+    double A[RamRegs<E>::NT];
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j; i < E; ++i) {
+            double a = S[ktri(0, i, E)] * S[ktri(0, j, E)];
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 1; k <= j; ++k) a = a + S[ktri(k, i, E)] * S[ktri(k, j, E)];
+            A[ktri(j, i, E)] = a + (c * w[i]) * w[j];                                       // :128
+        }
+    }
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {                                                           // :129, in place: A becomes the new factor
+        double sj = A[ktri(j, j, E)];
+KLARA_PRAGMA_UNROLL_E
+        for (int k = 0; k < j; ++k) sj = sj - A[ktri(k, j, E)] * A[ktri(k, j, E)];
+        const bool okj = sj > 0.0 && kfinite(sj);
+        ok = ok && okj;
+        const double ljj = __builtin_sqrt(okj ? sj : 1.0);
+        const double rj = 1.0 / ljj;
+        A[ktri(j, j, E)] = ljj;
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j + 1; i < E; ++i) {
+            double a = A[ktri(j, i, E)];
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 0; k < j; ++k) a = a - A[ktri(k, i, E)] * A[ktri(k, j, E)];
+            A[ktri(j, i, E)] = a * rj;
+        }
+    }
+KLARA_PRAGMA_UNROLL_E
+    for (int k = 0; k < RamRegs<E>::NT; ++k) S[k] = ok ? A[k] : S[k];
+    return ok;
+}
+// iterate!(job, RAM, Multivariate) — iterate/RAM.jl:65-130: MH's step with the proposal x + S z, then the update of S, accepted or not
+template <class T, int E, bool COMMIT = true>
+__device__ __forceinline__ bool step_ram(const KParams& p, const T& tg, const LaneCtx<E>& cx,
+                                         unsigned long long gchain, unsigned long long t,
+                                         const double (&z)[E], const AccDraw& ad, RamRegs<E>& rs,
+                                         double (&x)[E], double& lt, Proposal<E>& prop)
+{
+    double w[E], xp[E], gd[E], red[1];
+    double zz = 0.0;
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) zz = zz + z[e] * z[e];
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {                                                           // R1: w = S z, k ascending
+        double a = rs.S[ktri(0, i, E)] * z[0];
+KLARA_PRAGMA_UNROLL_E
+        for (int k = 1; k <= i; ++k) a = a + rs.S[ktri(k, i, E)] * z[k];
+        w[i] = a;
+    }
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) xp[e] = x[e] + w[e];                                        // :73
+    tg.template eval<true, false>(cx, xp, red[0], gd);                                      // :75
+    group_allreduce<1>(red, cx.G, cx.lane);
+    const double ltp = tg.finalize(red[0]);
+    const double ratio = ltp - lt;                                                          // :77
+    bool acc = ratio > 0.0;                                                                 // :79
+    acc = accept_log_test<E>(p, cx, gchain, t, ad, acc, ratio);
+    if (!COMMIT) {
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) prop.x[e] = xp[e];
+        prop.lt = ltp;
+    } else if (acc) {                                                                       // :80-82
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) x[e] = xp[e];
+        lt = ltp;
+    }
+    if (!ram_update<E>(p, t, ratio, zz, w, rs.S)) rs.skipped += 1;                           // :123-129
+    return acc;
+}
+
 // iterate!(job, HMC, Multivariate) — iterate/HMC.jl:124-201; leapfrog! samplers.jl:122-134;
 // hamiltonian samplers.jl:103
 template <class T, int E, bool PLAIN, bool COMMIT = true>
@@ -1429,7 +1554,13 @@ template <int SAMPLER, int TARGET, int E, int GT, int MODE>
 // (MALA and HMC on the logistic target at E = 4 — cfg 4 — ask for 4 wavefronts per SIMD: its row loop is a chain of exp / log / division latencies that two
 //  wavefronts cannot cover; the 128-register budget spills 156-272 B outside the row loop and still measured 1.01e9 against 8.1e8
 //  transitions/s with running sums, 1.05e9 against 9.4e8 without, same box)
-__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
+// (RAM: the factor S, E (E + 1) / 2 doubles, is live through the whole transition — the target's row loop included — and a second triangle while
+//  S S' + c w w' is formed and factored in place: 2 E (E + 1) registers before x, x', z and w — 144 at E = 8.  From the compiler's resource report on the
+//  logistic target: E = 2 takes 168-215 registers and E = 4 205-253 — two wavefronts per SIMD without scratch (asked for three they spill 32-160 B and
+//  116-304 B); E = 8 takes 256 + 52-80 accumulation registers at one wavefront per SIMD without scratch, and spills 136-304 B at two.  So 2, 2, 1: no RAM
+//  kernel uses scratch; DESIGN.md section 2 and profiles/ram.txt have the table)
+__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_RAM ? KLARA_RAM_WAVES(E, MODE) :
+                                   SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
                                                                                                   metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2; with the
                                                                                                   softabs transform's eigenvectors: 20-120 B in every mode) */ :
                                    TARGET == KLARA_TARGET_CUSTOM && GT > 1 ? 2 /* staged closures: two workgroups' rows fit a CU's LDS */ :
@@ -1536,6 +1667,10 @@ KLARA_PRAGMA_UNROLL_E
         // positive-definite metric (checked at the start state by k_init_smmala)
         SmmalaRegs<E> sms;
         if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA) smmala_state_at<T, E>(p, tg, cx, cur.x, cur.g, sms);
+        // RAM: the group's factors come from memory with the group and go back at the end of the launch, so a launch continues where the
+        // last one stopped whatever its length
+        RamRegs<SAMPLER == KLARA_SAMPLER_RAM ? E : 2> rms;
+        if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_load<E>(p, cx, rms);
 
         TuneRegs tn;
         if (per_chain_tune) tn = { cur.step, cur.accepted, cur.proposed, cur.totproposed, 0, 0.0, 0.0 };
@@ -1556,6 +1691,7 @@ KLARA_PRAGMA_UNROLL_E
             bool acc;
             if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA)
                 acc = step_smmala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, sms, prop);
+            else if constexpr (SAMPLER == KLARA_SAMPLER_RAM) acc = step_ram<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, rms, cur.x, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_MH) acc = step_mh<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_MALA) acc = step_mala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_HMC) {
@@ -1629,6 +1765,7 @@ KLARA_PRAGMA_UNROLL_E
             }
         }
         if (cx.chain_ok && cx.q == 0 && cx.rq == 0) {
+            if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_store<E>(p, cx, rms);
             if (do_sum) p.held[cx.chain] = held;
             if (nacc != 0) { p.LT[cx.chain] = cur.lt; p.naccept[cx.chain] += nacc; }
             if (da) { p.tune_step[cx.chain] = tn.step; p.da_epsbar[cx.chain] = tn.epsbar; p.da_hbar[cx.chain] = tn.hbar; }

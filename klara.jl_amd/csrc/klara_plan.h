@@ -65,7 +65,7 @@ struct KlaraPlan {
 
 static int cnt_predicate(const klara_desc& d)
 {
-    if (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_SLICE) return d.verbose != 0;
+    if (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_SLICE || d.sampler == KLARA_SAMPLER_RAM) return d.verbose != 0;   // (iterate/RAM.jl:68: tuner.verbose)
     return (d.tuner == KLARA_TUNER_VANILLA && d.verbose) || d.tuner == KLARA_TUNER_ACCEPT_RATE ||
            (d.tuner == KLARA_TUNER_DUAL_AVERAGING && d.verbose);
 }
@@ -208,6 +208,15 @@ static bool smmala_eligible(const klara_desc& d, const KlaraOverrides& o)
     return d.ndims <= 8 && d.target == KLARA_TARGET_CUSTOM && d.custom_src != nullptr && !pair_source(d.custom_src) && !custom_lik_prior(d.custom_src);
 }
 
+// RAM (KLARA_SAMPLER_RAM), D <= 8 on the group layout (E = 2 / 4 / 8), one chain per lane: the logistic target (kinds 0 / 2, never the matrix cores) and a
+// user-defined target as a whole-vector closure (plain or likelihood + prior form; pair closures are not taken).  No gradient is evaluated.
+static bool ram_eligible(const klara_desc& d, const KlaraOverrides& o)
+{
+    if (d.ndims > 8) return false;
+    if (d.target == KLARA_TARGET_LOGISTIC) return !logit_mfma_eligible(d, o);
+    return d.target == KLARA_TARGET_CUSTOM && d.custom_src != nullptr && strstr(d.custom_src, "KLARA_USER_PAIR_TARGET") == nullptr;
+}
+
 // kind, G, E (and a staged closure's wavefronts per workgroup) of the job as it runs (a closure-form rewrite has made it a user-defined target)
 static klara_status select_layout(const klara_desc& d, const KlaraOverrides& o, KlaraPlan& p)
 {
@@ -283,6 +292,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     p.steps_per_launch = d.steps_per_launch > 0 ? d.steps_per_launch : p.slice_free ? KLARA_DEFAULT_STEPS_PER_LAUNCH_SLICE : KLARA_DEFAULT_STEPS_PER_LAUNCH;
 
     if (d.sampler == KLARA_SAMPLER_SMMALA && !smmala_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
+    if (d.sampler == KLARA_SAMPLER_RAM && !ram_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
     if (custom_autodiff(d) > 0 && d.custom_src != nullptr && strstr(d.custom_src, "KLARA_USER_PAIR_TARGET") != nullptr) return KLARA_ERR_UNSUPPORTED;
     if (d.target == KLARA_TARGET_LOGISTIC && !logit_mfma_eligible(d, o) && logit_beyond_rowsplit(d)) p.rewrite = KLARA_REWRITE_LOGIT_WIDE;
     else if (pair_as_whole(d, o)) p.rewrite = KLARA_REWRITE_PAIR_AS_WHOLE;
@@ -298,6 +308,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     if (st != KLARA_OK) return st;
     if (d.tuner_mode == KLARA_TUNE_POOLED && d.sampler == KLARA_SAMPLER_SLICE) return KLARA_ERR_UNSUPPORTED;
     if (d.sampler == KLARA_SAMPLER_SMMALA && p.G != 1) return KLARA_ERR_UNSUPPORTED;     // (one chain per lane: KLARA_CUSTOM_LANES may ask for more)
+    if (d.sampler == KLARA_SAMPLER_RAM && (p.G != 1 || p.kind == 5)) return KLARA_ERR_UNSUPPORTED;
     // the logistic kernels keep the data rows (padded to E columns, + the responses) in LDS next to the 8 KB of math tables: up to
     // 144 KB of the CU's 160 (swiss: 200 x 5 doubles = 8 KB); beyond the 56 KB a launch gets by default the launchers raise the
     // kernel's limit, and fewer workgroups share a CU

@@ -1,0 +1,14 @@
+// klara_ram.hip — instantiates the RAM transition kernels (group layout, logistic target, D <= 8) for gfx950.  The start state is k_init's (the log-target,
+// as for MH); a user-defined target gets the same kernels from the run-time compiler (klara_jit.hip).
+#include "klara_launch.h"
+
+hipError_t klara_launch_ram(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
+{
+    const dim3 blk(256);
+    if (target != KLARA_TARGET_LOGISTIC || G != 1) return hipErrorInvalidValue;
+    if (E == 2) KLARA_LAUNCH_T(KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, 2, 0);
+    else if (E == 4) KLARA_LAUNCH_T(KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, 4, 0);
+    else if (E == 8) KLARA_LAUNCH_T(KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, 8, 0);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}

@@ -258,7 +258,8 @@ class Engine:
                  da_t0: int = 10, da_kappa: float = 0.75,
                  seed: int = 20260927, chain_offset: int = 0, device: int = 0, monitor: int = 0,
                  steps_per_launch: int = 0, stream: int = 0, nstreams: int = 0, bm_batchlen: int = 0, hist_ring_cols: int = 0,
-                 acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0):
+                 acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0,
+                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0):
         self._lib = L.load()
         self.target = target
         self.ndims = int(target.ndims)
@@ -316,6 +317,14 @@ class Engine:
         if float(smmala_softabs) > 0.0 and isinstance(target, LogisticTarget):
             raise ValueError("softabs is not applied to the logistic target's metric: X' diag(r (1 - r)) X + I / lambda is positive definite by construction")
         d.smmala_softabs = float(smmala_softabs)
+        # RAM(S0; targetrate, gamma): the initial factor (D x D, its lower triangle is read; a vector is its diagonal), RAM.jl:94-111
+        if ram_S0 is not None:
+            a = _f64(ram_S0)
+            a = _f64(np.diag(a.ravel())) if a.ndim < 2 else a
+            if a.shape != (self.ndims, self.ndims):
+                raise ValueError(f"ram_S0 must be {self.ndims} x {self.ndims} (or its diagonal), not {a.shape}")
+            keep.append(a); d.ram_S0 = _ptr(a)
+        d.ram_targetrate, d.ram_gamma = float(ram_targetrate), float(ram_gamma)
         d.stream = C.c_void_p(int(stream)) if stream else None
         self._h = C.c_void_p()
         L.check(self._lib.klara_create(C.byref(d), C.byref(self._h)), "klara_create")
@@ -527,6 +536,20 @@ class Engine:
         p = np.empty(self.nchains, dtype=np.int64); t = np.empty(self.nchains, dtype=np.int64)
         L.check(self._lib.klara_get_tune(self._h, step.ctypes.data, a.ctypes.data, p.ctypes.data, t.ctypes.data), "klara_get_tune")
         return step, a, p, t
+
+    def ram_factor(self):
+        """(S (nchains, ndims, ndims) lower triangular, skipped): the RAM sampler's current factor of every chain and the number of factor
+        updates skipped since set_state / reset (klara_get_ram_factor; 0 in exact arithmetic)."""
+        S = np.empty((self.nchains, self.ndims, self.ndims)); k = C.c_int64(0)
+        L.check(self._lib.klara_get_ram_factor(self._h, S.ctypes.data, C.byref(k)), "klara_get_ram_factor")
+        return S, int(k.value)
+
+    def set_ram_factor(self, S):
+        """per-chain factors for a warm start of the RAM sampler: (nchains, ndims, ndims), or one ndims x ndims factor for every chain; the
+        lower triangles are read (klara_set_ram_factor)"""
+        S = _f64(S)
+        S = _f64(np.broadcast_to(S, (self.nchains, self.ndims, self.ndims)))
+        L.check(self._lib.klara_set_ram_factor(self._h, S.ctypes.data), "klara_set_ram_factor")
 
     def dual_averaging(self):
         eb = np.empty(self.nchains); hb = np.empty(self.nchains)
