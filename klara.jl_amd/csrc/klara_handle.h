@@ -1,0 +1,120 @@
+// klara_handle.h — internal, host only: the handle behind the C ABI, the owner of its device arrays, and the functions the host translation
+// units share (klara_devmem / klara_create / klara_run / klara_monitors / klara_comm / klara_zv_api / klara_selftest .hip).
+// The ABI and the reference lines each entry point replaces are documented in include/klara_hip.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include "klara_plan.h"
+
+#define HIPCHK(expr)                                                                   \
+    do {                                                                               \
+        hipError_t e__ = (expr);                                                       \
+        if (e__ != hipSuccess) return (e__ == hipErrorOutOfMemory) ? KLARA_ERR_NOMEM : KLARA_ERR_HIP; \
+    } while (0)
+#define KCHK(expr) do { const klara_status s__ = (expr); if (s__ != KLARA_OK) return s__; } while (0)
+
+#pragma GCC visibility push(hidden)     // (shared between the library's own translation units, not exported)
+
+// ---- klara_devmem.hip: device allocations, between canaries under KLARA_DEBUG_CANARY=1
+hipError_t dalloc_bytes(void** p, size_t bytes);
+bool dfree(void* p);                    // false when the array's canaries were found damaged (always true without KLARA_DEBUG_CANARY)
+template <class T>
+static hipError_t dalloc(T** p, size_t n) { return dalloc_bytes((void**)p, n * sizeof(T)); }
+
+// The device arrays of one handle, or of one call's workspace: what alloc() hands out, release() frees — and checks: an array that is not
+// in this list would neither be freed nor have its canaries looked at.
+struct DeviceArrays {
+    std::vector<void*> owned;
+    template <class T>
+    hipError_t alloc(T** p, size_t n)
+    {
+        const hipError_t e = dalloc(p, n);
+        if (e == hipSuccess) owned.push_back(*p);
+        return e;
+    }
+    bool release()                      // false: a kernel wrote outside one of the arrays (KLARA_DEBUG_CANARY=1)
+    {
+        bool ok = true;
+        for (void* p : owned) ok &= dfree(p);
+        owned.clear();
+        return ok;
+    }
+};
+
+struct klara_handle {
+    klara_desc d;
+    KlaraPlan plan;            // layout, kernels, grids and LDS of the job, planned once by klara_create (klara_plan.h)
+    DeviceArrays mem;          // owns every device array below; the typed pointers are what the kernels' parameter block is filled from
+    double *X = nullptr, *GR = nullptr, *LT = nullptr;
+    double* tune_step = nullptr;
+    long long *tune_acc = nullptr, *tune_prop = nullptr, *tune_tot = nullptr;
+    double *da_epsbar = nullptr, *da_hbar = nullptr;
+    unsigned long long* pooled_acc = nullptr;
+    uint8_t* accept = nullptr; long long accept_cap = 0;
+    unsigned long long* naccept = nullptr;
+    double *sum = nullptr, *sumsq = nullptr;
+    long long* held = nullptr;      // running sums in sojourn form: saved steps at the current state not yet in sum / sumsq (KParams::held)
+    double* hist = nullptr; long long hist_cols = 0;     // hist_cols: columns of the history buffers (= ring when > 0 and ring is set)
+    bool ring = false;                                   // the history buffers hold the last hist_cols saved steps only
+    // streaming autocovariances (acov_maxlag > 0): W = maxlag + 1 lags; [k][series] layouts
+    int acov_W = 0; double *acov_S = nullptr, *acov_head = nullptr, *acov_tail = nullptr, *acov_total = nullptr, *acov_near = nullptr; long long acov_n = 0;
+    double *hist_lt = nullptr, *hist_g = nullptr, *hist_ll = nullptr, *hist_lp = nullptr;
+    unsigned long long* clock_probe = nullptr;        // pair-transposed kernels: (s_memtime, s_memrealtime) at the end / start of one workgroup of the last launch
+    bool pair_enqueued = false;                       // a launch of this handle has enqueued both kernel families (their one-time scratch set-up is behind us)
+    int* err = nullptr; int* flag_host = nullptr;     // error flag as the kernels address it; the same word as the host reads it (null: err is device memory)
+    double *vecparam = nullptr, *gw = nullptr, *gmu = nullptr, *lX = nullptr, *ly = nullptr, *Pfrag = nullptr,
+           *hY = nullptr, *hxc = nullptr;
+    double* pooled_out = nullptr;   // 2*D doubles + 1 u64 scratch for pooled summaries
+    double* pool_partial = nullptr; // KLARA_POOL_BLOCKS x (2 D doubles + 1 u64): stage-1 partials of the pooled summaries
+    double* cdata = nullptr; KlaraJit* jit = nullptr;   // user-defined target: data block, run-time compiled kernels
+    // RAM: the chains' factors (D (D + 1) / 2 planes of nchains doubles, KParams::ram_S), the packed lower triangle of klara_desc.ram_S0 they restart from, the skipped-update counter
+    double *ram_S = nullptr, *ram_S0 = nullptr; unsigned long long* ram_skipped = nullptr;
+    // streaming batch means (bm_batchlen > 0): running sum at the last batch boundary, Welford mean / M2 of the batch means
+    double *bm_prev = nullptr, *bm_mean = nullptr, *bm_m2 = nullptr; long long bm_count = 0;
+    KParams* d_params = nullptr;    // device copy of the handle's static kernel parameters
+    double lpconst = 0.0;
+    bool dense_mu = false;          // dense target with a mean: Pfrag carries mu behind the matrix fragments
+    int logit_nblocks = 0;          // layout kind 5 (klara_logit_mfma.h): row blocks of the fragment stream in Pfrag; ly holds the zero-padded responses
+    // run state
+    bool have_state = false;
+    unsigned long long epoch = 0;   // klara_reset calls so far: the Philox key of the job is seed + epoch * KLARA_EPOCH_KEY_STRIDE
+    long long steps_done = 0;       // transitions since set_state/reset (= global transition index)
+    long long nsaved = 0;           // postrange steps passed so far
+    // host mirror of the pooled tuner counters (decides where launches must end)
+    long long m_prop = 0, m_tot = 0;
+    hipStream_t stream = nullptr; bool own_stream = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; long long last_launches = 0; bool timed = false;
+    // layout kind 3: the chain groups are cut into plan.nparts contiguous partitions, partition j > 0 runs on its own
+    // internal stream.  Chains are independent, so partition j's transition t+1 only follows its own transition t; the
+    // streams drift apart and one partition's kernel fills the SIMDs while the other's drains / ramps up.
+    hipStream_t side[3] = { nullptr, nullptr, nullptr }; hipEvent_t fork_ev = nullptr, join_ev[3] = { nullptr, nullptr, nullptr };
+    // layout kind 3, untuned MH / MALA with 17 <= D <= 104: the 4-lanes-per-chain kernels are available as well (plan.np4 pairs per lane).
+    // They sum in the 8-lane order, so which of the two kernel families runs a launch changes no bit; with running sums on, the
+    // choice is taken on the device launch by launch (KAuto, klara_diagt.h): auto_cells = [partition][launch parity] decision,
+    // auto_ctr = [partition] launch counter, auto_mirror = host-visible {mode, accepted} per partition (may be null).
+    int* auto_cells = nullptr; unsigned long long* auto_ctr = nullptr; int* auto_mirror = nullptr; int* auto_mirror_dev = nullptr;
+    long long launch_idx = 0;
+    int query_lanes = 4;            // klara_get_kernel_attributes: which of the two kernel families to report
+    long long n_launch_mode[3] = { 0, 0, 0 };   // launches issued as: forced / single 4-lane, forced / single 8-lane, device-decided pair
+};
+
+// ---- klara_create.hip
+klara_status validate(const klara_desc* d);                 // every check a descriptor can fail without a device
+std::string pair_as_whole_source(const char* src);
+KParams make_params(klara_handle* h);
+
+// ---- klara_run.hip
+void part_range(const klara_handle* h, int nparts, int j, long long* c0, long long* c1);
+hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts);
+
+// ---- klara_monitors.hip: what klara_run_async enqueues behind a launch, and the pooled sums the gather calls reduce over the ranks
+hipError_t launch_bm_close(klara_handle* h, int nparts);
+hipError_t launch_acov_update(klara_handle* h, long long col0, long long m);
+hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);
+hipError_t pool_moments_async(klara_handle* h, double* out);
+
+#pragma GCC visibility pop

@@ -22,7 +22,7 @@
 #include <new>
 #include <string>
 #include <vector>
-#include "klara_launch.h"
+#include "klara_plan.h"
 #include "klara_jit_headers.inc"
 
 namespace {
@@ -236,7 +236,7 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
         }
     }
     // (MH, the slice sampler and RAM evaluate no gradient: k_transitions<KLARA_SAMPLER_RAM, ...> and k_init are instantiated by the names below like MH's)
-    const bool needgrad = sampler == KLARA_SAMPLER_MALA || sampler == KLARA_SAMPLER_HMC || sampler == KLARA_SAMPLER_SMMALA;
+    const bool needgrad = sampler_needs_gradient(sampler);
     // SMMALA: the metric is the user's klara_user_tensorlogtarget (klara_custom.h); a source without it cannot run the sampler
     // forward-mode autodiff (klara_autodiff.h): the marker's value; the generic function it promises has to be there
     const int ad = pf ? 0 : klara_autodiff_order(src);

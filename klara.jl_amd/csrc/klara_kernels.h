@@ -4,7 +4,7 @@
 // E contiguous elements per lane (element i lives on lane i / E of its group); a 64-lane wavefront
 // carries 64 / G chains.  D = 100 -> E = 4, G = 32: two chains per wavefront, lanes 0..24 of each half hold
 // (4q..4q+3), so two Philox4x32-10 blocks per lane yield exactly that lane's four proposal normals (E = 2, G = 64 is
-// the one-chain-per-wavefront variant; klara_api.hip select_layout picks E).
+// the one-chain-per-wavefront variant; klara_plan.h: select_layout picks E).
 // D = 4 (swiss logistic regression) -> E = 4, G = 1: one chain per lane, no cross-lane traffic at all.
 // State matrices are (nchains x D) row-major in HBM: a wavefront reads/writes contiguous rows.
 //
@@ -102,7 +102,7 @@ typedef KGLOBAL uint8_t guchar;
 typedef KGLOBAL int gint;
 
 // A device-detected error (non-finite start, slice sampler stuck).  The flag is a word of host memory mapped into the device's address
-// space (klara_api.hip), so that klara_synchronize reads it without a copy command; a plain store is all a PCIe write offers (no fetch-max), and
+// space (klara_create.hip): klara_synchronize then reads it without a copy command; a plain store is all a PCIe write offers (no fetch-max), and
 // the two conditions cannot meet in one launch (the first is raised by the initialisation kernels, the second by transitions).
 __device__ __forceinline__ void klara_raise(gint* flag, int code) { __hip_atomic_store((int*)flag, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 

@@ -6,7 +6,7 @@
 #include "klara_diagt.h"
 
 // Every transition kernel is launched through klara_go: when klara_attr_query points at a hipFuncAttributes (klara_get_kernel_attributes,
-// klara_api.hip) the launcher reports the kernel's registers / scratch / LDS instead of launching it — the dispatch code that
+// klara_monitors.hip) the launcher reports the kernel's registers / scratch / LDS instead of launching it — the dispatch code that
 // picks an instantiation for a job is then the one source of truth for "which kernel does this handle run".
 extern thread_local hipFuncAttributes* klara_attr_query;
 template <class... KArgs, class... Args>
@@ -58,7 +58,7 @@ hipError_t klara_launch_mfma_probe(const double* A, const double* B, const doubl
 hipError_t klara_launch_mfma4_probe(const double* A, const double* B, const double* C, double* D, hipStream_t st);
 
 // logistic regression beyond 16 parameters on the matrix cores (layout kind 5, klara_logit_mfma.h); NE in {8, 16, 24, 32}; F: the fragment stream of both
-// passes in the order of consumption, ypad: the responses zero-padded to the blocks' rows (klara_api.hip logit_mfma_stream)
+// passes in the order of consumption, ypad: the responses zero-padded to the blocks' rows (klara_create.hip pack_logit_stream)
 hipError_t klara_launch_logit_mfma(const KParams* p, const KLaunch& kl, int sampler, bool da, int NE, const double* F, const double* ypad, int nblocks,
                                    dim3 grid, hipStream_t st);
 hipError_t klara_launch_logit_mfma_init(const KParams& p, int NE, const double* F, const double* ypad, int nblocks, int needgrad, dim3 grid, hipStream_t st);

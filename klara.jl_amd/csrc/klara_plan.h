@@ -2,6 +2,7 @@
 // handle keeps the plan; klara_check_custom_target and klara_selftest_plan plan through the same function.  No device calls, no globals.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include "klara_launch.h"
 
@@ -70,7 +71,17 @@ static int cnt_predicate(const klara_desc& d)
            (d.tuner == KLARA_TUNER_DUAL_AVERAGING && d.verbose);
 }
 
-static int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+// per-sampler facts: the ids the library serves (0..4 and 6; 5 is reserved), which samplers carry a gradient, and the tuner's first step
+// (tuner_state, samplers.jl:29-45: the slice sampler has none)
+static bool sampler_valid(int s) { return (s >= KLARA_SAMPLER_MH && s <= KLARA_SAMPLER_SMMALA) || s == KLARA_SAMPLER_RAM; }
+static bool sampler_needs_gradient(int s) { return s == KLARA_SAMPLER_MALA || s == KLARA_SAMPLER_HMC || s == KLARA_SAMPLER_SMMALA; }
+static double sampler_step0(const klara_desc& d)
+{
+    return (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_RAM) ? 1.0 : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
+         : d.sampler == KLARA_SAMPLER_HMC ? d.leapstep : (double)NAN;
+}
+
+static int pow2ceil(int v){ int p = 1; while (p < v) p <<= 1; return p; }
 
 // lanes per chain of the pair-transposed layout (8 to D = 128, then 16, 32, 64)
 static int diagt_lanes(int D) { return D <= 128 ? 8 : (D <= 256 ? 16 : (D <= 512 ? 32 : 64)); }

@@ -1,0 +1,213 @@
+// klara_selftest.hip — self tests: the device's random blocks, math, normals and matrix-core probes as the kernels see them; compile checks of user targets.
+#include <rocrand/rocrand_kernel.h>
+#include "klara_handle.h"
+
+__global__ void k_rocrand_blocks(unsigned long long seed, unsigned long long subseq,
+                                 unsigned long long first_block, int nblocks, unsigned int* out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nblocks) return;
+    rocrand_state_philox4x32_10 st;
+    rocrand_init(seed, subseq, 4ull * (first_block + (unsigned long long)i), &st);
+    const uint4 r = rocrand4(&st);
+    out[4 * i + 0] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
+}
+
+extern "C" klara_status klara_selftest_rocrand_blocks(int32_t device, uint64_t seed, uint64_t subsequence,
+                                                      uint64_t first_block, int32_t nblocks, uint32_t* out)
+{
+    if (!out || nblocks <= 0) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    unsigned int* d = nullptr;
+    HIPCHK(dalloc(&d, (size_t)4 * nblocks));
+    hipLaunchKernelGGL(k_rocrand_blocks, dim3((nblocks + 63) / 64), dim3(64), 0, 0, (unsigned long long)seed,
+                       (unsigned long long)subsequence, (unsigned long long)first_block, nblocks, d);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out, d, sizeof(uint32_t) * 4 * (size_t)nblocks, hipMemcpyDeviceToHost);
+    (void)dfree(d);
+    return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+__global__ void k_math(int op, long long n, const double* in, const double* in2, double* out)
+{
+    kd_tables_to_lds();
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s, c;
+    switch (op) {
+    case 0: out[i] = kd_log(in[i]); break;
+    case 1: out[i] = kd_exp(in[i]); break;
+    case 2: kd_sincos2pi(in[i], &s, &c); out[i] = s; break;
+    case 3: kd_sincos2pi(in[i], &s, &c); out[i] = c; break;
+    case 4: out[i] = __builtin_sqrt(in[i]); break;
+    case 6: out[i] = kd_erf(in[i]); break;
+    case 7: out[i] = kd_log_u01(in[i]); break;
+    case 8: out[i] = kd_sqrt_radicand(in[i]); break;
+    case 9: out[i] = kd_exp_neg(in[i]); break;
+    case 10: kd_softplus_logistic(in[i], &s, &c); out[i] = s; break;
+    case 11: kd_softplus_logistic(in[i], &s, &c); out[i] = c; break;
+    case 12: out[i] = kd_log12(in[i]); break;
+    // the 20-bit angle of kd_normal_pair_w at index k = in[i] (0 <= k < 2^20), arithmetic form: sin, cos  (ops 13 / 14 are its table form, k_math_sctab)
+    case 15: kd_sincos2pi_bits(kd_angle_bits20((uint32_t)in[i] << 12), &s, &c); out[i] = s; break;
+    case 16: kd_sincos2pi_bits(kd_angle_bits20((uint32_t)in[i] << 12), &s, &c); out[i] = c; break;
+    default: out[i] = in[i] / in2[i]; break;
+    }
+}
+
+// ops 13 / 14: sin / cos of the same angle through the remainder table (kd_sincos2pi_tab20), which every workgroup fills first — as the transition
+// kernels that take the table do (klara_diagt.h SCTAB)
+__global__ __launch_bounds__(256) void k_math_sctab(int op, long long n, const double* in, double* out)
+{
+    kd_sincos_rem_to_lds();
+    kd_tables_to_lds();
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s, c;
+    kd_sincos2pi_tab20((uint32_t)in[i] << 12, &s, &c);
+    out[i] = op == 13 ? s : c;
+}
+
+extern "C" klara_status klara_selftest_math(int32_t device, int32_t op, int64_t n, const double* in,
+                                            const double* in2, double* out)
+{
+    if (!in || !out || n <= 0) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    double *di = nullptr, *di2 = nullptr, *dout = nullptr;
+    hipError_t e = dalloc(&di, (size_t)n);
+    if (e == hipSuccess) e = dalloc(&di2, (size_t)n);
+    if (e == hipSuccess) e = dalloc(&dout, (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(di, in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(di2, in2 ? in2 : in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (op == 13 || op == 14) {
+            e = hipFuncSetAttribute((const void*)k_math_sctab, hipFuncAttributeMaxDynamicSharedMemorySize, KD_SCREM_BYTES);
+            // (4,096 results per workgroup: the fill is a quarter of a workgroup's work, not all of it)
+            if (e == hipSuccess) hipLaunchKernelGGL(k_math_sctab, dim3((unsigned)((n + 255) / 256)), dim3(256), KD_SCREM_BYTES, 0, op, (long long)n, di, dout);
+        } else {
+            hipLaunchKernelGGL(k_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (long long)n, di, di2, dout);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
+    (void)dfree(di); (void)dfree(di2); (void)dfree(dout);
+    return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+// |z| exceedance counts and raw power sums of the proposal normals, drawn exactly as the transition kernels draw them
+// (kd_normal_pair_w on both halves of kd_stream_block(seed, chain, transition, slot 0)); one thread per chain, one atomic per thread
+// and threshold.  counts[k] = #{|z| > thr[k]} over 4 * nchains * ntransitions normals.
+__global__ __launch_bounds__(256) void k_normal_tail(unsigned long long seed, unsigned long long first_chain, long long nchains,
+                                                     long long ntransitions, int nthr, const double* __restrict__ thr,
+                                                     unsigned long long* __restrict__ counts, double* __restrict__ moments)
+{
+    kd_tables_to_lds();
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool ok = i < nchains;
+    unsigned long long c[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    double s1 = 0.0, s2 = 0.0, s4 = 0.0, mx = 0.0;
+    for (long long t = 0; t < ntransitions; ++t) {
+        const kd_u32x4 b = kd_stream_block(seed, first_chain + (unsigned long long)(ok ? i : 0), (unsigned long long)t, 0u);
+        for (int h = 0; h < 2; ++h) {                           // the block's two pairs: pair indices 0 and 8 of a transition
+            double z0, z1, u1, lg;
+            kd_normal_pair_w(h ? b.z : b.x, h ? b.w : b.y, &z0, &z1, &u1, &lg);
+            if (!ok) continue;
+            const double a0 = z0 < 0.0 ? -z0 : z0, a1 = z1 < 0.0 ? -z1 : z1;
+            for (int k = 0; k < 8; ++k) if (k < nthr) c[k] += (a0 > thr[k] ? 1ull : 0ull) + (a1 > thr[k] ? 1ull : 0ull);
+            s1 += z0 + z1; s2 += z0 * z0 + z1 * z1; s4 += (z0 * z0) * (z0 * z0) + (z1 * z1) * (z1 * z1);
+            mx = a0 > mx ? a0 : mx; mx = a1 > mx ? a1 : mx;
+        }
+    }
+    for (int k = 0; k < 8; ++k) if (k < nthr && c[k] != 0) atomicAdd(&counts[k], c[k]);
+    if (ok) {
+        atomicAdd(&moments[0], s1); atomicAdd(&moments[1], s2); atomicAdd(&moments[2], s4);
+        atomicMax((unsigned long long*)&moments[3], (unsigned long long)__double_as_longlong(mx));   // (non-negative doubles order like integers)
+    }
+}
+
+extern "C" klara_status klara_selftest_normal_tail(int32_t device, uint64_t seed, uint64_t first_chain, int64_t nchains,
+                                                   int64_t ntransitions, int32_t nthr, const double* thr, uint64_t* counts,
+                                                   double* moments)
+{
+    if (!thr || !counts || nthr <= 0 || nthr > 8 || nchains <= 0 || ntransitions <= 0) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    double* dthr = nullptr; unsigned long long* dc = nullptr; double* dm = nullptr;
+    hipError_t e = dalloc(&dthr, 8);
+    if (e == hipSuccess) e = dalloc(&dc, 8);
+    if (e == hipSuccess) e = dalloc(&dm, 4);
+    if (e == hipSuccess) e = hipMemcpy(dthr, thr, sizeof(double) * (size_t)nthr, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dc, 0, 8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(dm, 0, 4 * sizeof(double));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_normal_tail, dim3((unsigned)((nchains + 255) / 256)), dim3(256), 0, 0, (unsigned long long)seed,
+                           (unsigned long long)first_chain, (long long)nchains, (long long)ntransitions, (int)nthr, dthr, dc, dm);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(counts, dc, sizeof(uint64_t) * (size_t)nthr, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && moments) e = hipMemcpy(moments, dm, 4 * sizeof(double), hipMemcpyDeviceToHost);
+    (void)dfree(dthr); (void)dfree(dc); (void)dfree(dm);
+    return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+extern "C" klara_status klara_selftest_mfma_f64(int32_t device, const double* A, const double* B,
+                                                const double* C, double* D)
+{
+    if (!A || !B || !C || !D) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    double* buf = nullptr;
+    HIPCHK(dalloc(&buf, 64 + 64 + 256 + 256));
+    hipError_t e = hipMemcpy(buf, A, 64 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 64, B, 64 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 128, C, 256 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = klara_launch_mfma_probe(buf, buf + 64, buf + 128, buf + 384, 0);
+    if (e == hipSuccess) e = hipMemcpy(D, buf + 384, 256 * sizeof(double), hipMemcpyDeviceToHost);
+    (void)dfree(buf);
+    return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+extern "C" klara_status klara_selftest_mfma_f64_4x4x4(int32_t device, const double* A, const double* B,
+                                                      const double* C, double* D)
+{
+    if (!A || !B || !C || !D) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    double* buf = nullptr;
+    HIPCHK(dalloc(&buf, 256));
+    hipError_t e = hipMemcpy(buf, A, 64 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 64, B, 64 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(buf + 128, C, 64 * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = klara_launch_mfma4_probe(buf, buf + 64, buf + 128, buf + 192, 0);
+    if (e == hipSuccess) e = hipMemcpy(D, buf + 192, 64 * sizeof(double), hipMemcpyDeviceToHost);
+    (void)dfree(buf);
+    return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+extern "C" klara_status klara_check_custom_target(const char* src, int32_t sampler, int32_t ndims)
+{
+    if (!src || !sampler_valid(sampler) || ndims <= 0) return KLARA_ERR_INVALID_ARG;
+    // the plain fused instantiation of the layout klara_create plans for a job of this target (one chain; zeros: VanillaMCTuner per chain, no monitor)
+    klara_desc d;
+    memset(&d, 0, sizeof(d));
+    d.sampler = sampler; d.target = KLARA_TARGET_CUSTOM; d.ndims = ndims; d.nchains = 1; d.custom_src = src;
+    KlaraPlan plan;
+    const klara_status st = klara_plan_job(d, klara_read_overrides(), &plan);
+    if (st != KLARA_OK) return st;
+    const int modes[1] = { 0 };
+    if (plan.jit_pair) return klara_jit_create_pair(src, sampler, ndims, plan.E / 2, plan.G, false, false, false, modes, 1, false, nullptr);
+    const std::string whole = plan.rewrite == KLARA_REWRITE_PAIR_AS_WHOLE ? pair_as_whole_source(src) : std::string(src);
+    return klara_jit_create(whole.c_str(), sampler, ndims, plan.E, plan.G, modes, 1, false, nullptr);
+}
+
+// ... and the SMMALA kernels with the softabs transform of the metric (klara_desc.smmala_softabs > 0): the variant klara_create compiles for such a job
+extern "C" klara_status klara_check_custom_target_softabs(const char* src, int32_t ndims)
+{
+    if (!src || ndims <= 0) return KLARA_ERR_INVALID_ARG;
+    klara_desc d;
+    memset(&d, 0, sizeof(d));
+    d.sampler = KLARA_SAMPLER_SMMALA; d.target = KLARA_TARGET_CUSTOM; d.ndims = ndims; d.nchains = 1; d.custom_src = src; d.smmala_softabs = 1.0;
+    KlaraPlan plan;
+    const klara_status st = klara_plan_job(d, klara_read_overrides(), &plan);
+    if (st != KLARA_OK) return st;
+    const int modes[1] = { 0 };
+    return klara_jit_create(src, KLARA_SAMPLER_SMMALA, ndims, plan.E, plan.G, modes, 1, false, nullptr, true);
+}
+
+extern "C" const char* klara_compile_log(void) { return klara_jit_log(); }

@@ -134,22 +134,22 @@ def default_layout(target_kind: int, ndims: int, ndata: int = 0, sampler=None, t
                    hier_nunits: int = 0, hier_ntimes: int = 0, summaries: bool = True, sparse_moves: bool = False, pair_form: bool = False, custom_rows: int = 2):
     """Mirror of the product's layout choice (klara_get_layout reports the real one on the GPU box).  `sampler`, `tuner`,
     `tuner_mode` and `verbose` are only needed to recognise the pair-transposed layout (kind 3): diagonal Gaussian,
-    MH / MALA / HMC, even D <= 128, Vanilla or AcceptanceRate tuner (klara_api.hip diagt_eligible)."""
+    MH / MALA / HMC, even D <= 128, Vanilla or AcceptanceRate tuner (klara_plan.h diagt_eligible)."""
     d = int(ndims)
     plain = sampler is not None      # (name kept from when the layout excluded tuned jobs)
     if (target_kind == L.TARGET_GAUSS_DIAG and sampler is not None and plain
             and 17 <= d <= 1024 and os.environ.get("KLARA_LAYOUT_KIND", "3") != "0" and "KLARA_LAYOUT_E" not in os.environ):
-        q = 8 if d <= 128 else (16 if d <= 256 else (32 if d <= 512 else 64))          # lanes per chain (klara_api.hip select_layout)
+        q = 8 if d <= 128 else (16 if d <= 256 else (32 if d <= 512 else 64))          # lanes per chain (klara_plan.h select_layout)
         # (untuned MH / MALA up to D = 104 also run on 4-lane kernels: they sum in this 8-lane order, klara_diagt.h)
         return (3, q, 2 * ((d + 2 * q - 1) // (2 * q)))
     if (target_kind == L.TARGET_HIER_NORMAL and sampler in (L.SAMPLER_MH, L.SAMPLER_MALA, L.SAMPLER_HMC)
             and 9 <= hier_nunits <= 32 and os.environ.get("KLARA_LAYOUT_KIND", "4") != "0"):
         return (4, 8, 8)              # klara_hiert.h: 8 lanes per chain, 4 units per lane
-    if target_kind == L.TARGET_CUSTOM and pair_form:     # pair closure: the pair-transposed layout (klara_api.hip select_layout)
+    if target_kind == L.TARGET_CUSTOM and pair_form:     # pair closure: the pair-transposed layout (klara_plan.h select_layout)
         q = 8 if d <= 128 else (16 if d <= 256 else (32 if d <= 512 else 64))
         return (3, q, 2 * ((d + 2 * q - 1) // (2 * q)))
     if target_kind == L.TARGET_CUSTOM and d > 32 and os.environ.get("KLARA_CUSTOM_LANES", "0") != "1":
-        # whole-vector closure staged through LDS (klara_api.hip custom_layout): G lanes x E = 2 ceil(D / 2G) <= 16 elements, a workgroup's
+        # whole-vector closure staged through LDS (klara_plan.h custom_layout): G lanes x E = 2 ceil(D / 2G) <= 16 elements, a workgroup's
         # rows (4 wavefronts x 64 / G chains, `custom_rows` vectors each) within 56 KB
         g = int(os.environ.get("KLARA_CUSTOM_LANES", "0")) or 4
         rows = custom_rows
@@ -249,7 +249,7 @@ class OracleJob:
         d.hier_prior_prec, d.hier_gamma_a, d.hier_gamma_b = float(hier_prior_prec), float(hier_gamma_a), float(hier_gamma_b)
         self._user = None
         if custom_src is not None:
-            # (a pair closure the pair-transposed kernels do not serve runs as a whole-vector closure: klara_api.hip pair_as_whole, klara_custom_compose.h)
+            # (a pair closure the pair-transposed kernels do not serve runs as a whole-vector closure: klara_plan.h pair_as_whole, klara_custom_compose.h)
             if "KLARA_USER_PAIR_TARGET" in custom_src and (self.D < 17 or (int(sampler) == L.SAMPLER_SLICE and "KLARA_PAIR_SLICE_AS_WHOLE" in os.environ)):
                 custom_src = "#define KLARA_PAIR_AS_WHOLE 1\n" + custom_src
             self._user = compile_user_target(custom_src, self.D)

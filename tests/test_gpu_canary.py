@@ -3,7 +3,7 @@
 Every kernel addresses the chains' vectors through buffer resources (`group_window`: num_records = the bytes of the chains that exist) plus
 per-lane byte offsets, with KLARA_BUF_OOB offsets for padding lanes: the hardware returns 0 for an out-of-range load and drops the store.
 A window one element too large or an offset that is in range when it should not be is silent — unless the neighbours are canaries.
-KLARA_DEBUG_CANARY=1 puts 4 KiB of a signalling-NaN pattern before and after EVERY device array (klara_api.hip dalloc_bytes); a stray store
+KLARA_DEBUG_CANARY=1 puts 4 KiB of a signalling-NaN pattern before and after EVERY device array (klara_devmem.hip dalloc_bytes); a stray store
 is found when the handle is destroyed (klara_destroy -> KLARA_ERR_STATE -> Engine.close raises) or by klara_selftest_canary, a stray load
 brings a NaN into results the parity tests compare bit for bit with the oracle.
 """

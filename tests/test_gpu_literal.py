@@ -221,7 +221,7 @@ def _new_jobs():
 
 
 def _offsets(n, nparts=2):
-    blocks = (n + 15) // 16                               # chain partitions are cut in blocks of 16 chains (klara_api.hip part_range)
+    blocks = (n + 15) // 16                               # chain partitions are cut in blocks of 16 chains (klara_run.hip part_range)
     boundary = ((blocks + 1) // 2) * 16
     return (0, boundary - 8, n - BLOCK)
 

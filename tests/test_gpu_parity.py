@@ -1721,7 +1721,7 @@ def test_full_size_pair_transposed_on_sampled_chains(name, kw, nsteps, spl):
     mask = eng.accept_mask()
     na, _ = eng.accept_counts()
     assert np.array_equal(na, mask.sum(axis=0))
-    blocks = (n + 15) // 16                               # partitions are cut in blocks of 16 chains (klara_api.hip part_range)
+    blocks = (n + 15) // 16                               # partitions are cut in blocks of 16 chains (klara_run.hip part_range)
     boundary = ((blocks + 1) // 2) * 16                   # first chain of the second partition
     case = dict(kw, target=target, nchains=16, nsteps=nsteps, name=name, x0=None, seed=20260927)
     for off in (0, boundary - 8, n - 16):

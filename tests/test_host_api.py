@@ -812,6 +812,21 @@ def _plan(klib, runs, **kw):
     return k[:n], col[:n], ph[:n], fl[:n]
 
 
+def test_monitors_a_job_cannot_have_are_refused_without_a_device(klib):
+    """The gradient history on a sampler that carries no gradient (MH, slice) and the likelihood / prior history on a target that is not a
+    likelihood + prior user target are descriptor errors: validate() refuses them (klara_selftest_plan runs it and needs no device), before
+    klara_create allocates anything."""
+    ones = np.ones(3)
+    ptr = ones.ctypes.data_as(C.POINTER(C.c_double))
+    _plan(klib, [10], monitor=L.MON_HIST_GRAD)                       # MALA carries one
+    for kw in (dict(sampler=L.SAMPLER_MH, mh_sigma=ptr, monitor=L.MON_HIST_GRAD),
+               dict(sampler=L.SAMPLER_SLICE, slice_widths=ptr, monitor=L.MON_HIST_GRAD),
+               dict(monitor=L.MON_HIST_LLLP)):
+        with pytest.raises(K.KlaraError) as e:
+            _plan(klib, [10], **kw)
+        assert e.value.status == L.ERR_INVALID_ARG, kw
+
+
 @pytest.mark.parametrize("seed", range(40))
 def test_launch_planning_is_pure_host_logic(klib, seed):
     """klara_run's launch splitting, checked without a device against a step-by-step model: every launch stays within
