@@ -6,36 +6,19 @@
 hipError_t klara_launch_dense_big(const KParams* p, const KLaunch& kl, int sampler, bool da, int NE, const double* Pfrag, bool hasmu, dim3 grid, hipStream_t st);
 hipError_t klara_launch_dense_init_big(const KParams& p, int NE, const double* Pfrag, bool hasmu, int needgrad, dim3 grid, hipStream_t st);
 
-template <int SAMPLER, bool DA, bool HASMU, bool PLAIN = false>
-static hipError_t launch_dense_m(const KParams* p, const KLaunch& kl, int NE, const double* Pfrag, dim3 grid, hipStream_t st)
-{
-    const dim3 blk(512);
-#define KLARA_DENSE_CASE(N)                                                                            \
-    case N: {                                                                                          \
-        constexpr size_t lds = sizeof(double) * (64 * (size_t)N * (size_t)((N + 3) / 4) + (HASMU ? 4 * N : 0)); \
-        hipError_t e = hipFuncSetAttribute((const void*)k_dense_transitions<SAMPLER, N, DA, HASMU, PLAIN>,        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-        if (e != hipSuccess) return e;                                                                 \
-        e = klara_go(k_dense_transitions<SAMPLER, N, DA, HASMU, PLAIN>, grid, blk, lds, st, p, kl, Pfrag);  \
-        if (e != hipSuccess) return e;                                                                 \
-        break;                                                                                         \
-    }
-    switch (NE) {
-        KLARA_DENSE_CASE(8)
-        KLARA_DENSE_CASE(16)
-        KLARA_DENSE_CASE(25)
-        KLARA_DENSE_CASE(32)
-    default: return hipErrorInvalidValue;
-    }
-#undef KLARA_DENSE_CASE
-    return hipGetLastError();
-}
+// the workgroup's dynamic LDS: the precision matrix's fragments + the mean.  (NE = 8 and 16 ask for 8 and 32.5 KB, which every launch gets; 25 and 32 opt in.)
+template <int N, bool HASMU> constexpr size_t dense_lds() { return sizeof(double) * (64 * (size_t)N * (size_t)((N + 3) / 4) + (HASMU ? 4 * N : 0)); }
 
 template <int SAMPLER, bool DA, bool PLAIN = false>
 static hipError_t launch_dense_s(const KParams* p, const KLaunch& kl, int NE, const double* Pfrag, bool hasmu, dim3 grid, hipStream_t st)
 {
-    if (PLAIN) return hasmu ? launch_dense_m<SAMPLER, DA, true, PLAIN>(p, kl, NE, Pfrag, grid, st) : launch_dense_m<SAMPLER, DA, false, PLAIN>(p, kl, NE, Pfrag, grid, st);
-    return hasmu ? launch_dense_m<SAMPLER, DA, true>(p, kl, NE, Pfrag, grid, st) : launch_dense_m<SAMPLER, DA, false>(p, kl, NE, Pfrag, grid, st);
+    return klara_pick<1, 0>(hasmu, [&](auto m) {
+        return klara_pick<8, 16, 25, 32>(NE, [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            constexpr bool HASMU = decltype(m)::value != 0;
+            return klara_go(k_dense_transitions<SAMPLER, N, DA, HASMU, PLAIN>, grid, dim3(512), dense_lds<N, HASMU>(), st, p, kl, Pfrag);
+        });
+    });
 }
 
 hipError_t klara_launch_dense(const KParams* p, const KLaunch& kl, int sampler, int tuner, bool plain, int NE, const double* Pfrag, bool hasmu,
@@ -54,44 +37,24 @@ hipError_t klara_launch_dense(const KParams* p, const KLaunch& kl, int sampler, 
     }
 }
 
-template <bool HASMU>
-static hipError_t launch_dense_init_m(const KParams& p, int NE, const double* Pfrag, int needgrad, dim3 grid, hipStream_t st)
-{
-    const dim3 blk(512);
-#define KLARA_DENSE_CASE(N)                                                                            \
-    case N: {                                                                                          \
-        constexpr size_t lds = sizeof(double) * (64 * (size_t)N * (size_t)((N + 3) / 4) + (HASMU ? 4 * N : 0)); \
-        hipError_t e = hipFuncSetAttribute((const void*)k_dense_init<N, HASMU>,                        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-        if (e != hipSuccess) return e;                                                                 \
-        hipLaunchKernelGGL((k_dense_init<N, HASMU>), grid, blk, lds, st, p, Pfrag, needgrad);          \
-        break;                                                                                         \
-    }
-    switch (NE) {
-        KLARA_DENSE_CASE(8)
-        KLARA_DENSE_CASE(16)
-        KLARA_DENSE_CASE(25)
-        KLARA_DENSE_CASE(32)
-    default: return hipErrorInvalidValue;
-    }
-#undef KLARA_DENSE_CASE
-    return hipGetLastError();
-}
-
 hipError_t klara_launch_dense_init(const KParams& p, int NE, const double* Pfrag, bool hasmu, int needgrad, dim3 grid, hipStream_t st)
 {
     if (NE > 32) return klara_launch_dense_init_big(p, NE, Pfrag, hasmu, needgrad, grid, st);
-    return hasmu ? launch_dense_init_m<true>(p, NE, Pfrag, needgrad, grid, st) : launch_dense_init_m<false>(p, NE, Pfrag, needgrad, grid, st);
+    return klara_pick<1, 0>(hasmu, [&](auto m) {
+        return klara_pick<8, 16, 25, 32>(NE, [&](auto n) {
+            constexpr int N = decltype(n)::value;
+            constexpr bool HASMU = decltype(m)::value != 0;
+            return klara_start(k_dense_init<N, HASMU>, grid, dim3(512), dense_lds<N, HASMU>(), st, p, Pfrag, needgrad);
+        });
+    });
 }
 
 hipError_t klara_launch_mfma_probe(const double* A, const double* B, const double* C, double* D, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_mfma_f64_probe, dim3(1), dim3(64), 0, st, A, B, C, D);
-    return hipGetLastError();
+    return klara_start(k_mfma_f64_probe, dim3(1), dim3(64), 0, st, A, B, C, D);
 }
 
 hipError_t klara_launch_mfma4_probe(const double* A, const double* B, const double* C, double* D, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_mfma_f64_4x4x4_probe, dim3(1), dim3(64), 0, st, A, B, C, D);
-    return hipGetLastError();
+    return klara_start(k_mfma_f64_4x4x4_probe, dim3(1), dim3(64), 0, st, A, B, C, D);
 }

@@ -3,12 +3,7 @@
 
 hipError_t KLARA_DIAGT_FN(klara_launch_diagt_init)(const KParams& p, int NP, int needgrad, dim3 grid, hipStream_t st)
 {
-    const dim3 blk(256);
-    switch (NP) {
-#define X(NP_) case NP_: hipLaunchKernelGGL((k_diagt_init<NP_, KLARA_DIAGT_Q>), grid, blk, 0, st, p, needgrad); break;
-        KLARA_DIAGT_NP_MENU_DO(X)
-#undef X
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return klara_pick<KLARA_DIAGT_NP_MENU>(NP, [&](auto np) {
+        return klara_start(k_diagt_init<decltype(np)::value, KLARA_DIAGT_Q>, grid, dim3(256), 0, st, p, needgrad);
+    });
 }

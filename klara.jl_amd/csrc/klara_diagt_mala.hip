@@ -3,5 +3,5 @@
 
 hipError_t KLARA_DIAGT_FN(klara_launch_diagt_mala)(const KParams* p, const KLaunch& kl, int NP, bool onestep, bool unitw, bool mon, bool tune, bool da, const KAuto& ka, long long nwaves, hipStream_t st)
 {
-    KLARA_DISPATCH_DIAGT(KLARA_SAMPLER_MALA);
+    return launch_diagt<KLARA_SAMPLER_MALA>(p, kl, NP, onestep, unitw, mon, tune, da, ka, nwaves, st);
 }

@@ -2,24 +2,14 @@
 #include "klara_launch.h"
 #include "klara_diagt_slice.h"
 
-#define KLARA_DIAGT_SLICE_CASE(NP_)                                                                                       \
-    case NP_:                                                                                                              \
-        if (tune && unitw) e_ = diagt_go<KLARA_SAMPLER_SLICE, NP_, KLARA_DIAGT_Q, false, true, true, true>(p, kl, ka, nwaves, st);        \
-        else if (tune) e_ = diagt_go<KLARA_SAMPLER_SLICE, NP_, KLARA_DIAGT_Q, false, false, true, true>(p, kl, ka, nwaves, st);       \
-        else if (mon && unitw) e_ = diagt_go<KLARA_SAMPLER_SLICE, NP_, KLARA_DIAGT_Q, false, true, true>(p, kl, ka, nwaves, st);      \
-        else if (mon) e_ = diagt_go<KLARA_SAMPLER_SLICE, NP_, KLARA_DIAGT_Q, false, false, true>(p, kl, ka, nwaves, st);              \
-        else if (unitw) e_ = diagt_go<KLARA_SAMPLER_SLICE, NP_, KLARA_DIAGT_Q, false, true, false>(p, kl, ka, nwaves, st);            \
-        else e_ = diagt_go<KLARA_SAMPLER_SLICE, NP_, KLARA_DIAGT_Q, false, false, false>(p, kl, ka, nwaves, st);                      \
-        break;
-
 hipError_t KLARA_DIAGT_FN(klara_launch_diagt_slice)(const KParams* p, const KLaunch& kl, int NP, bool unitw, bool mon, bool tune, const KAuto& ka, long long nwaves, hipStream_t st)
 {
-    hipError_t e_ = hipSuccess;
-    switch (NP) {
-        KLARA_DIAGT_NP_MENU_DO(KLARA_DIAGT_SLICE_CASE)
-    default: return hipErrorInvalidValue;
-    }
-    return e_;
+    return klara_pick<KLARA_DIAGT_NP_MENU>(NP, [&](auto np) {
+        constexpr int NP_ = decltype(np)::value;
+        if (tune) return diagt_row<KLARA_SAMPLER_SLICE, NP_, false, true, true>(p, kl, unitw, ka, nwaves, st);
+        if (mon) return diagt_row<KLARA_SAMPLER_SLICE, NP_, false, true>(p, kl, unitw, ka, nwaves, st);
+        return diagt_row<KLARA_SAMPLER_SLICE, NP_, false, false>(p, kl, unitw, ka, nwaves, st);
+    });
 }
 
 // untuned jobs without a history monitor: every lane takes its element pairs through the whole launch on its own (klara_diagt_slice.h), nm = 1 or 2 machines each
@@ -30,11 +20,13 @@ hipError_t KLARA_DIAGT_FN(klara_launch_diagt_slice_free)(const KParams* p, const
     const dim3 grid((unsigned)((nwaves + 3) / 4)), blk(256);
     // dynamic LDS: the widths of the job's 2 NP Q element slots, and weights + means for a non-unit diagonal
     const size_t lds = (size_t)(unitw ? 1 : 3) * 2 * NP * KLARA_DIAGT_Q * sizeof(double);
-#define KLARA_SLICEF_GO(U, S)                                                                                          \
-    (nm == 1 ? klara_go(k_diagt_slice_free<KLARA_DIAGT_Q, U, S, 1>, grid, blk, lds, st, p, kl, ka, NP)                  \
-             : klara_go(k_diagt_slice_free<KLARA_DIAGT_Q, U, S, 2>, grid, blk, lds, st, p, kl, ka, NP))
-    const hipError_t e = unitw ? (sums ? KLARA_SLICEF_GO(true, true) : KLARA_SLICEF_GO(true, false)) : (sums ? KLARA_SLICEF_GO(false, true) : KLARA_SLICEF_GO(false, false));
-#undef KLARA_SLICEF_GO
+    const hipError_t e = klara_pick<1, 0>(unitw, [&](auto u) {
+        return klara_pick<1, 0>(sums, [&](auto s) {
+            return klara_pick<1, 2>(nm == 1 ? 1 : 2, [&](auto m) {
+                return klara_go(k_diagt_slice_free<KLARA_DIAGT_Q, decltype(u)::value != 0, decltype(s)::value != 0, decltype(m)::value>, grid, blk, lds, st, p, kl, ka, NP);
+            });
+        });
+    });
     if (e != hipSuccess || klara_attr_query != nullptr) return e;
     // the new state's log-target in the layout's order (the kernel above deals the elements to the lanes round robin): one wavefront per chain group
     return unitw ? klara_go(k_diagt_hist_lt<KLARA_DIAGT_Q, true, true>, grid, blk, 0, st, p, kl, NP, 0LL, 1)

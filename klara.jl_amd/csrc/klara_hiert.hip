@@ -30,6 +30,5 @@ hipError_t klara_launch_hiert(const KParams* p, const KLaunch& kl, int sampler, 
 hipError_t klara_launch_hiert_init(const KParams& p, int RPL, int NT, int needgrad, dim3 grid, hipStream_t st)
 {
     if (RPL != 4 || NT < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((k_hiert_init<4, 5>), grid, dim3(256), 0, st, p, needgrad);
-    return hipGetLastError();
+    return klara_start(k_hiert_init<4, 5>, grid, dim3(256), 0, st, p, needgrad);
 }

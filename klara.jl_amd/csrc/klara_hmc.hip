@@ -4,5 +4,5 @@
 hipError_t klara_launch_hmc(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
                             hipStream_t st)
 {
-    KLARA_DISPATCH_GROUP(k_transitions, KLARA_SAMPLER_HMC);
+    return launch_group<KLARA_SAMPLER_HMC>(p, kl, mode, target, E, G, grid, lds, st);
 }

@@ -5,16 +5,48 @@
 #include "klara_kernels.h"
 #include "klara_diagt.h"
 
-// Every transition kernel is launched through klara_go: when klara_attr_query points at a hipFuncAttributes (klara_get_kernel_attributes,
-// klara_monitors.hip) the launcher reports the kernel's registers / scratch / LDS instead of launching it — the dispatch code that
-// picks an instantiation for a job is then the one source of truth for "which kernel does this handle run".
+// How a kernel is launched — the one place.  Two entry points over one body, klara_launch_kernel<QUERY>:
+//   klara_go     every transition (step) kernel.  When klara_attr_query points at a hipFuncAttributes (klara_get_kernel_attributes, klara_monitors.hip)
+//                it reports the kernel's registers / scratch / LDS instead of launching it — the dispatch code that picks an instantiation for a job
+//                is then the one source of truth for "which kernel does this handle run".
+//   klara_start  the init / start-state kernels (and the self test): never queried, always launched.
+// The opt-in rule: a launch gets 64 KB of LDS — 8 KB of math tables + KLARA_LDS_DEFAULT_DYNAMIC = 56 KB of dynamic — without asking; a launch that asks
+// for more dynamic LDS opts in first (raises the kernel's limit), on every such launch (nothing remembers that the attribute is set), and BEFORE the query,
+// so a queried kernel reports the attributes it is launched with.  Both return the first error: the opt-in's, the query's or the launch's.
+#ifndef KLARA_LDS_DEFAULT_DYNAMIC
+#define KLARA_LDS_DEFAULT_DYNAMIC 57344u
+#endif
 extern thread_local hipFuncAttributes* klara_attr_query;
-template <class... KArgs, class... Args>
-static inline hipError_t klara_go(void (*kern)(KArgs...), dim3 grid, dim3 blk, size_t lds, hipStream_t st, Args... args)
+template <bool QUERY, class... KArgs, class... Args>
+static inline hipError_t klara_launch_kernel(void (*kern)(KArgs...), dim3 grid, dim3 blk, size_t lds, hipStream_t st, Args... args)
 {
-    if (klara_attr_query != nullptr) return hipFuncGetAttributes(klara_attr_query, (const void*)kern);
+    if (lds > KLARA_LDS_DEFAULT_DYNAMIC) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    if (QUERY && klara_attr_query != nullptr) return hipFuncGetAttributes(klara_attr_query, (const void*)kern);
     hipLaunchKernelGGL(kern, grid, blk, lds, st, args...);
     return hipGetLastError();
+}
+template <class K, class... Args>
+static inline hipError_t klara_go(K kern, dim3 grid, dim3 blk, size_t lds, hipStream_t st, Args... args)
+{
+    return klara_launch_kernel<true>(kern, grid, blk, lds, st, args...);
+}
+template <class K, class... Args>
+static inline hipError_t klara_start(K kern, dim3 grid, dim3 blk, size_t lds, hipStream_t st, Args... args)
+{
+    return klara_launch_kernel<false>(kern, grid, blk, lds, st, args...);
+}
+
+// A run-time integer as a template argument: calls f(KInt<N>()) for the N of the menu Ns... equal to v (a bool: the menu <1, 0>); a value that is
+// not on the menu is hipErrorInvalidValue.  Every launcher's "which instantiation" ladder is one of these; the menu says what is instantiated.
+template <int... Ns, class F>
+static inline hipError_t klara_pick(int v, F&& f)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)(... || (v == Ns ? (e = f(KInt<Ns>()), true) : false));     // (a left fold: the menu is instantiated in its order)
+    return e;
 }
 
 // Forward-mode autodiff of a user-defined target (klara_autodiff.h): the value of the source's `#define KLARA_USER_AUTODIFF n` marker — 1: the gradient,
@@ -108,72 +140,56 @@ hipError_t klara_launch_diagt_hmc_q4(const KParams* p, const KLaunch& kl, int NP
 hipError_t klara_launch_diagt_init_q4(const KParams& p, int NP, int needgrad, dim3 grid, hipStream_t st);
 // pairs per lane the kernels are instantiated for; a job takes NP = ceil(ceil(D/2) / Q) exactly (only the LAST pair of a lane
 // can be padding)
+// (a klara_pick menu)
 #if KLARA_DIAGT_Q == 4
-#define KLARA_DIAGT_NP_MENU_DO(X) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13)
+#define KLARA_DIAGT_NP_MENU 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13
 #elif KLARA_DIAGT_Q == 8
-#define KLARA_DIAGT_NP_MENU_DO(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+#define KLARA_DIAGT_NP_MENU 2, 3, 4, 5, 6, 7, 8
 #else                      // Q = 16 / 32 start where the narrower variant ends: NP = 5..8
-#define KLARA_DIAGT_NP_MENU_DO(X) X(5) X(6) X(7) X(8)
+#define KLARA_DIAGT_NP_MENU 5, 6, 7, 8
 #endif
 #define KLARA_DIAGT_NP_MAX 8
 
 // one launch of a pair-transposed kernel over `nwaves` chain groups: one wavefront each, four per workgroup.  The kernels that read the angle's
 // remainder terms from an LDS table (klara_diagt.h SCTAB) get the table's 64 KB of dynamic LDS; a launch too short to amortise the fill
 // runs the arithmetic instantiation (the same bits).
+static_assert(KD_SCREM_BYTES > KLARA_LDS_DEFAULT_DYNAMIC, "the table is more than a launch gets without asking: klara_go opts in");
 template <int S, int NP_, int Q_, bool ONESTEP, bool UNITW, bool MON, bool TUNE = false, bool DA = false>
 static hipError_t diagt_go(const KParams* p, const KLaunch& kl, const KAuto& ka, long long nwaves, hipStream_t st)
 {
     const dim3 grid((unsigned)((nwaves + 3) / 4)), blk(256);
     if constexpr (diagt_sctab<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE>()) {
-        if (kl.nsteps >= KLARA_SCTAB_MIN_STEPS) {
-            const auto kern = k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA, false, true>;
-            // a launch gets 64 KB of LDS without asking (8 KB of math tables + the table is more): asked for before the launch, like every launcher here
-            const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, KD_SCREM_BYTES);
-            if (e != hipSuccess) return e;
-            return klara_go(kern, grid, blk, (size_t)KD_SCREM_BYTES, st, p, kl, ka);
-        }
+        if (kl.nsteps >= KLARA_SCTAB_MIN_STEPS)
+            return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA, false, true>, grid, blk, (size_t)KD_SCREM_BYTES, st, p, kl, ka);
     }
     return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA>, grid, blk, 0, st, p, kl, ka);
 }
-
-#if KLARA_DIAGT_Q == 4     // (no tuned / dual-averaging instantiations: those jobs take the 8-lane form)
-#define KLARA_DIAGT_CASE(S, NP_)                                                                                   \
-    case NP_:                                                                                                      \
-        if (tune || da) return hipErrorInvalidValue;                                                               \
-        else if (mon && unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, true, true>(p, kl, ka, nwaves, st); \
-        else if (mon) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, false, true>(p, kl, ka, nwaves, st);        \
-        else if (onestep && unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, true, true, false>(p, kl, ka, nwaves, st);  \
-        else if (onestep) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, true, false, false>(p, kl, ka, nwaves, st);    \
-        else if (unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, true, false>(p, kl, ka, nwaves, st);      \
-        else e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, false, false>(p, kl, ka, nwaves, st);                \
-        break;
-#else
-#define KLARA_DIAGT_CASE(S, NP_)                                                                                   \
-    case NP_:                                                                                                      \
-        if (da && unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, true, true, true, (S == KLARA_SAMPLER_HMC)>(p, kl, ka, nwaves, st); \
-        else if (da) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, false, true, true, (S == KLARA_SAMPLER_HMC)>(p, kl, ka, nwaves, st); \
-        else if (tune && unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, true, true, true>(p, kl, ka, nwaves, st);  \
-        else if (tune) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, false, true, true>(p, kl, ka, nwaves, st);  \
-        else if (mon && unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, true, true>(p, kl, ka, nwaves, st); \
-        else if (mon) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, false, true>(p, kl, ka, nwaves, st);        \
-        else if (onestep && unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, true, true, false>(p, kl, ka, nwaves, st);  \
-        else if (onestep) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, true, false, false>(p, kl, ka, nwaves, st);    \
-        else if (unitw) e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, true, false>(p, kl, ka, nwaves, st);      \
-        else e_ = diagt_go<S, NP_, KLARA_DIAGT_Q, false, false, false>(p, kl, ka, nwaves, st);                \
-        break;
-#endif
-#define KLARA_DIAGT_CASE_KLARA_SAMPLER_MH(NP_) KLARA_DIAGT_CASE(KLARA_SAMPLER_MH, NP_)
-#define KLARA_DIAGT_CASE_KLARA_SAMPLER_MALA(NP_) KLARA_DIAGT_CASE(KLARA_SAMPLER_MALA, NP_)
-#define KLARA_DIAGT_CASE_KLARA_SAMPLER_HMC(NP_) KLARA_DIAGT_CASE(KLARA_SAMPLER_HMC, NP_)
-#define KLARA_DISPATCH_DIAGT(S)                                                                                    \
-    do {                                                                                                           \
-        hipError_t e_ = hipSuccess;                                                                                \
-        switch (NP) {                                                                                              \
-            KLARA_DIAGT_NP_MENU_DO(KLARA_DIAGT_CASE_##S)                                                           \
-            default: return hipErrorInvalidValue;                                                                  \
-        }                                                                                                          \
-        return e_;                                                                                                 \
-    } while (0)
+// ... both forms of the diagonal (unit weights or not) of one (ONESTEP, MON, TUNE, DA) row of the flag ladders
+template <int S, int NP_, bool ONESTEP, bool MON, bool TUNE = false, bool DA = false>
+static hipError_t diagt_row(const KParams* p, const KLaunch& kl, bool unitw, const KAuto& ka, long long nwaves, hipStream_t st)
+{
+    return unitw ? diagt_go<S, NP_, KLARA_DIAGT_Q, ONESTEP, true, MON, TUNE, DA>(p, kl, ka, nwaves, st)
+                 : diagt_go<S, NP_, KLARA_DIAGT_Q, ONESTEP, false, MON, TUNE, DA>(p, kl, ka, nwaves, st);
+}
+// the MH / MALA / HMC launchers of klara_diagt_{mh,mala,hmc}.hip: NP, then the flag ladder — dual averaging (its kernel state only in HMC),
+// a tuner, a monitor, one transition per launch, plain
+template <int S>
+static hipError_t launch_diagt(const KParams* p, const KLaunch& kl, int NP, bool onestep, bool unitw, bool mon, bool tune, bool da, const KAuto& ka, long long nwaves,
+                               hipStream_t st)
+{
+    return klara_pick<KLARA_DIAGT_NP_MENU>(NP, [&](auto np) {
+        constexpr int NP_ = decltype(np)::value;
+        if constexpr (KLARA_DIAGT_Q == 4) {     // (no tuned / dual-averaging instantiations: those jobs take the 8-lane form)
+            if (tune || da) return hipErrorInvalidValue;
+        } else {
+            if (da) return diagt_row<S, NP_, false, true, true, (S == KLARA_SAMPLER_HMC)>(p, kl, unitw, ka, nwaves, st);
+            if (tune) return diagt_row<S, NP_, false, true, true>(p, kl, unitw, ka, nwaves, st);
+        }
+        if (mon) return diagt_row<S, NP_, false, true>(p, kl, unitw, ka, nwaves, st);
+        if (onestep) return diagt_row<S, NP_, true, false>(p, kl, unitw, ka, nwaves, st);
+        return diagt_row<S, NP_, false, false>(p, kl, unitw, ka, nwaves, st);
+    });
+}
 
 // MH / MALA / HMC on the hierarchical target, 8 lanes per chain (layout kind 4, klara_hiert.h); RPL = 4 units per lane, NT = 5
 hipError_t klara_launch_hiert(const KParams* p, const KLaunch& kl, int sampler, int RPL, int NT, bool mon, bool tune, bool da, dim3 grid,
@@ -196,49 +212,33 @@ hipError_t klara_jit_launch_init(KlaraJit* j, const KParams& p, int needgrad, di
 hipError_t klara_jit_launch(KlaraJit* j, int mode, const KParams* p, const KLaunch& kl, dim3 grid, size_t lds, hipStream_t st, int block = 256);
 const char* klara_jit_log();
 
-// mode 7: mode 3 with exactly one transition per launch; mode 3: nothing counts/tunes and nothing is monitored;
-// mode 1: nothing counts/tunes; mode 0: general
-// (a launch gets 64 KB of LDS — 8 KB of math tables + 56 KB of dynamic — without asking; the logistic target's data rows may need more)
-#ifndef KLARA_LDS_DEFAULT_DYNAMIC
-#define KLARA_LDS_DEFAULT_DYNAMIC 57344u
-#endif
-#define KLARA_LAUNCH_TM(S, T, E_, G_, M_)                                                                                          \
-    do {                                                                                                                          \
-        if (lds > KLARA_LDS_DEFAULT_DYNAMIC) {                                                                                    \
-            hipError_t e_ = hipFuncSetAttribute((const void*)k_transitions<S, T, E_, G_, M_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e_ != hipSuccess) return e_;                                                                                      \
-        }                                                                                                                         \
-        { const hipError_t e_ = klara_go(k_transitions<S, T, E_, G_, M_>, grid, blk, lds, st, p, kl); if (e_ != hipSuccess) return e_; }  \
-    } while (0)
-#define KLARA_LAUNCH_T(S, T, E_, G_)                                                                    \
-    do {                                                                                               \
-        if (mode == 7) KLARA_LAUNCH_TM(S, T, E_, G_, 7);                                                \
-        else if ((mode & 3) == 3) KLARA_LAUNCH_TM(S, T, E_, G_, 3);                                     \
-        else if (mode & 1) KLARA_LAUNCH_TM(S, T, E_, G_, 1);                                            \
-        else KLARA_LAUNCH_TM(S, T, E_, G_, 0);                                                          \
-    } while (0)
+// the group-layout transition kernels' MODE — 7: mode 3 with exactly one transition per launch; 3: nothing counts/tunes and nothing is monitored;
+// 1: nothing counts/tunes; 0: general — from the launch's mode bits.  (The logistic target's data rows may need more LDS than a launch gets without asking.)
+template <int S, int T, int E_, int G_>
+static hipError_t launch_transitions(const KParams* p, const KLaunch& kl, int mode, dim3 grid, size_t lds, hipStream_t st)
+{
+    return klara_pick<7, 3, 1, 0>(mode == 7 ? 7 : (mode & 3) == 3 ? 3 : (mode & 1), [&](auto m) {
+        return klara_go(k_transitions<S, T, E_, G_, decltype(m)::value>, grid, dim3(256), lds, st, p, kl);
+    });
+}
 
-// dispatch helper used by every group-layout launcher
-#define KLARA_DISPATCH_GROUP(KERNEL_EXPR_PREFIX, SAMPLER)                                              \
-    do {                                                                                               \
-        const dim3 blk(256);                                                                           \
-        if (target == KLARA_TARGET_GAUSS_DIAG) {                                                       \
-            if (E == 2 && G == 64) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_GAUSS_DIAG, 2, 64); \
-            else if (E == 2) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_GAUSS_DIAG, 2, 0);       \
-            else if (E == 4 && G == 32) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_GAUSS_DIAG, 4, 32); \
-            else if (E == 4) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_GAUSS_DIAG, 4, 0);       \
-            else if (E == 8) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_GAUSS_DIAG, 8, 0);       \
-            else return hipErrorInvalidValue;                                                          \
-        } else if (target == KLARA_TARGET_LOGISTIC) {                                                  \
-            if (E == 2) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_LOGISTIC, 2, 0);              \
-            else if (E == 4) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_LOGISTIC, 4, 0);         \
-            else if (E == 8) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_LOGISTIC, 8, 0);         \
-            else if (E == 16) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_LOGISTIC, 16, 0);       \
-            else return hipErrorInvalidValue;                                                          \
-        } else if (target == KLARA_TARGET_HIER_NORMAL) {                                               \
-            if (E == 2) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_HIER_NORMAL, 2, 0);           \
-            else if (E == 4) KLARA_LAUNCH_T(SAMPLER, KLARA_TARGET_HIER_NORMAL, 4, 0);      \
-            else return hipErrorInvalidValue;                                                          \
-        } else return hipErrorInvalidValue;                                                            \
-        return hipGetLastError();                                                                      \
-    } while (0)
+// every group-layout launcher of the four base samplers (klara_{mh,mala,hmc,slice}.hip): E = 2 and 4 for every target, 8 for all but the hierarchical
+// one, 16 for the logistic regression alone; G != 0 names the diagonal target's one chain per wavefront (2, 64) and per half (4, 32)
+template <int S>
+static hipError_t launch_group(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
+{
+    const auto go = [&](auto t, auto e, auto g) {
+        return launch_transitions<S, decltype(t)::value, decltype(e)::value, decltype(g)::value>(p, kl, mode, grid, lds, st);
+    };
+    using G0 = KInt<0>;
+    if (target == KLARA_TARGET_GAUSS_DIAG) {
+        using T = KInt<KLARA_TARGET_GAUSS_DIAG>;
+        if (E == 2) return G == 64 ? go(T(), KInt<2>(), KInt<64>()) : go(T(), KInt<2>(), G0());
+        if (E == 4) return G == 32 ? go(T(), KInt<4>(), KInt<32>()) : go(T(), KInt<4>(), G0());
+        if (E == 8) return go(T(), KInt<8>(), G0());
+        return hipErrorInvalidValue;
+    }
+    if (target == KLARA_TARGET_LOGISTIC) return klara_pick<2, 4, 8, 16>(E, [&](auto e) { return go(KInt<KLARA_TARGET_LOGISTIC>(), e, G0()); });
+    if (target == KLARA_TARGET_HIER_NORMAL) return klara_pick<2, 4>(E, [&](auto e) { return go(KInt<KLARA_TARGET_HIER_NORMAL>(), e, G0()); });
+    return hipErrorInvalidValue;
+}

@@ -4,11 +4,8 @@
 
 hipError_t klara_launch_ram(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
 {
-    const dim3 blk(256);
     if (target != KLARA_TARGET_LOGISTIC || G != 1) return hipErrorInvalidValue;
-    if (E == 2) KLARA_LAUNCH_T(KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, 2, 0);
-    else if (E == 4) KLARA_LAUNCH_T(KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, 4, 0);
-    else if (E == 8) KLARA_LAUNCH_T(KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, 8, 0);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return klara_pick<2, 4, 8>(E, [&](auto e) {
+        return launch_transitions<KLARA_SAMPLER_RAM, KLARA_TARGET_LOGISTIC, decltype(e)::value, 0>(p, kl, mode, grid, lds, st);
+    });
 }

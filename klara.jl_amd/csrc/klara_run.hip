@@ -8,28 +8,17 @@
 
 thread_local hipFuncAttributes* klara_attr_query = nullptr;     // see klara_launch.h klara_go
 
-// ---- init kernels (group layout) instantiated here
-template <int TARGET, int E_, int G_>
-static hipError_t launch_init_one(const KParams& p, int needgrad, dim3 grid, size_t lds, hipStream_t st)
-{
-    if (lds > KLARA_LDS_DEFAULT_DYNAMIC) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_init<TARGET, E_, G_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((k_init<TARGET, E_, G_>), grid, dim3(256), lds, st, p, needgrad);
-    return hipGetLastError();
-}
-// E = 2 and 4 for every target, 8 for all but the hierarchical one, 16 for the logistic regression alone
+// ---- init kernels (group layout) instantiated here: E = 2 and 4 for every target, 8 for all but the hierarchical one, 16 for the logistic regression alone
 template <int TARGET>
 static hipError_t launch_init_t(const KParams& p, int E, int G, int needgrad, dim3 grid, size_t lds, hipStream_t st)
 {
+    const auto go = [&](auto e, auto g) { return klara_start(k_init<TARGET, decltype(e)::value, decltype(g)::value>, grid, dim3(256), lds, st, p, needgrad); };
     // (one chain per wavefront: diagonal-Gaussian jobs only — a run-time condition, so every target keeps the <2, 64> instantiation it has always had)
-    if (E == 2 && G == 64 && TARGET == KLARA_TARGET_GAUSS_DIAG) return launch_init_one<TARGET, 2, 64>(p, needgrad, grid, lds, st);
-    if (E == 2) return launch_init_one<TARGET, 2, 0>(p, needgrad, grid, lds, st);
-    if (E == 4) return launch_init_one<TARGET, 4, 0>(p, needgrad, grid, lds, st);
-    if constexpr (TARGET != KLARA_TARGET_HIER_NORMAL) { if (E == 8) return launch_init_one<TARGET, 8, 0>(p, needgrad, grid, lds, st); }
-    if constexpr (TARGET == KLARA_TARGET_LOGISTIC) { if (E == 16) return launch_init_one<TARGET, 16, 0>(p, needgrad, grid, lds, st); }
-    return hipErrorInvalidValue;
+    if (E == 2 && G == 64 && TARGET == KLARA_TARGET_GAUSS_DIAG) return go(KInt<2>(), KInt<64>());
+    const auto go0 = [&](auto e) { return go(e, KInt<0>()); };
+    if constexpr (TARGET == KLARA_TARGET_HIER_NORMAL) return klara_pick<2, 4>(E, go0);
+    else if constexpr (TARGET == KLARA_TARGET_LOGISTIC) return klara_pick<2, 4, 8, 16>(E, go0);
+    else return klara_pick<2, 4, 8>(E, go0);
 }
 
 __global__ void k_fill_tune(double* step, long long* acc, long long* prop, long long* tot, long long n,
@@ -199,11 +188,8 @@ extern "C" klara_status klara_init_state_normal(klara_handle* h)
     p.G = G; p.rs = 1;     // the init stream is drawn without the row split (same values, any layout)
     const long long cpw = 64 / G, waves = (h->d.nchains + cpw - 1) / cpw;
     const dim3 grid((unsigned)((waves + 3) / 4)), blk(256);
-    if (E == 2) hipLaunchKernelGGL((k_init_normal<2, 0>), grid, blk, 0, h->stream, p);
-    else if (E == 4) hipLaunchKernelGGL((k_init_normal<4, 0>), grid, blk, 0, h->stream, p);
-    else if (E == 8) hipLaunchKernelGGL((k_init_normal<8, 0>), grid, blk, 0, h->stream, p);
-    else hipLaunchKernelGGL((k_init_normal<16, 0>), grid, blk, 0, h->stream, p);
-    HIPCHK(hipGetLastError());
+    const hipError_t e0 = klara_pick<2, 4, 8, 16>(E, [&](auto e) { return klara_start(k_init_normal<decltype(e)::value, 0>, grid, blk, 0, h->stream, p); });
+    HIPCHK(e0);
     return init_common(h);
 }
 

@@ -80,13 +80,11 @@ extern "C" klara_status klara_selftest_math(int32_t device, int32_t op, int64_t 
     if (e == hipSuccess) e = hipMemcpy(di2, in2 ? in2 : in, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         if (op == 13 || op == 14) {
-            e = hipFuncSetAttribute((const void*)k_math_sctab, hipFuncAttributeMaxDynamicSharedMemorySize, KD_SCREM_BYTES);
             // (4,096 results per workgroup: the fill is a quarter of a workgroup's work, not all of it)
-            if (e == hipSuccess) hipLaunchKernelGGL(k_math_sctab, dim3((unsigned)((n + 255) / 256)), dim3(256), KD_SCREM_BYTES, 0, op, (long long)n, di, dout);
+            e = klara_start(k_math_sctab, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)KD_SCREM_BYTES, (hipStream_t)0, op, (long long)n, di, dout);
         } else {
-            hipLaunchKernelGGL(k_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (long long)n, di, di2, dout);
+            e = klara_start(k_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)0, op, (long long)n, di, di2, dout);
         }
-        if (e == hipSuccess) e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost);
     (void)dfree(di); (void)dfree(di2); (void)dfree(dout);

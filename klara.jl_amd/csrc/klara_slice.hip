@@ -4,5 +4,5 @@
 hipError_t klara_launch_slice(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
                             hipStream_t st)
 {
-    KLARA_DISPATCH_GROUP(k_transitions, KLARA_SAMPLER_SLICE);
+    return launch_group<KLARA_SAMPLER_SLICE>(p, kl, mode, target, E, G, grid, lds, st);
 }

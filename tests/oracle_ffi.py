@@ -109,7 +109,7 @@ def compile_user_target(src: str, ndims: int):
     return _user_libs[key]
 
 
-DIAGT_NP_MENU = (2, 3, 4, 5, 6, 7, 8)      # klara_launch.h KLARA_DIAGT_NP_MENU_DO
+DIAGT_NP_MENU = (2, 3, 4, 5, 6, 7, 8)      # klara_launch.h KLARA_DIAGT_NP_MENU
 DIAGT_Q = 8
 
 

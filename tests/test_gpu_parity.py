@@ -1811,6 +1811,60 @@ def test_kernel_attributes_and_launch_modes_queries():
         e.close()
 
 
+# the launcher families the test above does not reach: (case module, the family's smallest case, layout kind or None)
+QUERY_FAMILIES = {
+    "logit_rowsplit": ("cases", "mala_logit_d2", 2),
+    "hierarchical": ("cases", "mh_rats", 4),
+    "logit_mfma": ("cases", "hmc_logitm_d17_pooled", 5),
+    "dense_streamed": ("cases", "hmc_dense_d129_stream", 1),
+    "dense_split_d257": ("cases", "hmc_dense_d257_split_pooled", 6),
+    "smmala_logit": ("smmala", "logit_d1", None),
+    "ram_logit": ("ram", "logit_d1", None),
+    "closure_jit": ("cases", "custom_banana_mh", 0),
+}
+
+
+@pytest.mark.parametrize("family", list(QUERY_FAMILIES))
+def test_kernel_attribute_query_launches_nothing_on_every_launcher(family):
+    """Every launcher family honours the attribute query: on the family's smallest case cut to 128 chains and 2 transitions, klara_get_kernel_attributes
+    after the start state changes no state and counts no launch, reports a kernel (registers > 0), the 2 transitions that follow are the
+    oracle's / the reference's bit for bit (the case's own parity comparison), and the query answers the same afterwards."""
+    mod, name, kind = QUERY_FAMILIES[family]
+    if mod == "cases":
+        case = cases.make_case(name)
+    else:
+        import smmala_cases, ram_cases, test_gpu_smmala, test_gpu_ram
+        CM, TM = (smmala_cases, test_gpu_smmala) if mod == "smmala" else (ram_cases, test_gpu_ram)
+        case = CM.make(name)
+    case.update(nchains=128, nsteps=2, burnin=0, thinning=1)
+    if case["x0"] is not None:
+        case["x0"] = np.ascontiguousarray(np.resize(case["x0"], (128, case["target"].ndims)))     # (the case's own start rows, repeated)
+    if mod == "cases":
+        eng = K.Engine(**cases.engine_kwargs(case))
+        job = O.OracleJob(**cases.oracle_kwargs(case, layout=eng.layout()))
+    else:
+        eng = K.Engine(**CM.engine_kwargs(case, monitor=TM.HIST))
+        job = CM.ref_job(case, layout=eng.layout(), want_hist=True)
+    assert kind is None or eng.layout()[0] == kind, eng.layout()
+    assert kind != 1 or eng.layout()[2] > 32, eng.layout()          # (the streamed dense kernels: more than 32 elements per lane)
+    if case["x0"] is None:
+        eng.init_state_normal(); assert job.init_state_normal() == 0
+    else:
+        eng.set_state(case["x0"]); assert job.set_state(case["x0"]) == 0
+    before = [v.copy() for v in eng.state()]
+    a = eng.kernel_attributes(0, 2)
+    assert all(np.array_equal(v, w) for v, w in zip(eng.state(), before)), "the query changed the state"
+    assert tuple(eng.launch_modes()[0]) == (0, 0, 0)
+    assert a[0] > 0 and a[1] >= 0 and a[2] >= 0, a
+    eng.run(2); assert job.run(2) == 0
+    if mod == "cases":
+        _assert_same(eng, job, case)
+    else:
+        TM._assert_same(eng, job)
+    assert eng.kernel_attributes(0, 2) == a
+    eng.close()
+
+
 def test_pair_transposed_slice_sampler_moments():
     """Slice sampler on layout kind 3, MvNormal(mu, sigma) with D = 20, 16,384 chains x 60 transitions from x0 ~ N(0, I): the
     ensemble of final states has the target's mean and standard deviation (tolerance 5 standard errors, max over coordinates)."""
