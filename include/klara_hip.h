@@ -534,6 +534,15 @@ klara_status klara_selftest_mfma_f64(int32_t device, const double* A, const doub
 klara_status klara_selftest_mfma_f64_4x4x4(int32_t device, const double* A, const double* B, const double* C,
                                            double* D);
 
+/* Self-test hook: the chain statistics kernels on a caller's series.  hist holds ncols (>= 2) saved steps of nchains x ndims series as the device keeps a
+ * value history (column t at hist + t * nchains * ndims).  Post-hoc estimators over the whole history (what klara_get_chain_mcvar / _ipse run) with lag
+ * window maxlag (1..127) and batch length batchlen: iid, bm, imse, ipse; and the streaming autocovariance path (what a job with klara_desc.acov_maxlag =
+ * maxlag runs after every launch, then klara_get_chain_acov_mcvar) fed launch by launch — launch j brings splits[j] saved steps, the splits sum to ncols:
+ * stream_imse, stream_ipse.  Every output is nchains x ndims and may be NULL.  Tests compare them with exact rational arithmetic. */
+klara_status klara_selftest_chain_stats(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t maxlag,
+                                        int64_t batchlen, int32_t nsplits, const int64_t* splits, double* iid, double* bm, double* imse,
+                                        double* ipse, double* stream_imse, double* stream_ipse);
+
 /* Self-test hook, no device needed: the launches a sequence of klara_run calls of the given lengths issues on a fresh job of
  * this descriptor — transitions per launch k[i], the save-rule bookkeeping handed to the kernels (columns already saved,
  * thinning phase of the launch's first post-burn-in transition) and flags (bit 0: a pooled tuner update follows, bit 1: a batch

@@ -409,13 +409,15 @@ def _mcvar_pair(chains: MuvChains, vtype: str, batchlen: int, maxlag: Optional[i
 def chain_ess(chains: MuvChains, vtype: str = "imse", batchlen: int = 100, maxlag: Optional[int] = None) -> np.ndarray:
     """ess(s, vtype) = n * mcvar_iid / mcvar_vtype (stats/convergence/ess.jl:3) for every chain and dimension."""
     iid, v = _mcvar_pair(chains, vtype, batchlen, maxlag)
-    return chains.n * iid / v
+    with np.errstate(invalid="ignore", divide="ignore"):       # (a series that never moved: 0 / 0 = NaN, as in the reference's arithmetic)
+        return chains.n * iid / v
 
 
 def chain_iact(chains: MuvChains, vtype: str = "imse", batchlen: int = 100, maxlag: Optional[int] = None) -> np.ndarray:
     """iact(s, vtype) = mcvar_vtype / mcvar_iid (stats/convergence/iact.jl:3) for every chain and dimension."""
     iid, v = _mcvar_pair(chains, vtype, batchlen, maxlag)
-    return v / iid
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return v / iid
 
 
 def _zv_engine(chains: MuvChains, name: str):

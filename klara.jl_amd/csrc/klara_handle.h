@@ -113,7 +113,15 @@ hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts);
 
 // ---- klara_monitors.hip: what klara_run_async enqueues behind a launch, and the pooled sums the gather calls reduce over the ranks
 hipError_t launch_bm_close(klara_handle* h, int nparts);
-hipError_t launch_acov_update(klara_handle* h, long long col0, long long m);
+// streaming autocovariances on plain buffers (the job path and klara_selftest_chain_stats run the same kernels): columns [col0, col0 + m) of hist update
+// S / head / tail ([W][nd]) and total ([nd]) after n_before samples (near: 32 nd scratch, W > 32 only); then Geyer's estimators from them
+hipError_t launch_acov_update(hipStream_t stream, const double* hist, double* S, double* head, double* tail, double* near, double* total,
+                              long long n_before, int W, long long nd, long long col0, long long m);
+hipError_t launch_acov_finalize(hipStream_t stream, const double* S, const double* head, const double* tail, const double* total,
+                                long long n, int W, long long nd, double* imse, double* ipse);
+// the post-hoc estimators over a stored history (k_chain_stats), every output optional (device, N * D each)
+hipError_t launch_chain_stats(hipStream_t stream, const double* hist, long long ncols, long long N, int D, long long batchlen, long long maxlag,
+                              double* iid, double* bm, double* imse, double* ipse);
 hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);
 hipError_t pool_moments_async(klara_handle* h, double* out);
 

@@ -40,8 +40,16 @@ hipError_t launch_bm_close(klara_handle* h, int nparts)
 }
 
 // ---- streaming autocovariances (klara_desc.acov_maxlag): after every launch the samples it saved — columns [col0, col0 + m) of
-// the value ring — update, for every (chain, dimension) series, the lagged cross-products S_k = sum_t x_t x_(t-k), k < W, the total,
-// the first W samples and the last W samples (most recent first).  One thread per series, S and the window in registers.
+// the value ring — update, for every (chain, dimension) series, the lagged cross-products S_k = sum_t z_t z_(t-k), k < W, the total of z
+// and the last W values of z (most recent first), where z_t = x_t - pivot and the pivot is the series' first saved sample; the first W
+// samples are kept as they are (head[0] is the pivot).  The autocovariance does not depend on a shift, and sums of z lose
+// ((pivot - mean) / sd)^2 digits where sums of x lose (mean / sd)^2: a chain at 1e6 +- 1 keeps its ESS.  One thread per series, S and
+// the window in registers.
+__device__ inline double acov_pivot(const double* __restrict__ hist, long long col0, long long n_before, long long nd,
+                                    const double* __restrict__ head, long long i)
+{
+    return n_before == 0 ? hist[col0 * nd + i] : head[i];
+}
 template <int WMAX>
 __global__ __launch_bounds__(256) void k_acov_update(const double* __restrict__ hist, long long col0, int m, long long n_before, int W,
                                                      long long nd, double* __restrict__ S, double* __restrict__ head,
@@ -49,16 +57,17 @@ __global__ __launch_bounds__(256) void k_acov_update(const double* __restrict__ 
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nd) return;
+    const double pivot = acov_pivot(hist, col0, n_before, nd, head, i);
     double s[WMAX], win[WMAX];
 #pragma unroll
     for (int k = 0; k < WMAX; ++k) { s[k] = k < W ? S[(long long)k * nd + i] : 0.0; win[k] = k < W ? tail[(long long)k * nd + i] : 0.0; }
     double tot = total[i];
     for (int j = 0; j < m; ++j) {
-        const double x = hist[(col0 + j) * nd + i];
+        const double raw = hist[(col0 + j) * nd + i], x = raw - pivot;
         s[0] = s[0] + x * x;
 #pragma unroll
         for (int k = 1; k < WMAX; ++k) s[k] = s[k] + x * win[k - 1];        // (win holds zeros where no sample exists yet)
-        if (n_before + j < W) head[(n_before + j) * nd + i] = x;
+        if (n_before + j < W) head[(n_before + j) * nd + i] = raw;
 #pragma unroll
         for (int k = WMAX - 1; k > 0; --k) win[k] = win[k - 1];
         win[0] = x;
@@ -69,25 +78,27 @@ __global__ __launch_bounds__(256) void k_acov_update(const double* __restrict__ 
     total[i] = tot;
 }
 
-// Lags 32 b .. 32 b + 31 (b >= 1; windows beyond 32 lags, klara_desc.acov_maxlag up to 127): the cross-products of x with its own history delayed by
-// 32 b samples, y_j = x_(j - 32 b) — the same 32-lag update on the pair (x, y): S_(32b + r) += x_j y_(j - r).  y comes from the launch's own
-// columns where j >= 32 b and from the tail kept by the earlier launches (tail[k] = the (k + 1)-th most recent sample before this launch)
-// otherwise; the passes of the higher blocks run BEFORE the lag-0 pass rewrites the tail.
-__global__ __launch_bounds__(256) void k_acov_update_block(const double* __restrict__ hist, long long col0, int m, int b, int W, long long nd,
-                                                           double* __restrict__ S, const double* __restrict__ tail)
+// Lags 32 b .. 32 b + 31 (b >= 1; windows beyond 32 lags, klara_desc.acov_maxlag up to 127): the cross-products of z with its own history delayed by
+// 32 b samples, y_j = z_(j - 32 b) — the same 32-lag update on the pair (z, y): S_(32b + r) += z_j y_(j - r).  y comes from the launch's own
+// columns where j >= 32 b and from the tail kept by the earlier launches (tail[k] = the (k + 1)-th most recent z before this launch)
+// otherwise; the passes of the higher blocks run BEFORE the lag-0 pass rewrites the tail (and, in a job's first launch, before it writes head[0]).
+__global__ __launch_bounds__(256) void k_acov_update_block(const double* __restrict__ hist, long long col0, int m, long long n_before, int b, int W,
+                                                           long long nd, double* __restrict__ S, const double* __restrict__ head,
+                                                           const double* __restrict__ tail)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nd) return;
+    const double pivot = acov_pivot(hist, col0, n_before, nd, head, i);
     const int k0 = 32 * b;
     double s[32], win[32];
 #pragma unroll
     for (int r = 0; r < 32; ++r) {
         s[r] = k0 + r < W ? S[(long long)(k0 + r) * nd + i] : 0.0;
-        win[r] = k0 + r < W ? tail[(long long)(k0 + r) * nd + i] : 0.0;            // y_(-1-r) = x_(-1-r-k0)   (zeros where no sample exists yet)
+        win[r] = k0 + r < W ? tail[(long long)(k0 + r) * nd + i] : 0.0;            // y_(-1-r) = z_(-1-r-k0)   (zeros where no sample exists yet)
     }
     for (int j = 0; j < m; ++j) {
-        const double x = hist[(col0 + j) * nd + i];
-        const double y = j >= k0 ? hist[(col0 + j - k0) * nd + i] : tail[(long long)(k0 - j - 1) * nd + i];
+        const double x = hist[(col0 + j) * nd + i] - pivot;
+        const double y = j >= k0 ? hist[(col0 + j - k0) * nd + i] - pivot : tail[(long long)(k0 - j - 1) * nd + i];
         s[0] = s[0] + x * y;
 #pragma unroll
         for (int r = 1; r < 32; ++r) s[r] = s[r] + x * win[r - 1];
@@ -98,43 +109,44 @@ __global__ __launch_bounds__(256) void k_acov_update_block(const double* __restr
 #pragma unroll
     for (int r = 0; r < 32; ++r) if (k0 + r < W) S[(long long)(k0 + r) * nd + i] = s[r];
 }
-// ... and the tail of a window beyond 32 lags, after the lag-0 pass (which has moved entries 0..31): entries 32 .. W-1 take the samples that are now
-// 33 .. W back — from this launch's columns or from the old tail, moved from the far end so that nothing is overwritten before it is read
+// ... and the tail of a window beyond 32 lags, after the lag-0 pass (which has moved entries 0..31 and written head[0]): entries 32 .. W-1 take the
+// values of z that are now 33 .. W back — from this launch's columns or from the old tail, moved from the far end so that nothing is overwritten before it is read
 __global__ __launch_bounds__(256) void k_acov_tail_far(const double* __restrict__ hist, long long col0, int m, int W, long long nd,
-                                                       double* __restrict__ tail, const double* __restrict__ old_near)
+                                                       const double* __restrict__ head, double* __restrict__ tail, const double* __restrict__ old_near)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nd) return;
-    for (int k = W - 1; k >= 32; --k) {                     // new tail[k] = x_(m-1-k): a column of this launch, or the old tail[k - m]
+    const double pivot = head[i];
+    for (int k = W - 1; k >= 32; --k) {                     // new tail[k] = z_(m-1-k): a column of this launch, or the old tail[k - m]
         double v;
-        if (k < m) v = hist[(col0 + m - 1 - k) * nd + i];
+        if (k < m) v = hist[(col0 + m - 1 - k) * nd + i] - pivot;
         else if (k - m >= 32) v = tail[(long long)(k - m) * nd + i];            // (an entry further down: not yet overwritten — k descends)
         else v = old_near[(long long)(k - m) * nd + i];                          // (one of the first 32 entries as they were BEFORE the lag-0 pass)
         tail[(long long)k * nd + i] = v;
     }
 }
 
-hipError_t launch_acov_update(klara_handle* h, long long col0, long long m)
+// (the buffers, not the handle: klara_run and klara_selftest_chain_stats launch the same kernels through this one function)
+hipError_t launch_acov_update(hipStream_t stream, const double* hist, double* S, double* head, double* tail, double* near, double* total,
+                              long long n_before, int W, long long nd, long long col0, long long m)
 {
-    const long long nd = (long long)h->d.nchains * h->d.ndims;
     const dim3 grid((unsigned)((nd + 255) / 256)), blk(256);
-    const int W = h->acov_W;
     if (W > 32) {       // windows beyond 32 lags: the higher lag blocks first (they read the tail as the earlier launches left it)
         for (int b = (W - 1) / 32; b >= 1; --b)
-            hipLaunchKernelGGL(k_acov_update_block, grid, blk, 0, h->stream, h->hist, col0, (int)m, b, W, nd, h->acov_S, h->acov_tail);
+            hipLaunchKernelGGL(k_acov_update_block, grid, blk, 0, stream, hist, col0, (int)m, n_before, b, W, nd, S, head, tail);
         // (the lag-0 pass below rewrites tail[0..31]; the far tail needs their old values when fewer than 32 samples arrive: keep a copy)
-        hipError_t e = hipMemcpyAsync(h->acov_near, h->acov_tail, (size_t)32 * nd * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        hipError_t e = hipMemcpyAsync(near, tail, (size_t)32 * nd * sizeof(double), hipMemcpyDeviceToDevice, stream);
         if (e != hipSuccess) return e;
     }
-    if (W <= 8) hipLaunchKernelGGL((k_acov_update<8>), grid, blk, 0, h->stream, h->hist, col0, (int)m, h->acov_n, W, nd, h->acov_S, h->acov_head, h->acov_tail, h->acov_total);
-    else if (W <= 16) hipLaunchKernelGGL((k_acov_update<16>), grid, blk, 0, h->stream, h->hist, col0, (int)m, h->acov_n, W, nd, h->acov_S, h->acov_head, h->acov_tail, h->acov_total);
-    else hipLaunchKernelGGL((k_acov_update<32>), grid, blk, 0, h->stream, h->hist, col0, (int)m, h->acov_n, W, nd, h->acov_S, h->acov_head, h->acov_tail, h->acov_total);
-    if (W > 32) hipLaunchKernelGGL(k_acov_tail_far, grid, blk, 0, h->stream, h->hist, col0, (int)m, W, nd, h->acov_tail, h->acov_near);
+    if (W <= 8) hipLaunchKernelGGL((k_acov_update<8>), grid, blk, 0, stream, hist, col0, (int)m, n_before, W, nd, S, head, tail, total);
+    else if (W <= 16) hipLaunchKernelGGL((k_acov_update<16>), grid, blk, 0, stream, hist, col0, (int)m, n_before, W, nd, S, head, tail, total);
+    else hipLaunchKernelGGL((k_acov_update<32>), grid, blk, 0, stream, hist, col0, (int)m, n_before, W, nd, S, head, tail, total);
+    if (W > 32) hipLaunchKernelGGL(k_acov_tail_far, grid, blk, 0, stream, hist, col0, (int)m, W, nd, head, tail, near);
     return hipGetLastError();
 }
 
-// autocov(v, 0:maxlag) of StatsBase (demean = true) from the streamed sums: with m = total / n,
-//   n acv_k = sum_(t>k) (x_t - m)(x_(t-k) - m) = S_k - m [(total - first k) + (total - last k)] + (n - k) m^2,
+// autocov(v, 0:maxlag) of StatsBase (demean = true) from the streamed sums of z = x - pivot (pivot = head[0]): with m = total / n,
+//   n acv_k = sum_(t>k) (z_t - m)(z_(t-k) - m) = S_k - m [(total - first k) + (total - last k)] + (n - k) m^2,
 // then Geyer's truncation (mcvar.jl:75-105 imse, :137-158 ipse).
 __global__ __launch_bounds__(256) void k_acov_finalize(const double* __restrict__ S, const double* __restrict__ head, const double* __restrict__ tail,
                                                        const double* __restrict__ total, long long n, int W, long long nd,
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(256) void k_acov_finalize(const double* __restrict_
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nd) return;
-    const double tot = total[i], mean = tot / (double)n;
+    const double tot = total[i], mean = tot / (double)n, pivot = head[i];
     const long long maxlag = (W - 1) < (n - 1) ? (W - 1) : (n - 1);
     const long long kk = (maxlag - 1) / 2;                       // floor((maxlag-1)/2), mcvar.jl:76
     double hs = 0.0, ts = 0.0, acv0 = 0.0, gsum_m = 0.0, gsum_p = 0.0, gprev = 0.0;
@@ -151,11 +163,11 @@ __global__ __launch_bounds__(256) void k_acov_finalize(const double* __restrict_
         double pair = 0.0;
         for (int h2 = 0; h2 < 2; ++h2) {
             const long long k = 2 * j + h2;
-            // hs / ts = sum of the first / last k samples
+            // hs / ts = sum of the first / last k values of z
             const double a = (S[k * nd + i] - mean * ((tot - ts) + (tot - hs)) + (double)(n - k) * mean * mean) / (double)n;
             if (k == 0) acv0 = a;
             pair += a;
-            hs += head[k * nd + i]; ts += tail[k * nd + i];
+            hs += head[k * nd + i] - pivot; ts += tail[k * nd + i];
         }
         if (pair <= 0.0) { stop = true; break; }                 // m = j (mcvar.jl:87-90)
         gsum_p += pair;
@@ -167,6 +179,14 @@ __global__ __launch_bounds__(256) void k_acov_finalize(const double* __restrict_
     if (ipse) ipse[i] = (-acv0 + 2.0 * gsum_p) / (double)n;
 }
 
+// Geyer's estimators from the streamed sums of n samples into imse / ipse (device, nd each; either may be null), on `stream`
+hipError_t launch_acov_finalize(hipStream_t stream, const double* S, const double* head, const double* tail, const double* total,
+                                long long n, int W, long long nd, double* imse, double* ipse)
+{
+    hipLaunchKernelGGL(k_acov_finalize, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, stream, S, head, tail, total, n, W, nd, imse, ipse);
+    return hipGetLastError();
+}
+
 extern "C" klara_status klara_get_chain_acov_mcvar(klara_handle* h, double* mcvar_imse, double* mcvar_ipse, int64_t* nsamples_out)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;
@@ -175,9 +195,8 @@ extern "C" klara_status klara_get_chain_acov_mcvar(klara_handle* h, double* mcva
     const long long nd = (long long)h->d.nchains * h->d.ndims;
     double* buf = nullptr;
     HIPCHK(dalloc(&buf, (size_t)2 * nd));
-    hipLaunchKernelGGL(k_acov_finalize, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, h->stream, h->acov_S, h->acov_head, h->acov_tail,
-                       h->acov_total, h->acov_n, h->acov_W, nd, mcvar_imse ? buf : nullptr, mcvar_ipse ? buf + nd : nullptr);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_acov_finalize(h->stream, h->acov_S, h->acov_head, h->acov_tail, h->acov_total, h->acov_n, h->acov_W, nd,
+                                        mcvar_imse ? buf : nullptr, mcvar_ipse ? buf + nd : nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && mcvar_imse) e = hipMemcpy(mcvar_imse, buf, nd * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && mcvar_ipse) e = hipMemcpy(mcvar_ipse, buf + nd, nd * sizeof(double), hipMemcpyDeviceToHost);
@@ -537,25 +556,29 @@ __global__ __launch_bounds__(256) void k_chain_stats(const double* __restrict__ 
     if (i >= N * D) return;
     const double* v = hist + i;                 // v[t * stride]
     const long long stride = N * D, n = ncols;
+    // Deviations as (v_t - v_0) - mean(v - v_0): the first difference is exact or nearly so, and the mean of the differences carries an error of
+    // n u |v - v_0| where the mean of v carries n u |v| — which, at a mean of 1e6 sd, already costs 1e-9 of imse (profiles/chain_stats_accuracy.txt).
+    // A series that never moves has every deviation exactly 0 (0 / 0 = NaN for its ESS, as in the reference's arithmetic, not a ratio of noise).
+    const double v0 = v[0];
     double m = 0.0;
-    for (long long t = 0; t < n; ++t) m += v[t * stride];
+    for (long long t = 0; t < n; ++t) m += v[t * stride] - v0;
     m /= (double)n;
     double acv0 = 0.0;
-    for (long long t = 0; t < n; ++t) { const double z = v[t * stride] - m; acv0 += z * z; }
+    for (long long t = 0; t < n; ++t) { const double z = (v[t * stride] - v0) - m; acv0 += z * z; }
     if (iid) iid[i] = (n > 1) ? acv0 / (double)(n - 1) / (double)n : NAN;
     if (bm) {
         const long long nb = batchlen > 0 ? n / batchlen : 0;
         if (nb > 1) {
-            double sb = 0.0, sb2 = 0.0;                       // two-pass over batch means for stability
+            double sb = 0.0, sb2 = 0.0;                       // two-pass over the batch means (of v - v_0: the variance does not depend on a shift)
             for (long long b = 0; b < nb; ++b) {
                 double a = 0.0;
-                for (long long t = 0; t < batchlen; ++t) a += v[(b * batchlen + t) * stride];
+                for (long long t = 0; t < batchlen; ++t) a += v[(b * batchlen + t) * stride] - v0;
                 sb += a / (double)batchlen;
             }
             const double mb = sb / (double)nb;
             for (long long b = 0; b < nb; ++b) {
                 double a = 0.0;
-                for (long long t = 0; t < batchlen; ++t) a += v[(b * batchlen + t) * stride];
+                for (long long t = 0; t < batchlen; ++t) a += v[(b * batchlen + t) * stride] - v0;
                 const double dm = a / (double)batchlen - mb;
                 sb2 += dm * dm;
             }
@@ -570,8 +593,8 @@ __global__ __launch_bounds__(256) void k_chain_stats(const double* __restrict__ 
             double a0 = 0.0, a1 = 0.0;
             const long long l0 = 2 * j, l1 = 2 * j + 1;
             if (j == 0) a0 = acv0;
-            else for (long long t = 0; t + l0 < n; ++t) a0 += (v[t * stride] - m) * (v[(t + l0) * stride] - m);
-            for (long long t = 0; t + l1 < n; ++t) a1 += (v[t * stride] - m) * (v[(t + l1) * stride] - m);
+            else for (long long t = 0; t + l0 < n; ++t) a0 += ((v[t * stride] - v0) - m) * ((v[(t + l0) * stride] - v0) - m);
+            for (long long t = 0; t + l1 < n; ++t) a1 += ((v[t * stride] - v0) - m) * ((v[(t + l1) * stride] - v0) - m);
             double gj = (a0 + a1) / (double)n;
             if (gj <= 0.0) break;                             // m = j (mcvar.jl:87-90)
             gsum_p += gj;                                     // initial positive sequence (mcvar.jl:137-158): no monotone step
@@ -583,6 +606,13 @@ __global__ __launch_bounds__(256) void k_chain_stats(const double* __restrict__ 
     }
 }
 
+hipError_t launch_chain_stats(hipStream_t stream, const double* hist, long long ncols, long long N, int D, long long batchlen, long long maxlag,
+                              double* iid, double* bm, double* imse, double* ipse)
+{
+    hipLaunchKernelGGL(k_chain_stats, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, stream, hist, ncols, N, D, batchlen, maxlag, iid, bm, imse, ipse);
+    return hipGetLastError();
+}
+
 extern "C" klara_status klara_get_chain_mcvar(klara_handle* h, int64_t batchlen, int64_t maxlag, double* mcvar_iid,
                                               double* mcvar_bm, double* mcvar_imse)
 {
@@ -592,10 +622,8 @@ extern "C" klara_status klara_get_chain_mcvar(klara_handle* h, int64_t batchlen,
     const long long N = h->d.nchains, D = h->d.ndims, total = N * D;
     double* buf = nullptr;
     HIPCHK(dalloc(&buf, (size_t)3 * total));
-    hipLaunchKernelGGL(k_chain_stats, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->hist,
-                       (long long)h->nsaved, N, (int)D, (long long)batchlen, (long long)(maxlag > 0 ? maxlag : h->nsaved - 1),
-                       mcvar_iid ? buf : nullptr, mcvar_bm ? buf + total : nullptr, mcvar_imse ? buf + 2 * total : nullptr, (double*)nullptr);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_chain_stats(h->stream, h->hist, (long long)h->nsaved, N, (int)D, (long long)batchlen, (long long)(maxlag > 0 ? maxlag : h->nsaved - 1),
+                                      mcvar_iid ? buf : nullptr, mcvar_bm ? buf + total : nullptr, mcvar_imse ? buf + 2 * total : nullptr, nullptr);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess && mcvar_iid) e = hipMemcpy(mcvar_iid, buf, total * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess && mcvar_bm) e = hipMemcpy(mcvar_bm, buf + total, total * sizeof(double), hipMemcpyDeviceToHost);
@@ -612,9 +640,8 @@ extern "C" klara_status klara_get_chain_mcvar_ipse(klara_handle* h, int64_t maxl
     const long long N = h->d.nchains, D = h->d.ndims, total = N * D;
     double* buf = nullptr;
     HIPCHK(dalloc(&buf, (size_t)total));
-    hipLaunchKernelGGL(k_chain_stats, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, h->hist, (long long)h->nsaved, N, (int)D, 0ll,
-                       (long long)(maxlag > 0 ? maxlag : h->nsaved - 1), (double*)nullptr, (double*)nullptr, (double*)nullptr, buf);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_chain_stats(h->stream, h->hist, (long long)h->nsaved, N, (int)D, 0ll, (long long)(maxlag > 0 ? maxlag : h->nsaved - 1),
+                                      nullptr, nullptr, nullptr, buf);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e == hipSuccess) e = hipMemcpy(mcvar_ipse, buf, total * sizeof(double), hipMemcpyDeviceToHost);
     (void)dfree(buf);

@@ -532,7 +532,8 @@ extern "C" klara_status klara_run_async(klara_handle* h, int64_t nsteps)
         }
         if (err == hipSuccess && pl.bm_close_after) err = launch_bm_close(h, nparts);   // (reads h->bm_count: batches closed before this one)
         if (err == hipSuccess && h->acov_S && pl.saved > 0) {                   // streaming autocovariances consume the launch's samples
-            err = launch_acov_update(h, pl.save_col0, pl.saved);
+            err = launch_acov_update(h->stream, h->hist, h->acov_S, h->acov_head, h->acov_tail, h->acov_near, h->acov_total, h->acov_n, h->acov_W,
+                                     (long long)d.nchains * d.ndims, pl.save_col0, pl.saved);
             h->acov_n += pl.saved;
         }
         if (err != hipSuccess) break;

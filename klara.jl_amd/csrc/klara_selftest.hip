@@ -1,4 +1,5 @@
-// klara_selftest.hip — self tests: the device's random blocks, math, normals and matrix-core probes as the kernels see them; compile checks of user targets.
+// klara_selftest.hip — self tests: the device's random blocks, math, normals and matrix-core probes as the kernels see them; the chain statistics kernels on a
+// caller's series; compile checks of user targets.
 #include <rocrand/rocrand_kernel.h>
 #include "klara_handle.h"
 
@@ -175,6 +176,53 @@ extern "C" klara_status klara_selftest_mfma_f64_4x4x4(int32_t device, const doub
     if (e == hipSuccess) e = klara_launch_mfma4_probe(buf, buf + 64, buf + 128, buf + 192, 0);
     if (e == hipSuccess) e = hipMemcpy(D, buf + 192, 64 * sizeof(double), hipMemcpyDeviceToHost);
     (void)dfree(buf);
+    return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+// The chain statistics kernels on a caller's series: k_chain_stats over the uploaded history, then the streaming autocovariances launch by launch
+// (launch_acov_update with col0 running through the history, as klara_run issues them; an empty launch is skipped there too) and their finalize step.
+extern "C" klara_status klara_selftest_chain_stats(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t maxlag,
+                                                   int64_t batchlen, int32_t nsplits, const int64_t* splits, double* iid, double* bm, double* imse,
+                                                   double* ipse, double* stream_imse, double* stream_ipse)
+{
+    if (!hist || !splits || nchains <= 0 || ndims <= 0 || ncols < 2 || maxlag < 1 || maxlag > 127 || nsplits <= 0 || batchlen < 0) return KLARA_ERR_INVALID_ARG;
+    long long sum = 0;
+    for (int j = 0; j < nsplits; ++j) {
+        if (splits[j] < 0 || splits[j] > 0x7fffffffll) return KLARA_ERR_INVALID_ARG;
+        sum += splits[j];
+    }
+    if (sum != ncols) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    const long long nd = (long long)nchains * ndims;
+    const int W = maxlag + 1;
+    const size_t ws = (size_t)W * nd;
+    double *dh = nullptr, *S = nullptr, *head = nullptr, *tail = nullptr, *near = nullptr, *total = nullptr, *out = nullptr;
+    hipError_t e = dalloc(&dh, (size_t)ncols * nd);
+    if (e == hipSuccess) e = dalloc(&S, ws);
+    if (e == hipSuccess) e = dalloc(&head, ws);
+    if (e == hipSuccess) e = dalloc(&tail, ws);
+    if (e == hipSuccess && W > 32) e = dalloc(&near, (size_t)32 * nd);
+    if (e == hipSuccess) e = dalloc(&total, (size_t)nd);
+    if (e == hipSuccess) e = dalloc(&out, (size_t)6 * nd);
+    if (e == hipSuccess) e = hipMemcpy(dh, hist, (size_t)ncols * nd * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(S, 0, ws * sizeof(double));           // (what klara_set_state / klara_reset leave)
+    if (e == hipSuccess) e = hipMemset(head, 0, ws * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(tail, 0, ws * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(total, 0, (size_t)nd * sizeof(double));
+    const hipStream_t st = 0;
+    if (e == hipSuccess) e = launch_chain_stats(st, dh, (long long)ncols, (long long)nchains, (int)ndims, (long long)batchlen, (long long)maxlag,
+                                                out, out + nd, out + 2 * nd, out + 3 * nd);
+    long long col0 = 0;
+    for (int j = 0; j < nsplits && e == hipSuccess; ++j) {
+        if (splits[j] > 0) e = launch_acov_update(st, dh, S, head, tail, near, total, col0, W, nd, col0, (long long)splits[j]);
+        col0 += splits[j];
+    }
+    if (e == hipSuccess) e = launch_acov_finalize(st, S, head, tail, total, (long long)ncols, W, nd, out + 4 * nd, out + 5 * nd);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    double* dst[6] = { iid, bm, imse, ipse, stream_imse, stream_ipse };
+    for (int k = 0; k < 6 && e == hipSuccess; ++k)
+        if (dst[k]) e = hipMemcpy(dst[k], out + (size_t)k * nd, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost);
+    (void)dfree(dh); (void)dfree(S); (void)dfree(head); (void)dfree(tail); if (near) (void)dfree(near); (void)dfree(total); (void)dfree(out);
     return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
 }
 
