@@ -520,11 +520,14 @@ KD_FN void kd_sincos_rem(uint64_t uu_bits, double* sy_out, double* dc_out)
     *sy_out = kd_fma(y * z, kd_fma(z, kd_fma(z, S3, S2), S1), y);               /* sin y */
     *dc_out = z * kd_fma(z, kd_fma(z, C3, C2), -0.5);                           /* cos y - 1 */
 }
-KD_FN void kd_sincos_rotate(uint32_t j, double sy, double dc, double* sn, double* cs)
+KD_FN void kd_sincos_rotate_entry(double C, double S, double sy, double dc, double* sn, double* cs)
 {
-    const double C = KD_SCTAB(2 * j), S = KD_SCTAB(2 * j + 1);
     *cs = kd_fma(-S, sy, kd_fma(C, dc, C));
     *sn = kd_fma(C, sy, kd_fma(S, dc, S));
+}
+KD_FN void kd_sincos_rotate(uint32_t j, double sy, double dc, double* sn, double* cs)
+{
+    kd_sincos_rotate_entry(KD_SCTAB(2 * j), KD_SCTAB(2 * j + 1), sy, dc, sn, cs);
 }
 KD_FN void kd_sincos2pi_bits(uint64_t uu_bits, double* sn, double* cs)
 {
@@ -640,6 +643,39 @@ KD_FN void kd_normal_pair_w(uint32_t wa, uint32_t wb, double* z0, double* z1, do
 KD_FN void kd_normal_pair_w(uint32_t wa, uint32_t wb, double* z0, double* z1, double* u1_out, double* logu1_out)
 {
     kd_normal_pair_w_t<false>(wa, wb, z0, z1, u1_out, logu1_out);
+}
+#endif
+/* kd_normal_pair_w_t<true> split at its table reads.  The three addresses of a pair depend on its two Philox words alone — the log table's bin
+ * on the bits of u1, the rotation entry and the remainder entry on wb — and on neither the log nor the radius: kd_normal_pair_issue forms them
+ * and starts the three 16-byte LDS reads, kd_normal_pair_finish is everything that consumes an entry (kd_log_u01_finish, the radius,
+ * kd_sincos_rotate_entry).  A caller puts independent work between the two, so that the round trips run under it instead of stalling the
+ * wavefront (klara_diagt.h pair_issue / pair_finish); the two in sequence are kd_normal_pair_w_t<true>: the same operations on the same
+ * values, the same bits. */
+#if defined(__HIPCC__)
+typedef struct {
+    kd_screm_t lg, rot, rem;         /* raw entries: (1/c, log c) of the log bin, (C, S) of the table angle, (sin y, cos y - 1) of the remainder */
+    double z; int k; double u1;      /* the reduced argument and exponent of u1 (kd_log_u01_reduce), u1 itself */
+} kd_pair_reads;
+__device__ __forceinline__ void kd_normal_pair_issue(uint32_t wa, uint32_t wb, kd_pair_reads* r)
+{
+    uint32_t i;
+    r->u1 = kd_u44(wa, wb);
+    kd_log_u01_reduce(r->u1, &i, &r->k, &r->z);
+    const uint32_t k = wb >> 12;
+    r->lg = *(const kd_screm_t*)&KD_LOGTAB(2 * i);
+    r->rot = *(const kd_screm_t*)&KD_SCTAB(2 * (k >> 12));
+    r->rem = kd_screm_lds[k & (KD_SCREM_ENTRIES - 1u)];
+}
+__device__ __forceinline__ void kd_normal_pair_finish(const kd_pair_reads* r, double* z0, double* z1, double* u1_out, double* logu1_out)
+{
+    const double lg = kd_log_u01_finish(r->z, r->k, r->lg.x, r->lg.y);
+    const double rad = kd_sqrt_radicand(-2.0 * lg);
+    double sn, cs;
+    kd_sincos_rotate_entry(r->rot.x, r->rot.y, r->rem.x, r->rem.y, &sn, &cs);
+    *z0 = rad * cs;
+    *z1 = rad * sn;
+    *u1_out = r->u1;
+    *logu1_out = lg;
 }
 #endif
 

@@ -315,12 +315,11 @@ template <int Q> struct PairShare {
     static constexpr bool second(int p) { return STEP != 0 && ((p / (STEP ? STEP : 1)) & 1) != 0; }
 };
 // SCTAB: the angle's remainder terms come from the workgroup's table (detmath.h kd_normal_pair_w_t<true>) — the same bits.
-template <int NP, int Q, bool SCTAB = false>
-__device__ __forceinline__ void pair_normals(const PairCtx<NP, Q>& c, unsigned long long seed, unsigned long long gchain,
-                                             unsigned long long t, int p, uint32_t (&stash)[4], double& z0, double& z1, double& u1, double& lg1)
+template <int NP, int Q>
+__device__ __forceinline__ void pair_words(const PairCtx<NP, Q>& c, unsigned long long seed, unsigned long long gchain,
+                                           unsigned long long t, int p, uint32_t (&stash)[4], uint32_t& wa, uint32_t& wb)
 {
     constexpr int STEP = PairShare<Q>::STEP, S1 = STEP ? STEP : 1;
-    uint32_t wa, wb;
     if (PairShare<Q>::second(p)) {
         wa = stash[2 * (p % S1)]; wb = stash[2 * (p % S1) + 1];
     } else {
@@ -335,8 +334,36 @@ __device__ __forceinline__ void pair_normals(const PairCtx<NP, Q>& c, unsigned l
             wa = hb ? b.z : b.x; wb = hb ? b.w : b.y;
         }
     }
+}
+template <int NP, int Q, bool SCTAB = false>
+__device__ __forceinline__ void pair_normals(const PairCtx<NP, Q>& c, unsigned long long seed, unsigned long long gchain,
+                                             unsigned long long t, int p, uint32_t (&stash)[4], double& z0, double& z1, double& u1, double& lg1)
+{
+    uint32_t wa, wb;
+    pair_words<NP, Q>(c, seed, gchain, t, p, stash, wa, wb);
     kd_normal_pair_w_t<SCTAB>(wa, wb, &z0, &z1, &u1, &lg1);
     KLARA_PIN(z0); KLARA_PIN(z1);        // formed HERE: left to itself the compiler sinks the transforms of the stashed halves towards their uses (+60 registers)
+    if (p == NP - 1 && !c.last_ok) z0 = 0.0;
+    if (p == NP - 1 && !c.last_full) z1 = 0.0;
+}
+// pair_normals<.., SCTAB = true> in two halves (detmath.h kd_normal_pair_issue / kd_normal_pair_finish): pair_issue forms the pair's words and
+// starts its three table reads, pair_finish consumes them.  The kernel issues pair p + 1 before it works on pair p, so an LDS round trip
+// runs under a pair's arithmetic instead of stalling the wavefront — with the table a SIMD holds two wavefronts, and one other wavefront does
+// not cover 39 round trips per transition.  The sched_barrier keeps the reads where they are written: nothing moves across it.
+template <int NP, int Q>
+__device__ __forceinline__ void pair_issue(const PairCtx<NP, Q>& c, unsigned long long seed, unsigned long long gchain,
+                                           unsigned long long t, int p, uint32_t (&stash)[4], kd_pair_reads& rd)
+{
+    uint32_t wa, wb;
+    pair_words<NP, Q>(c, seed, gchain, t, p, stash, wa, wb);
+    kd_normal_pair_issue(wa, wb, &rd);
+    __builtin_amdgcn_sched_barrier(0);
+}
+template <int NP, int Q>
+__device__ __forceinline__ void pair_finish(const PairCtx<NP, Q>& c, int p, const kd_pair_reads& rd, double& z0, double& z1, double& u1, double& lg1)
+{
+    kd_normal_pair_finish(&rd, &z0, &z1, &u1, &lg1);
+    KLARA_PIN(z0); KLARA_PIN(z1);
     if (p == NP - 1 && !c.last_ok) z0 = 0.0;
     if (p == NP - 1 && !c.last_full) z1 = 0.0;
 }
@@ -384,6 +411,11 @@ __host__ __device__ constexpr int diagt_min_waves()       // wavefronts per SIMD
 // holds 72 KB of the compute unit's 160: two workgroups of 256 threads, two wavefronts per SIMD — what the 8-lane kernel runs at anyway; the
 // 4-lane kernel gives up its third wavefront for it and still comes out ahead (-5.6 % at 32 transitions per launch).  The other
 // instantiations keep the arithmetic: none of them has been timed with the table.  profiles/ab_sincos_table.txt.
+// With two wavefronts per SIMD nothing hides an LDS round trip but the wavefront's own instructions, so the table kernels' step loop is ordered for
+// that (profiles/ab_headline_latency.txt): the three table reads of pair p + 1 — log bin, rotation entry, remainder entry; their addresses need the
+// pair's Philox words only — are issued before the arithmetic of pair p and consumed after it (pair_issue / pair_finish above), and the loop
+// holds no scalar load: the launch constants it uses are read once before it (KLARA_LC in k_diagt), because every wait for a scalar load also
+// drains the LDS queue.  -10 % on the headline job at unchanged registers (168 / 219) and bits.
 #ifndef KLARA_SCTAB_MIN_STEPS
 #define KLARA_SCTAB_MIN_STEPS 8
 #endif
@@ -392,6 +424,16 @@ __host__ __device__ constexpr bool diagt_sctab()
 {
     return SAMPLER == KLARA_SAMPLER_MALA && ((Q == 4 && NP == 13) || (Q == 8 && NP == 7)) && !ONESTEP && UNITW && MON && !TUNE;
 }
+// threads per workgroup of a kernel (the launcher's workgroup, klara_launch.h diagt_go): 256 — four chain groups — everywhere; the 4-lane table
+// kernel's is a build-time choice, because 384 threads (two workgroups per compute unit: 2 x 72 KB, three wavefronts per SIMD at its 168
+// registers) would give it back the wavefront the table took.  Measured, it loses: 13.96 against 11.47 us per transition on the loop as it
+// was and 12.43 against 10.32 with the early-issued reads (4,096 wavefronts on 3,072 slots are 1.33 rounds, and six wavefronts fill a table
+// that four filled) — profiles/ab_headline_latency.txt.  256 stays; every use of the workgroup size in the kernel is blockDim.x.
+#ifndef KLARA_Q4_SCTAB_WG
+#define KLARA_Q4_SCTAB_WG 256
+#endif
+template <int Q, bool SCTAB>
+__host__ __device__ constexpr int diagt_wg_threads() { return SCTAB && Q == 4 ? KLARA_Q4_SCTAB_WG : 256; }
 
 // USERPAIR (run-time compiled instantiations only, klara_custom_pair.h): the target is the user's pair closure
 //     lt(x) = sum over element pairs P of klara_user_pair(x[2P], x[2P+1], P, ...)      (it also returns the pair's two partial derivatives)
@@ -405,7 +447,7 @@ __host__ __device__ constexpr bool diagt_sctab()
 #define KLARA_PAIR_CALL(a, b, P, g0, g1) 0.0
 #endif
 template <int SAMPLER, int NP, int Q, bool ONESTEP, bool UNITW, bool MON, bool TUNE = false, bool DA = false, bool USERPAIR = false, bool SCTAB = false>
-__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_SLICE && NP <= 8 && !MON && !TUNE ? KLARA_DT_SLICE_WF : diagt_min_waves<SAMPLER, NP, Q, ONESTEP, TUNE>()))
+__global__ __launch_bounds__((diagt_wg_threads<Q, SCTAB>()), (SAMPLER == KLARA_SAMPLER_SLICE && NP <= 8 && !MON && !TUNE ? KLARA_DT_SLICE_WF : diagt_min_waves<SAMPLER, NP, Q, ONESTEP, TUNE>()))
 void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 {
 #ifndef KLARA_USER_PAIR_TARGET
@@ -538,6 +580,20 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
         const long long acc0 = tn.accepted;
         tn.phase = per_chain_tune ? (int)(tn.proposed % p.period) : 0;
 
+        // Launch constants the step loop uses every transition.  Read where they are used (KLaunch, klara_kernels.h) the compiler re-reads them inside the
+        // loop rather than hold an SGPR pair — 14 scalar loads per transition in the table kernels, each followed by a wait that also drains
+        // the LDS queue, so no table read could stay in flight across one.  The table kernels read them once, here, and KLARA_PIN_S makes the
+        // registers opaque (nothing to rematerialise); the Philox key schedule then hangs off registers, not off a load.
+        // (held_inc: a saved step's held += 1 as a scalar operand — the compiler's own form is a select in two vector registers.)  The other
+        // instantiations keep reading at the point of use: KLARA_LC picks at compile time, and their code is what it was.
+        struct { unsigned long long seed; long long burnin, nsteps_total, hist_cols, held_inc; int thinning; double sqrt_step0, inv_step0; } lc = {};
+        if constexpr (SCTAB) {
+            lc.seed = p.seed; lc.burnin = p.burnin; lc.nsteps_total = p.nsteps_total; lc.hist_cols = p.hist_cols; lc.thinning = (int)p.thinning;
+            lc.held_inc = __builtin_amdgcn_readfirstlane(do_sum ? 1 : 0); lc.sqrt_step0 = p.sqrt_step0; lc.inv_step0 = p.inv_step0;
+            KLARA_PIN_S(lc.seed); KLARA_PIN_S(lc.burnin); KLARA_PIN_S(lc.nsteps_total); KLARA_PIN_S(lc.hist_cols); KLARA_PIN_S(lc.thinning);
+            KLARA_PIN_S(lc.held_inc); KLARA_PIN_S(lc.sqrt_step0); KLARA_PIN_S(lc.inv_step0);
+        }
+#define KLARA_LC(f) (SCTAB ? lc.f : p.f)
         for (int s = 0; s < nsteps; ++s) {
             const unsigned long long t = kl.t0 + (unsigned long long)s;
             if (KCNT) tune_count_proposal(p, tn);
@@ -560,11 +616,19 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
             // and drawing first measured faster: 15.3 vs 17.1 us per transition for the monitored MALA job)
             constexpr bool ZFIRST = (ONESTEP || Q != 4) && SAMPLER != KLARA_SAMPLER_HMC && !SLICE;
             double z[ZFIRST ? E : 2];
+            kd_pair_reads rd[2];                                 // (SCTAB) the table entries of the pair in work and of the next one
             if (ZFIRST) {
+                if constexpr (SCTAB) pair_issue<NP, Q>(cx, KLARA_LC(seed), gchain, t, 0, nstash, rd[0]);
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
-                    pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, z[2 * pi], z[2 * pi + 1], u_last, lg_last);
-                    KLARA_DT_PAIR_FENCE(pi);
+                    if constexpr (SCTAB) {                       // pair pi + 1's reads run under pair pi's log, radius and rotation
+                        if (pi + 1 < NP) pair_issue<NP, Q>(cx, KLARA_LC(seed), gchain, t, pi + 1, nstash, rd[(pi + 1) & 1]);
+                        pair_finish<NP, Q>(cx, pi, rd[pi & 1], z[2 * pi], z[2 * pi + 1], u_last, lg_last);
+                        __builtin_amdgcn_sched_barrier(0);
+                    } else {
+                        pair_normals<NP, Q, SCTAB>(cx, KLARA_LC(seed), gchain, t, pi, nstash, z[2 * pi], z[2 * pi + 1], u_last, lg_last);
+                        KLARA_DT_PAIR_FENCE(pi);
+                    }
                 }
             }
             if constexpr (SLICE) {
@@ -590,7 +654,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     const int i = 2 * ((e >> 1) * Q + cx.q) + (e & 1);
                     const bool live = chain_ok && i < D;
                     const uint32_t base = (uint32_t)(live ? i : 0) << KLARA_SLICE_ATT_BITS;
-                    const kd_u32x4 b0 = kd_stream_block(p.seed, gchain, t, base);
+                    const kd_u32x4 b0 = kd_stream_block(KLARA_LC(seed), gchain, t, base);
                     const double lgu = kd_log_u01(kd_uniform_xy(b0));                          // :66 log(rand()); the slice level is lgu + lt
                     const double ru = kd_uniform_zw(b0);                                       // :71
                     const double wi_t = UNITW ? 1.0 : wv(e), mi_t = UNITW ? 0.0 : mv(e);
@@ -637,7 +701,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     for (uint32_t a = 1;; ++a) {                                               // :91-106
                         if (!done && a > KLARA_SLICE_MAX_ATT) { stuck = true; done = true; }
                         if (!__any(!done)) break;
-                        if (a & 1u) ab = kd_stream_block(p.seed, gchain, t, kd_slice_attempt_slot(base, a));   // (a is wave-uniform: attempts 2k - 1 and 2k share a block)
+                        if (a & 1u) ab = kd_stream_block(KLARA_LC(seed), gchain, t, kd_slice_attempt_slot(base, a));   // (a is wave-uniform: attempts 2k - 1 and 2k share a block)
                         const double u = (a & 1u) ? kd_uniform_xy(ab) : kd_uniform_zw(ab);
                         const double cand = u * (Ri - Li) + Li;                                // :92-93
                         const double tc = term_of(done ? xprime : cand);                       // :94
@@ -675,7 +739,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
                     double z0 = ZFIRST ? z[(2 * pi) % (ZFIRST ? E : 2)] : 0.0, z1 = ZFIRST ? z[(2 * pi + 1) % (ZFIRST ? E : 2)] : 0.0;
-                    if (!ZFIRST) pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, z0, z1, u_last, lg_last);
+                    if (!ZFIRST) pair_normals<NP, Q, SCTAB>(cx, KLARA_LC(seed), gchain, t, pi, nstash, z0, z1, u_last, lg_last);
                     const int r = (NR == 2 && (pi & 1)) ? 3 : 0;
                     if constexpr (USERPAIR) {
                         const double a = x[2 * pi] + sig[2 * pi] * z0, b = x[2 * pi + 1] + sig[2 * pi + 1] * z1;      // MH.jl:79
@@ -702,33 +766,42 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 acc = ratio > 0.0;                                                             // :97
                 if (acc_free) acc = acc || ratio > lane_bcast(lg_last, acc_lane);
                 else if (!acc && ratio > KD_LOG_UMIN_GUARD)
-                    acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(p.seed, gchain, t, (uint32_t)acc_slot)));
+                    acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot)));
             } else if (SAMPLER == KLARA_SAMPLER_MALA) {                            // iterate/MALA.jl:78-128
-                const double h_ = tn.step, halfh = 0.5 * h_, sq = KCNT ? __builtin_sqrt(h_) : p.sqrt_step0;
-                const double half_inv_h = 0.5 * (KCNT ? 1.0 / h_ : p.inv_step0);
+                const double h_ = tn.step, halfh = 0.5 * h_, sq = KCNT ? __builtin_sqrt(h_) : KLARA_LC(sqrt_step0);
+                const double half_inv_h = 0.5 * (KCNT ? 1.0 / h_ : KLARA_LC(inv_step0));
                 // UNITW: the gradient -2.0 * x is an exact scaling, so halfh * (-2.0 * x) and (-h) * x are one real number, rounded once
                 // either way: the same bits and one instruction less per mean (still a multiply and an add, never an fma).  It needs h to
                 // be a normal number (0.5 * h is exact) and -2 x not to overflow (|x| <= DBL_MAX / 2; lt is -inf from |x| ~ 1e154 on).
                 // Other weights keep halfh * (m2w * dd): halfh * m2w would round on its own.  The gradient that is stored stays -2.0 * x.
                 const double neg_h = -h_;
-                const auto mala_elem = [&](int e, double ze, int r) -> double {
+                // (first: the partial sum's first term.  0 + term is term bit for bit — a square, or a square times h > 0's 0.5 / h, is never -0 — so
+                // the sums start FROM it: six additions per transition less on 4 lanes)
+                constexpr bool FROM_TERM = UNITW && PLAIN;
+                const auto mala_elem = [&](int e, double ze, int r, bool first) -> double {
                     double term, ge = 0.0, gpe;
                     if constexpr (!UNITW) diag_elem<UNITW>(x[e], wv(e), m2wv(e), mv(e), term, ge);   // (the current gradient, re-formed)
                     const double m_ = UNITW ? x[e] + neg_h * x[e] : x[e] + halfh * ge;         // :83
                     const double xe = m_ + sq * ze;                                            // :84
                     diag_elem<UNITW>(xe, wv(e), m2wv(e), mv(e), term, gpe);         // :86
-                    red[r] = red[r] + term;
+                    red[r] = first ? term : red[r] + term;
                     const double q1 = m_ - xe;
-                    red[r + 1] = red[r + 1] + (q1 * q1) * half_inv_h;                          // :90
+                    red[r + 1] = first ? (q1 * q1) * half_inv_h : red[r + 1] + (q1 * q1) * half_inv_h;   // :90
                     const double mup = UNITW ? xe + neg_h * xe : xe + halfh * gpe;             // :91
                     const double q2 = mup - x[e];
-                    red[r + 2] = red[r + 2] + (q2 * q2) * half_inv_h;                          // :92
+                    red[r + 2] = first ? (q2 * q2) * half_inv_h : red[r + 2] + (q2 * q2) * half_inv_h;   // :92
                     return xe;
                 };
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
                     double z0 = ZFIRST ? z[(2 * pi) % (ZFIRST ? E : 2)] : 0.0, z1 = ZFIRST ? z[(2 * pi + 1) % (ZFIRST ? E : 2)] : 0.0;
-                    if (!ZFIRST) pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, z0, z1, u_last, lg_last);
+                    if constexpr (!ZFIRST && SCTAB) {
+                        // pair pi's entries were asked for one pair ago: its angle reads have had the last pair's arithmetic and this pair's log and
+                        // radius to arrive.  Pair pi + 1's reads (after its Philox block, where it forms one) go out in front of this pair's arithmetic.
+                        if (pi == 0) pair_issue<NP, Q>(cx, KLARA_LC(seed), gchain, t, 0, nstash, rd[0]);
+                        pair_finish<NP, Q>(cx, pi, rd[pi & 1], z0, z1, u_last, lg_last);
+                        if (pi + 1 < NP) pair_issue<NP, Q>(cx, KLARA_LC(seed), gchain, t, pi + 1, nstash, rd[(pi + 1) & 1]);
+                    } else if (!ZFIRST) pair_normals<NP, Q, SCTAB>(cx, KLARA_LC(seed), gchain, t, pi, nstash, z0, z1, u_last, lg_last);
                     const int r = (NR == 2 && (pi & 1)) ? 3 : 0;
                     if constexpr (USERPAIR) {
                         double nt, ge0, ge1, gp0, gp1;
@@ -745,10 +818,11 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                         red[r + 2] = red[r + 2] + (q21 * q21) * half_inv_h;
                         put_xp(pi, a, b);
                     } else {
-                        const double a = mala_elem(2 * pi, z0, r), b = mala_elem(2 * pi + 1, z1, r);
+                        const double a = mala_elem(2 * pi, z0, r, FROM_TERM && pi < NR), b = mala_elem(2 * pi + 1, z1, r, false);
                         put_xp(pi, a, b);
                     }
-                    if (!ZFIRST) KLARA_DT_PAIR_FENCE(pi);
+                    if constexpr (!ZFIRST && SCTAB) __builtin_amdgcn_sched_barrier(0);
+                    else if (!ZFIRST) KLARA_DT_PAIR_FENCE(pi);
                 }
                 group_allreduce<3 * NR>(red, Q, cx.lane);
                 if (NR == 2) { red[0] = red[0] + red[3]; red[1] = red[1] + red[4]; red[2] = red[2] + red[5]; }
@@ -759,7 +833,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 acc = ratio > 0.0;                                                             // :94
                 if (acc_free) acc = acc || ratio > lane_bcast(lg_last, acc_lane);
                 else if (!acc && ratio > KD_LOG_UMIN_GUARD)
-                    acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(p.seed, gchain, t, (uint32_t)acc_slot)));
+                    acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot)));
             } else {                                                               // iterate/HMC.jl:124-201
                 const double eps = tn.step, halfe = 0.5 * eps;
                 double mom[E], gp[E];
@@ -768,7 +842,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 double k0[NR] = {};
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
-                    pair_normals<NP, Q, SCTAB>(cx, p.seed, gchain, t, pi, nstash, mom[2 * pi], mom[2 * pi + 1], u_last, lg_last);   // :135
+                    pair_normals<NP, Q, SCTAB>(cx, KLARA_LC(seed), gchain, t, pi, nstash, mom[2 * pi], mom[2 * pi + 1], u_last, lg_last);   // :135
                     const int r = (NR == 2 && (pi & 1)) ? 1 : 0;
                     k0[r] = k0[r] + mom[2 * pi] * mom[2 * pi];
                     k0[r] = k0[r] + mom[2 * pi + 1] * mom[2 * pi + 1];
@@ -859,7 +933,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 const double a = 1.0 < ex ? 1.0 : ex;                                          // :163
                 a_da = a;
                 const double u = acc_free ? lane_bcast(u_last, acc_lane)
-                                          : kd_accept_uniform(kd_stream_block(p.seed, gchain, t, (uint32_t)acc_slot));
+                                          : kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot));
                 acc = u < a;                                                                   // :165
             }
 
@@ -899,10 +973,11 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
             // save rule: BasicMCJob.jl:226-231 with postrange = (burnin+1):thinning:nsteps (BasicMCRange.jl:36); the
             // phase / column bookkeeping comes from the host (klara_run_async), as in the group-layout kernel
             const long long i1 = (long long)t + 1;
-            if (MON && i1 > p.burnin && i1 <= p.nsteps_total) {
+            if (MON && i1 > KLARA_LC(burnin) && i1 <= KLARA_LC(nsteps_total)) {
                 if (sphase == 0) {
-                    if (do_sum) held += 1;
-                    if (scol < p.hist_cols) {
+                    if constexpr (SCTAB) held += lc.held_inc;
+                    else if (do_sum) held += 1;
+                    if (scol < KLARA_LC(hist_cols)) {
                         const long long col0 = scol * p.nchains + first_chain;
                         if (p.hist != nullptr) store_pairs<NP, Q>(cx, group_window(p.hist, col0, here, D), x);
                         if (NEEDG && p.hist_g != nullptr) { double gq[E]; grad_of(x, gq); store_pairs<NP, Q>(cx, group_window(p.hist_g, col0, here, D), gq); }
@@ -910,7 +985,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     }
                     ++scol;
                 }
-                sphase = (sphase + 1 == (int)p.thinning) ? 0 : sphase + 1;
+                sphase = (sphase + 1 == (SCTAB ? lc.thinning : (int)p.thinning)) ? 0 : sphase + 1;
             }
         }
         if (do_sum) {
@@ -945,6 +1020,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
         p.clock_probe[0] = __builtin_amdgcn_s_memtime(); p.clock_probe[1] = __builtin_amdgcn_s_memrealtime();
     }
     auto_finish(ka, wave_acc);
+#undef KLARA_LC
 }
 
 // initialize!(pstate, parameter, sampler) for layout kind 3: lt (and the gradient) at X, finiteness check

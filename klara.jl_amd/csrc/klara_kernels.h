@@ -50,9 +50,11 @@ __host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { re
 #if defined(__HIP_DEVICE_COMPILE__)
 #define KLARA_SCHED_STAGE() __builtin_amdgcn_sched_barrier(0)
 #define KLARA_PIN(v) asm volatile("" : "+v"(v))
+#define KLARA_PIN_S(v) asm volatile("" : "+s"(v))      // the same for a wave-uniform value in scalar registers: it cannot be re-formed (re-loaded) later either
 #else
 #define KLARA_SCHED_STAGE() ((void)0)
 #define KLARA_PIN(v) ((void)0)
+#define KLARA_PIN_S(v) ((void)0)
 #endif
 // Loops over a lane's E elements are fully unrolled (the element arrays are registers).  The run-time compiled closure kernels with
 // 256 elements per lane define this to "nounroll" (klara_jit.hip): unrolled, such a kernel takes half a minute to compile per mode
@@ -156,7 +158,9 @@ struct KParams {
 // Per-launch values, passed by value.  Everything else (KParams) is static for a handle and lives in device memory:
 // the kernels read it through a `const KParams* __restrict__` with scalar loads at the point of use, which keeps
 // the ~100 dwords of configuration out of the SGPR file (passed by value they were spilled to VGPR lanes:
-// 600+ v_readlane/v_writelane in the transition kernel).
+// 600+ v_readlane/v_writelane in the transition kernel).  Inside a step loop a read at the point of use is a scalar load per transition whose
+// wait also drains the LDS queue: the table kernels of klara_diagt.h therefore read the few values their loop needs (the Philox key, the save
+// rule's bounds, the MALA step constants) once in front of it and pin them (KLARA_PIN_S); everything outside the loop is still read where it is used.
 struct KLaunch {
     unsigned long long t0;                     // global index of the first transition of this launch
     int nsteps;                                // transitions in this launch

@@ -159,8 +159,11 @@ static hipError_t diagt_go(const KParams* p, const KLaunch& kl, const KAuto& ka,
 {
     const dim3 grid((unsigned)((nwaves + 3) / 4)), blk(256);
     if constexpr (diagt_sctab<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE>()) {
-        if (kl.nsteps >= KLARA_SCTAB_MIN_STEPS)
-            return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA, false, true>, grid, blk, (size_t)KD_SCREM_BYTES, st, p, kl, ka);
+        if (kl.nsteps >= KLARA_SCTAB_MIN_STEPS) {
+            constexpr int WPG = diagt_wg_threads<Q_, true>() / 64;       // wavefronts (chain groups) per workgroup of the table kernel
+            return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA, false, true>, dim3((unsigned)((nwaves + WPG - 1) / WPG)), dim3(64 * WPG),
+                            (size_t)KD_SCREM_BYTES, st, p, kl, ka);
+        }
     }
     return klara_go(k_diagt<S, NP_, Q_, ONESTEP, UNITW, MON, TUNE, DA>, grid, blk, 0, st, p, kl, ka);
 }
