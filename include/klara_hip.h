@@ -543,6 +543,21 @@ klara_status klara_selftest_chain_stats(int32_t device, int64_t nchains, int32_t
                                         int64_t batchlen, int32_t nsplits, const int64_t* splits, double* iid, double* bm, double* imse,
                                         double* ipse, double* stream_imse, double* stream_ipse);
 
+/* Self-test hook: the across-chain reductions on a caller's per-chain running sums, through the launch functions klara_get_pooled_summaries and
+ * klara_gather_moments use.  sum, sumsq and X are nchains x ndims (ndims 1..1024), held and naccept nchains: chain c's sums over its nsaved (>= 0) saved
+ * steps are sum + held x and sumsq + held x^2 (held = 0: as stored).
+ * (a) over all chains: pooled_sum, pooled_sumsq (ndims each; with_sums = 0 leaves the device's sum slots untouched: they start as the values these two
+ * arrays hold on entry and are handed back as they are), accept_total, and the pooled moments mean, m2 (ndims each).
+ * (b) the chains cut into nranks shards, rank r owning [bounds[r], bounds[r + 1]) with 0 = bounds[0] < ... < bounds[nranks] = nchains: every shard's
+ * moments and the two rank-local steps of klara_gather_moments' between-rank merge, each all-reduce replaced by a host sum over the ranks in ascending
+ * order starting from zero: ranks_mean, ranks_m2 (ndims each), ranks_counters[3] = accept total, saved samples, chains.
+ * Every output may be NULL.  KLARA_ERR_INVALID_ARG (before any launch) for a NULL input, nchains <= 0, ndims outside 1..1024, nsaved < 0 or bad bounds.
+ * Tests compare the outputs bit for bit with a restatement of the order of operations and with exact rational arithmetic. */
+klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
+                                   const double* X, const int64_t* held, const uint64_t* naccept, int32_t nranks, const int64_t* bounds,
+                                   int32_t with_sums, double* pooled_sum, double* pooled_sumsq, uint64_t* accept_total, double* mean, double* m2,
+                                   double* ranks_mean, double* ranks_m2, uint64_t* ranks_counters);
+
 /* Self-test hook, no device needed: the launches a sequence of klara_run calls of the given lengths issues on a fresh job of
  * this descriptor — transitions per launch k[i], the save-rule bookkeeping handed to the kernels (columns already saved,
  * thinning phase of the launch's first post-burn-in transition) and flags (bit 0: a pooled tuner update follows, bit 1: a batch

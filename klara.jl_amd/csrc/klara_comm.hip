@@ -136,6 +136,17 @@ __global__ void k_moments_between(double* __restrict__ m2, const double* mean_r,
     mean_out[j] = mean;
     m2[j] = m2[j] + n_r * (d * d);
 }
+hipError_t moments_scale_async(hipStream_t stream, double* wsum, const double* mean_r, double n_r, int D)
+{
+    hipLaunchKernelGGL(k_scale, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, stream, wsum, mean_r, n_r, D);
+    return hipGetLastError();
+}
+hipError_t moments_between_async(hipStream_t stream, double* m2, const double* mean_r, const double* wsum, const unsigned long long* ntot, double n_r,
+                                 int D, double* mean_out)
+{
+    hipLaunchKernelGGL(k_moments_between, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, stream, m2, mean_r, wsum, ntot, n_r, D, mean_out);
+    return hipGetLastError();
+}
 
 extern "C" klara_status klara_gather_moments(klara_handle* h, klara_comm* c, double* mean, double* m2, uint64_t* nsamples,
                                              uint64_t* naccept, uint64_t* ntransitions, uint64_t* nchains)
@@ -168,13 +179,11 @@ extern "C" klara_status klara_gather_moments(klara_handle* h, klara_comm* c, dou
         H(hipMemcpyAsync(dcnt + 1, cnt + 1, 3 * sizeof(cnt[0]), hipMemcpyHostToDevice, h->stream));
         double* wsum = c->buf + 2 * D + 4;
         const double n_r = (double)cnt[2];
-        hipLaunchKernelGGL(k_scale, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream, wsum, c->buf, n_r, (int)D);
-        H(hipGetLastError());
+        H(moments_scale_async(h->stream, wsum, c->buf, n_r, (int)D));
         // three in-place all-reduces on the job's stream: 4 counters, D weighted means, D sums of squares — latency-bound
         if (c->AllReduce(dcnt, dcnt, 4, ncclUint64, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
         if (c->AllReduce(wsum, wsum, D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        hipLaunchKernelGGL(k_moments_between, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, h->stream, c->buf + D, c->buf, wsum, dcnt + 2, n_r, (int)D, c->buf);
-        H(hipGetLastError());
+        H(moments_between_async(h->stream, c->buf + D, c->buf, wsum, dcnt + 2, n_r, (int)D, c->buf));
         if (c->AllReduce(c->buf + D, c->buf + D, D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
         std::vector<double> hostc(2 * D + 4);
         H(hipMemcpyAsync(hostc.data(), c->buf, (2 * D + 4) * sizeof(double), hipMemcpyDeviceToHost, h->stream));

@@ -122,7 +122,20 @@ hipError_t launch_acov_finalize(hipStream_t stream, const double* S, const doubl
 // the post-hoc estimators over a stored history (k_chain_stats), every output optional (device, N * D each)
 hipError_t launch_chain_stats(hipStream_t stream, const double* hist, long long ncols, long long N, int D, long long batchlen, long long maxlag,
                               double* iid, double* bm, double* imse, double* ipse);
-hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);
+// the across-chain reductions on plain buffers (the job path and klara_selftest_pooled run the same kernels): sum / sumsq / X are N x D, held and
+// naccept N, partial 1024 (2 D + 1) doubles of staging; out = 2 D doubles and the u64 accept total (sum, sumsq — untouched when sum is null — or mean, M2)
+hipError_t pool_summaries_async(hipStream_t stream, const double* sum, const double* sumsq, const double* X, const long long* held,
+                                const unsigned long long* naccept, long long N, int D, double* partial, double* out);
+hipError_t pool_moments_async(hipStream_t stream, const double* sum, const double* sumsq, const double* X, const long long* held,
+                              const unsigned long long* naccept, long long N, int D, long long nsaved, double* partial, double* out);
+hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);      // ... with the handle's arrays, on its stream
 hipError_t pool_moments_async(klara_handle* h, double* out);
+
+// ---- klara_comm.hip: the rank-local halves of the between-rank merge of the pooled moments, around the all-reduces of klara_gather_moments
+// wsum[j] = n_r mean_r[j]
+hipError_t moments_scale_async(hipStream_t stream, double* wsum, const double* mean_r, double n_r, int D);
+// with wsum and *ntot summed over the ranks: mean_out[j] = wsum[j] / ntot (0 when ntot is 0), m2[j] = M2_r[j] + n_r (mean_r[j] - mean)^2  (mean_out may be mean_r)
+hipError_t moments_between_async(hipStream_t stream, double* m2, const double* mean_r, const double* wsum, const unsigned long long* ntot, double n_r,
+                                 int D, double* mean_out);
 
 #pragma GCC visibility pop

@@ -358,19 +358,23 @@ __global__ __launch_bounds__(256) void k_pool_stage2(const double* __restrict__ 
         if (t == 0) *reinterpret_cast<unsigned long long*>(out + 2 * D) = su[0];
     }
 }
-// out: 2 D doubles (sum, sumsq; untouched unless with_sums) followed by the u64 accept total; on the handle's stream
-hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out)
+// out: 2 D doubles (sum, sumsq; untouched when sum is null) followed by the u64 accept total.  partial: KLARA_POOL_BLOCKS x (2 D doubles + 1 u64).
+// (the buffers, not the handle: the job path and klara_selftest_pooled launch the same kernels through this one function)
+hipError_t pool_summaries_async(hipStream_t stream, const double* sum, const double* sumsq, const double* X, const long long* held,
+                                const unsigned long long* naccept, long long N, int D, double* partial, double* out)
 {
-    const int D = h->d.ndims;
-    const long long N = h->d.nchains;
     const int nb = (int)(N < KLARA_POOL_BLOCKS ? N : KLARA_POOL_BLOCKS);
-    hipLaunchKernelGGL(k_pool_stage1, dim3(nb), dim3(256), 0, h->stream, with_sums ? h->sum : nullptr, h->sumsq, h->X, h->held, h->naccept, N, D, nb,
-                       h->pool_partial, reinterpret_cast<unsigned long long*>(h->pool_partial + (size_t)KLARA_POOL_BLOCKS * 2 * D));
+    unsigned long long* partial_acc = reinterpret_cast<unsigned long long*>(partial + (size_t)KLARA_POOL_BLOCKS * 2 * D);
+    hipLaunchKernelGGL(k_pool_stage1, dim3(nb), dim3(256), 0, stream, sum, sumsq, X, held, naccept, N, D, nb, partial, partial_acc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pool_stage2, dim3(2 * D + 1), dim3(256), 0, h->stream, h->pool_partial,
-                       reinterpret_cast<const unsigned long long*>(h->pool_partial + (size_t)KLARA_POOL_BLOCKS * 2 * D), D, nb, with_sums, out);
+    hipLaunchKernelGGL(k_pool_stage2, dim3(2 * D + 1), dim3(256), 0, stream, partial, partial_acc, D, nb, sum != nullptr, out);
     return hipGetLastError();
+}
+hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out)
+{
+    return pool_summaries_async(h->stream, with_sums ? h->sum : nullptr, h->sumsq, h->X, h->held, h->naccept, (long long)h->d.nchains, h->d.ndims,
+                                h->pool_partial, out);
 }
 
 extern "C" klara_status klara_get_pooled_summaries(klara_handle* h, double* sum, double* sumsq,
@@ -451,18 +455,22 @@ __global__ __launch_bounds__(256) void k_moments_stage2(const double* __restrict
     }
     if (t == 0) { out[j] = sm[0]; out[D + j] = sq[0]; }
 }
-// out: mean[D], M2[D], then the u64 accept total; on the handle's stream
+// out: mean[D], M2[D], then the u64 accept total; partial as for pool_summaries_async
+hipError_t pool_moments_async(hipStream_t stream, const double* sum, const double* sumsq, const double* X, const long long* held,
+                              const unsigned long long* naccept, long long N, int D, long long nsaved, double* partial, double* out)
+{
+    const int nb = (int)(N < KLARA_POOL_BLOCKS ? N : KLARA_POOL_BLOCKS);
+    hipError_t e = pool_summaries_async(stream, nullptr, sumsq, X, held, naccept, N, D, partial, out);   // the accept total -> out[2 D]
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_moments_stage1, dim3(nb), dim3(256), 0, stream, sum, sumsq, X, held, N, D, nb, (double)nsaved, partial);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_moments_stage2, dim3(D), dim3(256), 0, stream, partial, N, D, nb, (double)nsaved, out);
+    return hipGetLastError();
+}
 hipError_t pool_moments_async(klara_handle* h, double* out)
 {
-    const int D = h->d.ndims;
-    const long long N = h->d.nchains;
-    const int nb = (int)(N < KLARA_POOL_BLOCKS ? N : KLARA_POOL_BLOCKS);
-    hipError_t e = pool_summaries_async(h, false, out);                     // the accept total -> out[2 D]
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_moments_stage1, dim3(nb), dim3(256), 0, h->stream, h->sum, h->sumsq, h->X, h->held, N, D, nb, (double)h->nsaved, h->pool_partial);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_moments_stage2, dim3(D), dim3(256), 0, h->stream, h->pool_partial, N, D, nb, (double)h->nsaved, out);
-    return hipGetLastError();
+    return pool_moments_async(h->stream, h->sum, h->sumsq, h->X, h->held, h->naccept, (long long)h->d.nchains, h->d.ndims, (long long)h->nsaved,
+                              h->pool_partial, out);
 }
 
 // Columns [first, first + count) of the saved steps from a history buffer whose column c lives at slot c % hist_cols (ring) or c:

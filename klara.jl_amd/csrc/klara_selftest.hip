@@ -1,5 +1,5 @@
 // klara_selftest.hip — self tests: the device's random blocks, math, normals and matrix-core probes as the kernels see them; the chain statistics kernels on a
-// caller's series; compile checks of user targets.
+// caller's series; the across-chain reductions on a caller's chain sums; compile checks of user targets.
 #include <rocrand/rocrand_kernel.h>
 #include "klara_handle.h"
 
@@ -224,6 +224,98 @@ extern "C" klara_status klara_selftest_chain_stats(int32_t device, int64_t nchai
         if (dst[k]) e = hipMemcpy(dst[k], out + (size_t)k * nd, (size_t)nd * sizeof(double), hipMemcpyDeviceToHost);
     (void)dfree(dh); (void)dfree(S); (void)dfree(head); (void)dfree(tail); if (near) (void)dfree(near); (void)dfree(total); (void)dfree(out);
     return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
+}
+
+// The across-chain reductions on a caller's per-chain sums, through the launch functions of the job path: (a) pool_summaries_async and pool_moments_async
+// over all the chains; (b) the chains cut into nranks shards, pool_moments_async on every shard's slice and the rank-local halves of klara_gather_moments'
+// between-rank merge around it, every all-reduce replaced by a host sum over the ranks in ascending order, starting from 0.
+extern "C" klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
+                                              const double* X, const int64_t* held, const uint64_t* naccept, int32_t nranks, const int64_t* bounds,
+                                              int32_t with_sums, double* pooled_sum, double* pooled_sumsq, uint64_t* accept_total, double* mean, double* m2,
+                                              double* ranks_mean, double* ranks_m2, uint64_t* ranks_counters)
+{
+    if (!sum || !sumsq || !X || !held || !naccept || !bounds || nchains <= 0 || ndims < 1 || ndims > 1024 || nsaved < 0 || nranks < 1) return KLARA_ERR_INVALID_ARG;
+    if (bounds[0] != 0 || bounds[nranks] != nchains) return KLARA_ERR_INVALID_ARG;
+    for (int r = 0; r < nranks; ++r) if (bounds[r + 1] <= bounds[r]) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    const size_t D = (size_t)ndims, nd = (size_t)nchains * D, per = 3 * D + 4;       // per rank, as klara_gather_moments stages it: mean_r, M2_r, accept total, 3 counters, n_r mean_r
+    const long long N = nchains;
+    DeviceArrays mem;
+    double *dsum = nullptr, *dsumsq = nullptr, *dX = nullptr, *partial = nullptr, *out = nullptr, *rb = nullptr, *dw = nullptr;
+    long long* dheld = nullptr; unsigned long long *dacc = nullptr, *dnt = nullptr;
+    hipError_t e = mem.alloc(&dsum, nd);
+    if (e == hipSuccess) e = mem.alloc(&dsumsq, nd);
+    if (e == hipSuccess) e = mem.alloc(&dX, nd);
+    if (e == hipSuccess) e = mem.alloc(&dheld, (size_t)N);
+    if (e == hipSuccess) e = mem.alloc(&dacc, (size_t)N);
+    if (e == hipSuccess) e = mem.alloc(&partial, (size_t)1024 * (2 * D + 1));            // (as klara_create sizes pool_partial)
+    if (e == hipSuccess) e = mem.alloc(&out, 2 * (2 * D + 1));
+    if (e == hipSuccess) e = mem.alloc(&rb, (size_t)nranks * per);
+    if (e == hipSuccess) e = mem.alloc(&dw, D);
+    if (e == hipSuccess) e = mem.alloc(&dnt, 1);
+    if (e == hipSuccess) e = hipMemcpy(dsum, sum, nd * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dsumsq, sumsq, nd * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dX, X, nd * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dheld, held, (size_t)N * sizeof(long long), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dacc, naccept, (size_t)N * sizeof(unsigned long long), hipMemcpyHostToDevice);
+    // the sum slots start as the caller's pooled_sum / pooled_sumsq (zeros without them): with_sums = 0 has to hand them back as they were
+    if (e == hipSuccess) e = hipMemset(out, 0, 2 * (2 * D + 1) * sizeof(double));
+    if (e == hipSuccess && pooled_sum) e = hipMemcpy(out, pooled_sum, D * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && pooled_sumsq) e = hipMemcpy(out + D, pooled_sumsq, D * sizeof(double), hipMemcpyHostToDevice);
+    const hipStream_t st = 0;
+    double* outm = out + 2 * D + 1;
+    // (a)
+    if (e == hipSuccess) e = pool_summaries_async(st, with_sums ? dsum : nullptr, dsumsq, dX, dheld, dacc, N, ndims, partial, out);
+    if (e == hipSuccess) e = pool_moments_async(st, dsum, dsumsq, dX, dheld, dacc, N, ndims, (long long)nsaved, partial, outm);
+    // (b) every rank's moments and n_r mean_r
+    for (int r = 0; r < nranks && e == hipSuccess; ++r) {
+        const long long c0 = bounds[r], Nr = bounds[r + 1] - bounds[r];
+        double* b = rb + (size_t)r * per;
+        e = pool_moments_async(st, dsum + c0 * D, dsumsq + c0 * D, dX + c0 * D, dheld + c0, dacc + c0, Nr, ndims, (long long)nsaved, partial, b);
+        if (e == hipSuccess) e = moments_scale_async(st, b + 2 * D + 4, b, (double)((unsigned long long)nsaved * (unsigned long long)Nr), ndims);
+    }
+    std::vector<double> hout(2 * (2 * D + 1)), hrb((size_t)nranks * per), acc(D);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(hout.data(), out, hout.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
+    // the all-reduce of the counters and of n_r mean_r
+    unsigned long long cnt[3] = { 0, 0, 0 };                                              // accept total, saved samples, chains
+    if (e == hipSuccess) {
+        for (size_t j = 0; j < D; ++j) acc[j] = 0.0;
+        for (int r = 0; r < nranks; ++r) {
+            const double* b = hrb.data() + (size_t)r * per;
+            unsigned long long a;
+            memcpy(&a, b + 2 * D, sizeof(a));
+            cnt[0] += a;
+            cnt[1] += (unsigned long long)nsaved * (unsigned long long)(bounds[r + 1] - bounds[r]);
+            cnt[2] += (unsigned long long)(bounds[r + 1] - bounds[r]);
+            for (size_t j = 0; j < D; ++j) acc[j] = acc[j] + b[2 * D + 4 + j];
+        }
+        e = hipMemcpy(dw, acc.data(), D * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(dnt, &cnt[1], sizeof(cnt[1]), hipMemcpyHostToDevice);
+    for (int r = 0; r < nranks && e == hipSuccess; ++r) {
+        double* b = rb + (size_t)r * per;
+        e = moments_between_async(st, b + D, b, dw, dnt, (double)((unsigned long long)nsaved * (unsigned long long)(bounds[r + 1] - bounds[r])), ndims, b);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
+    const bool clean = mem.release();
+    if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
+    if (pooled_sum) memcpy(pooled_sum, hout.data(), D * sizeof(double));
+    if (pooled_sumsq) memcpy(pooled_sumsq, hout.data() + D, D * sizeof(double));
+    if (accept_total) memcpy(accept_total, hout.data() + 2 * D, sizeof(uint64_t));
+    if (mean) memcpy(mean, hout.data() + 2 * D + 1, D * sizeof(double));
+    if (m2) memcpy(m2, hout.data() + 3 * D + 1, D * sizeof(double));
+    if (ranks_mean) memcpy(ranks_mean, hrb.data(), D * sizeof(double));                   // (every rank holds the same mean)
+    if (ranks_m2) {                                                                       // the all-reduce of M2_r + n_r (mean_r - mean)^2
+        for (size_t j = 0; j < D; ++j) acc[j] = 0.0;
+        for (int r = 0; r < nranks; ++r)
+            for (size_t j = 0; j < D; ++j) acc[j] = acc[j] + hrb[(size_t)r * per + D + j];
+        memcpy(ranks_m2, acc.data(), D * sizeof(double));
+    }
+    if (ranks_counters) { ranks_counters[0] = cnt[0]; ranks_counters[1] = cnt[1]; ranks_counters[2] = cnt[2]; }
+    return KLARA_OK;
 }
 
 extern "C" klara_status klara_check_custom_target(const char* src, int32_t sampler, int32_t ndims)
