@@ -189,6 +189,13 @@ typedef enum klara_tuner_mode {
 #define KLARA_MON_HIST_GRAD 0x10u /* :monitor=>[:gradlogtarget] (MALA/HMC only)                    */
 #define KLARA_MON_HIST_LLLP 0x20u /* :monitor=>[:loglikelihood, :logprior]: the two parts of a likelihood + prior user target
                                      (KLARA_TARGET_CUSTOM whose source defines KLARA_USER_LIKELIHOOD_PRIOR) at every postrange step */
+#define KLARA_MON_COVARIANCE 0x40u /* accumulate the pooled D x D cross-products of the saved samples of all chains while sampling, on the FP64 matrix
+                                     cores (the covariance / correlations of the posterior; see the gather call below).  A consumer of the saved samples, as
+                                     klara_desc.acov_maxlag is: the values are kept (a 32-column ring of its own when no value history was asked for), the
+                                     job runs as one chain partition, and a job that cannot keep a value history is refused as with KLARA_MON_HISTORY.
+                                     ndims > KLARA_COV_MAX_DIMS: KLARA_ERR_UNSUPPORTED.  The transition kernels never see the bit: the chains of a job are the
+                                     same bits with and without it. */
+#define KLARA_COV_MAX_DIMS 256
 
 typedef struct klara_desc {
     uint32_t struct_size;        /* = sizeof(klara_desc), ABI check                                  */
@@ -371,6 +378,16 @@ klara_status klara_gather_summaries(klara_handle* h, klara_comm* comm, double* s
  * Collective when comm != NULL: every rank calls it. */
 klara_status klara_gather_moments(klara_handle* h, klara_comm* comm, double* mean, double* m2, uint64_t* nsamples,
                                   uint64_t* naccept, uint64_t* ntransitions, uint64_t* nchains);
+
+/* The pooled posterior covariance (requires KLARA_MON_COVARIANCE, else KLARA_ERR_STATE): over all chains c and all saved steps t, n = chains x saved steps,
+ * mean[D] and m2[D x D] = sum (x - mean)(x - mean)', row-major, both triangles filled and bitwise symmetric — the D x D form of what klara_gather_moments
+ * returns (its diagonal is that call's m2); the caller divides: cov = m2 / (n - 1).  Accumulated while sampling: after every launch the saved samples go
+ * through v_mfma_f64_16x16x4_f64 as z = x - pivot (pivot = the first saved sample of local chain 0), slab of chains by slab, every element one fma chain
+ * in the order (saved step, chain) — the same bits however the steps are cut into launches (klara.jl_amd/csrc/klara_cov.h).  This call
+ * only reads the accumulators: m2 = S - T T' / n with the product's rounding carried.  comm = NULL: this handle's chains only; otherwise collective, the
+ * ranks merged by Chan's update in three all-reduces (4 counters, D weighted means, D x D cross-products).  Any output pointer may be NULL.  Before the
+ * first saved sample: zeros, as klara_gather_moments.  klara_set_state and klara_reset clear the accumulators. */
+klara_status klara_gather_covariance(klara_handle* h, klara_comm* comm, double* mean, double* m2, uint64_t* nsamples, uint64_t* nchains);
 
 /* Memory-safety aid (tests only).  With KLARA_DEBUG_CANARY=1 in the environment every device array the library allocates lies between
  * two 4 KiB canaries of a signalling-NaN pattern; klara_destroy returns KLARA_ERR_STATE when a kernel of the job wrote into one, and this
@@ -557,6 +574,19 @@ klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndim
                                    const double* X, const int64_t* held, const uint64_t* naccept, int32_t nranks, const int64_t* bounds,
                                    int32_t with_sums, double* pooled_sum, double* pooled_sumsq, uint64_t* accept_total, double* mean, double* m2,
                                    double* ranks_mean, double* ranks_m2, uint64_t* ranks_counters);
+
+/* Self-test hook: the pooled covariance kernels on a caller's value history.  hist holds ncols (>= 1) saved steps of nchains x ndims values as the device
+ * keeps a value history (column t at hist + t * nchains * ndims), ndims 1..KLARA_COV_MAX_DIMS; it is fed launch by launch through the launch functions the
+ * job path uses — launch j brings splits[j] saved steps (0..32 each), the splits sum to ncols — then finalized as klara_gather_covariance does:
+ * (a) over all chains: mean (ndims), m2 (ndims x ndims).
+ * (b) the chains cut into nranks shards, rank r owning [bounds[r], bounds[r + 1]) with 0 = bounds[0] < ... < bounds[nranks] = nchains: every shard accumulated
+ * and finalized on its own (its pivot is its own first chain's first sample), then the between-rank merge with each all-reduce replaced by a host sum over
+ * the ranks in ascending order starting from zero: ranks_mean (ndims), ranks_m2 (ndims x ndims), ranks_counters[2] = saved samples, chains.
+ * Every output may be NULL.  KLARA_ERR_INVALID_ARG (before any launch) for a NULL input, nchains <= 0, ndims outside 1..KLARA_COV_MAX_DIMS, ncols < 1, a
+ * split outside 0..32, splits that do not sum to ncols or bad bounds. */
+klara_status klara_selftest_covariance(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
+                                       const int64_t* splits, int32_t nranks, const int64_t* bounds, double* mean, double* m2, double* ranks_mean,
+                                       double* ranks_m2, uint64_t* ranks_counters);
 
 /* Self-test hook, no device needed: the launches a sequence of klara_run calls of the given lengths issues on a fresh job of
  * this descriptor — transitions per launch k[i], the save-rule bookkeeping handed to the kernels (columns already saved,

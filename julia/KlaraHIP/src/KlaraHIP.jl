@@ -38,7 +38,7 @@ import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
        check_custom_target_softabs, SoftAbs, ramfactor,
-       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, KlaraDesc, klara_desc
+       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
 # ---------------------------------------------------------------- Julia 0.6 / >= 0.7 compatibility (the only version-dependent code)
@@ -60,6 +60,7 @@ const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
 const MON_ACCEPT, MON_HISTORY, MON_SUMMARIES, MON_HIST_LT, MON_HIST_GRAD, MON_HIST_LLLP = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+const MON_COVARIANCE = 0x40            # KLARA_MON_COVARIANCE: the pooled D x D cross-products, accumulated while sampling (pooledcovariance)
 
 # struct klara_desc — field order/types exactly as include/klara_hip.h
 struct KlaraDesc
@@ -235,7 +236,7 @@ end
 function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
                   tuner=nothing, outopts::Dict=Dict{Symbol, Any}(), pooled::Bool=false, nchains::Integer=1,
                   seed::Integer=rand(UInt64), chain_offset::Integer=0, device::Integer=0, steps_per_launch::Integer=0,
-                  summaries::Bool=true, bm_batchlen::Integer=0)
+                  summaries::Bool=true, bm_batchlen::Integer=0, covariance::Bool=false)
     X0 = startmatrix(v0[parameter.key], nchains)                          # D x N: column = chain == N x D row-major
     D, N = size(X0)
     t = parameter.target
@@ -325,6 +326,7 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         get!(oo, :monitor, [:value]); get!(oo, :diagnostics, Symbol[])
     end
     mon = UInt32(summaries ? MON_SUMMARIES : 0x00)
+    if covariance; mon |= MON_COVARIANCE; end                             # D <= 256; the chains are the same bits with and without it
     if :accept in get(oo, :diagnostics, Symbol[]); mon |= MON_ACCEPT; end
     for m in get(oo, :monitor, Symbol[])
         m == :value && (mon |= MON_HISTORY)
@@ -550,5 +552,25 @@ function pooledmoments(job::HIPMCJob)
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{UInt64}, Ref{UInt64}, Ref{UInt64}),
                 job.handle, C_NULL, m, m2, ns, na, nt, nc), "klara_gather_moments")
     (m, m2 ./ Float64(ns[]), ns[], na[], nt[], nc[])
+end
+# The pooled posterior covariance of a job built with covariance=true (klara_gather_covariance: M = sum (x - mean)(x - mean)' over all chains and saved
+# steps, accumulated while sampling on the FP64 matrix cores; no history is stored): (mean, cov = M / (n - 1), nsamples, chains) over every chain of
+# every GPU.  (Klara's own covariance! is the in-place sample covariance of ONE stored chain: another function.)
+function gather_covariance(job::HIPMCJob, comm::HIPComm)
+    m = newarray(Float64, job.ndims); m2 = newarray(Float64, job.ndims * job.ndims)
+    ns = Ref{UInt64}(0); nc = Ref{UInt64}(0)
+    check(ccall((:klara_gather_covariance, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{UInt64}),
+                job.handle, comm.handle, m, m2, ns, nc), "klara_gather_covariance")
+    (m, reshape(m2, job.ndims, job.ndims) ./ (Float64(ns[]) - 1.0), ns[], nc[])       # (symmetric: row-major == column-major)
+end
+# ... and of this job's chains alone (no communicator, no RCCL)
+function pooledcovariance(job::HIPMCJob)
+    m = newarray(Float64, job.ndims); m2 = newarray(Float64, job.ndims * job.ndims)
+    ns = Ref{UInt64}(0); nc = Ref{UInt64}(0)
+    check(ccall((:klara_gather_covariance, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{UInt64}),
+                job.handle, C_NULL, m, m2, ns, nc), "klara_gather_covariance")
+    (m, reshape(m2, job.ndims, job.ndims) ./ (Float64(ns[]) - 1.0), ns[], nc[])
 end
 end # module

@@ -28,6 +28,11 @@ many = HIPMCJob(model, sampler, mcrange, v0; nchains=4096, seed=7)      # the sa
 run(many)
 m, v, ns, na, nt, nc = pooledmoments(many)
 @test nc == 4096 && maximum(abs.(m)) < 5e-3 && maximum(abs.(v .- 0.5)) < 5e-3
+cj = HIPMCJob(model, sampler, mcrange, v0; nchains=4096, seed=7, covariance=true)     # ... accumulating the pooled 2 x 2 cross-products while sampling
+run(cj)
+cm, cS, cns, cnc = pooledcovariance(cj)                # (mean, cov = M / (n - 1), samples, chains): -x'x has covariance I / 2
+@test cnc == 4096 && size(cS) == (2, 2) && maximum(abs.(cS .- [0.5 0.0; 0.0 0.5])) < 5e-3 && cS == cS'
+@test maximum(abs.(cm .- m)) < 1e-12
 
 D, N = 100, 4096
 p   = HIPParameter(:p, GaussDiagTarget(D))

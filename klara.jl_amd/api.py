@@ -464,6 +464,24 @@ def qzv(chains: MuvChains, chain: int = 0):
     return _zv_one(chains, chain, L.ZV_QUADRATIC, "qzv")
 
 
+def pooled_cov(job_or_chains, comm=None) -> np.ndarray:
+    """The posterior covariance pooled over all chains and saved steps of a job run with covariance=True: M / (n - 1), M = sum (x - mean)(x - mean)'
+    accumulated while sampling (Engine.pooled_covariance); `comm`: a klara_comm handle, to pool over every rank's chains."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    _, m2, ns, _ = job.engine.pooled_covariance(comm)
+    if ns < 2:
+        raise ValueError("pooled_cov needs at least two saved samples")
+    return m2 / (ns - 1)
+
+
+def pooled_cor(job_or_chains, comm=None) -> np.ndarray:
+    """The correlations of pooled_cov: cov_ij / sqrt(cov_ii cov_jj) (NaN where a coordinate never moved)."""
+    c = pooled_cov(job_or_chains, comm)
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(np.diag(c))
+        return c / np.outer(sd, sd)
+
+
 def acceptance(chains: MuvChains, diagnostics: bool = True) -> np.ndarray:
     """acceptance(s::MultivariateParameterNState; key=:accept) — stats/acceptance.jl:28-34:
     mean of the accept diagnostics over the saved steps (per chain)."""
@@ -506,13 +524,14 @@ class BasicMCJob:
     diagnostics ([] or ["accept"]).  Extra keyword arguments pick the shard: `chain_offset` (global id of
     the first chain), `device`, `seed` (default: a fresh key per job, see "random streams of jobs" above), `steps_per_launch`; `bm_batchlen` > 0 keeps streaming batch means so that
     `chain_mcvar(chain, "bm", bm_batchlen)` needs no stored history (destination "none"); `acov_maxlag` > 0 does the same for
-    `chain_mcvar(chain, "imse" | "ipse", maxlag=acov_maxlag)` (autocovariances accumulated while sampling).
+    `chain_mcvar(chain, "imse" | "ipse", maxlag=acov_maxlag)` (autocovariances accumulated while sampling); `covariance=True` accumulates the
+    pooled D x D cross-products of all chains' saved samples on the matrix cores (`pooled_cov`, `pooled_cor`), again with no stored history.
     """
 
     def __init__(self, model: GenericModel, sampler: MCSampler, mcrange: BasicMCRange, v0: Dict[str, Sequence],
                  tuner: Optional[MCTuner] = None, outopts: Optional[dict] = None, *, seed: Optional[int] = None,
                  chain_offset: int = 0, device: int = 0, steps_per_launch: int = 0, summaries: bool = True,
-                 bm_batchlen: int = 0, acov_maxlag: int = 0, sparse_moves: int = 0):
+                 bm_batchlen: int = 0, acov_maxlag: int = 0, sparse_moves: int = 0, covariance: bool = False):
         self.model, self.sampler, self.range = model, sampler, mcrange
         self.seed = _next_job_seed() if seed is None else int(seed)
         seed = self.seed
@@ -561,6 +580,9 @@ class BasicMCJob:
                 monitor |= L.MON_HIST_LLLP
         if summaries:
             monitor |= L.MON_SUMMARIES
+        if covariance:                                                # the pooled D x D cross-products, accumulated while sampling (pooled_cov)
+            monitor |= L.MON_COVARIANCE
+        self.covariance = bool(covariance)
         kw = dict(sampler=sampler.kind, target=self.parameter.target, nchains=nchains, nsteps=mcrange.nsteps,
                   burnin=mcrange.burnin, thinning=mcrange.thinning, tuner=self.tuner.kind,
                   period=self.tuner.period, verbose=self.tuner.verbose, seed=seed, chain_offset=chain_offset,

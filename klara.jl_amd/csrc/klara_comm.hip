@@ -200,3 +200,60 @@ extern "C" klara_status klara_gather_moments(klara_handle* h, klara_comm* c, dou
     if (nchains) *nchains = cnt[3];
     return KLARA_OK;
 }
+
+// The pooled covariance (klara_cov.h): this rank's (mean_r, M_r) from its accumulators, then — with a communicator — the D x D form of the merge above
+extern "C" klara_status klara_gather_covariance(klara_handle* h, klara_comm* c, double* mean, double* m2, uint64_t* nsamples, uint64_t* nchains)
+{
+    if (!h) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state || !h->cov_S) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    const size_t D = (size_t)h->d.ndims, DD = D * D;
+    unsigned long long cnt[4] = { 0, (unsigned long long)h->steps_done * (unsigned long long)h->d.nchains,
+                                  (unsigned long long)h->cov_n * (unsigned long long)h->d.nchains, (unsigned long long)h->d.nchains };
+    const double n_r = (double)cnt[2];
+    std::vector<double> host(D + DD);
+    // this rank's mean | M (before the first saved sample: zeros)
+    const auto local = [&](double* out) -> hipError_t {
+        if (h->cov_n == 0) return hipMemsetAsync(out, 0, (D + DD) * sizeof(double), h->stream);
+        return klara_cov_launch_finalize(h->cov, h->cov_S, h->cov_T, h->cov_pivot, n_r, out, h->stream);
+    };
+    if (!c) {
+        HIPCHK(local(h->cov_out));
+        HIPCHK(hipMemcpyAsync(host.data(), h->cov_out, (D + DD) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        // device staging: [0, D) mean_r, [D, D + DD) M_r -> M, 4 counters, [.. + D) n_r mean_r, [.. + D) mean
+        const size_t need = 3 * D + DD + 4;
+        if (c->cap < need) {
+            if (c->buf) (void)dfree(c->buf);
+            c->buf = nullptr; c->cap = 0;
+            HIPCHK(dalloc(&c->buf, need));
+            c->cap = need;
+        }
+        // (as in klara_gather_summaries: once the sequence of collectives starts, every rank goes through all of it; errors are reported after the last)
+        bool bad = false;
+        const auto H = [&](hipError_t e) { if (e != hipSuccess) bad = true; };
+        H(local(c->buf));
+        unsigned long long* dcnt = reinterpret_cast<unsigned long long*>(c->buf + D + DD);
+        H(hipMemcpyAsync(dcnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream));
+        double* wsum = c->buf + D + DD + 4;
+        double* mean_out = wsum + D;
+        H(moments_scale_async(h->stream, wsum, c->buf, n_r, (int)D));
+        if (c->AllReduce(dcnt, dcnt, 4, ncclUint64, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
+        if (c->AllReduce(wsum, wsum, D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
+        H(klara_cov_launch_between(h->stream, c->buf + D, c->buf, wsum, dcnt + 2, n_r, (int)D, mean_out));
+        if (c->AllReduce(c->buf + D, c->buf + D, DD, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
+        std::vector<double> hostc(need);
+        H(hipMemcpyAsync(hostc.data(), c->buf, need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        H(hipStreamSynchronize(h->stream));
+        if (bad) return KLARA_ERR_HIP;
+        memcpy(host.data(), hostc.data() + 2 * D + DD + 4, D * sizeof(double));
+        memcpy(host.data() + D, hostc.data() + D, DD * sizeof(double));
+        memcpy(cnt, hostc.data() + D + DD, sizeof(cnt));
+    }
+    if (mean) memcpy(mean, host.data(), D * sizeof(double));
+    if (m2) memcpy(m2, host.data() + D, DD * sizeof(double));
+    if (nsamples) *nsamples = cnt[2];
+    if (nchains) *nchains = cnt[3];
+    return KLARA_OK;
+}

@@ -305,20 +305,25 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
         h->accept_cap = desc->nsteps;
         HIPCHK(mem.alloc(&h->accept, (size_t)desc->nsteps * N));
     }
-    const bool acov = desc->acov_maxlag > 0;
-    if ((desc->monitor & (KLARA_MON_HISTORY | KLARA_MON_HIST_LT | KLARA_MON_HIST_GRAD | KLARA_MON_HIST_LLLP)) || acov) {
+    const bool acov = desc->acov_maxlag > 0, cov = plan.cov, keeps = acov || cov;      // the consumers of the saved samples keep values
+    if ((desc->monitor & (KLARA_MON_HISTORY | KLARA_MON_HIST_LT | KLARA_MON_HIST_GRAD | KLARA_MON_HIST_LLLP)) || keeps) {
         // npoststeps = length((burnin+1):thinning:nsteps)  (BasicMCRange.jl:26)
         h->hist_cols = (desc->nsteps - desc->burnin - 1) / desc->thinning + 1;
         long long ringc = desc->hist_ring_cols;
-        if (acov && !(desc->monitor & KLARA_MON_HISTORY) && ringc == 0) ringc = 32;     // the estimator's own value ring
-        if (acov) { h->d.monitor |= KLARA_MON_HISTORY; h->d.hist_ring_cols = ringc; }   // (the kernels save values; ring_cols(h->d) == ringc)
+        if (keeps && !(desc->monitor & KLARA_MON_HISTORY) && ringc == 0) ringc = 32;    // the consumer's own value ring
+        if (keeps) { h->d.monitor |= KLARA_MON_HISTORY; h->d.hist_ring_cols = ringc; }   // (the kernels save values; ring_cols(h->d) == ringc)
         if (ringc > 0 && ringc < h->hist_cols) { h->hist_cols = ringc; h->ring = true; }
-        if ((desc->monitor & KLARA_MON_HISTORY) || acov) HIPCHK(mem.alloc(&h->hist, (size_t)h->hist_cols * N * D));
+        if ((desc->monitor & KLARA_MON_HISTORY) || keeps) HIPCHK(mem.alloc(&h->hist, (size_t)h->hist_cols * N * D));
         if (acov) {
             h->acov_W = desc->acov_maxlag + 1;
             const size_t ws = (size_t)h->acov_W * N * D;
             HIPCHK(mem.alloc(&h->acov_S, ws)); HIPCHK(mem.alloc(&h->acov_head, ws)); HIPCHK(mem.alloc(&h->acov_tail, ws)); HIPCHK(mem.alloc(&h->acov_total, N * D));
             if (h->acov_W > 32) HIPCHK(mem.alloc(&h->acov_near, (size_t)32 * N * D));      // (scratch of the far-tail update, launch_acov_update)
+        }
+        if (cov) {
+            if (!klara_cov_plan((long long)N, (int)D, &h->cov)) return KLARA_ERR_UNSUPPORTED;
+            HIPCHK(mem.alloc(&h->cov_S, klara_cov_S_elems(h->cov))); HIPCHK(mem.alloc(&h->cov_T, klara_cov_T_elems(h->cov)));
+            HIPCHK(mem.alloc(&h->cov_pivot, D)); HIPCHK(mem.alloc(&h->cov_out, D + D * D));
         }
         if (desc->monitor & KLARA_MON_HIST_LT) HIPCHK(mem.alloc(&h->hist_lt, (size_t)h->hist_cols * N));
         if (desc->monitor & KLARA_MON_HIST_LLLP) { HIPCHK(mem.alloc(&h->hist_ll, (size_t)h->hist_cols * N)); HIPCHK(mem.alloc(&h->hist_lp, (size_t)h->hist_cols * N)); }
@@ -412,6 +417,7 @@ extern "C" klara_status klara_create(const klara_desc* desc, klara_handle** out)
         dd.custom_src = src.c_str();
     }
     if (plan.rewrite == KLARA_REWRITE_LOGIT_WIDE || plan.rewrite == KLARA_REWRITE_DENSE_WIDE) { dd.target = KLARA_TARGET_CUSTOM; dd.custom_data = blk.data(); dd.custom_ndata = (int64_t)blk.size(); }
+    dd.monitor &= ~(uint32_t)KLARA_MON_COVARIANCE;      // (plan.cov carries it: a consumer's flag, not a monitor of the kernels)
     st = validate_monitors(dd);                  // (the job as it runs: a pair closure in its whole-vector form is not a pair closure any more)
     if (st != KLARA_OK) return st;
     return create_impl(&dd, plan, out);

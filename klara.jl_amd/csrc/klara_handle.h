@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "klara_plan.h"
+#include "klara_cov.h"
 
 #define HIPCHK(expr)                                                                   \
     do {                                                                               \
@@ -62,6 +63,8 @@ struct klara_handle {
     bool ring = false;                                   // the history buffers hold the last hist_cols saved steps only
     // streaming autocovariances (acov_maxlag > 0): W = maxlag + 1 lags; [k][series] layouts
     int acov_W = 0; double *acov_S = nullptr, *acov_head = nullptr, *acov_tail = nullptr, *acov_total = nullptr, *acov_near = nullptr; long long acov_n = 0;
+    // pooled covariance (KLARA_MON_COVARIANCE, klara_cov.h): the slabs' cross-products and sums, the pivot, the finalized mean | M; saved steps consumed
+    KCovGeom cov = {}; double *cov_S = nullptr, *cov_T = nullptr, *cov_pivot = nullptr, *cov_out = nullptr; long long cov_n = 0;
     double *hist_lt = nullptr, *hist_g = nullptr, *hist_ll = nullptr, *hist_lp = nullptr;
     unsigned long long* clock_probe = nullptr;        // pair-transposed kernels: (s_memtime, s_memrealtime) at the end / start of one workgroup of the last launch
     bool pair_enqueued = false;                       // a launch of this handle has enqueued both kernel families (their one-time scratch set-up is behind us)

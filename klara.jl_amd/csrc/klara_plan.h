@@ -56,6 +56,7 @@ struct KlaraPlan {
     int modes[2] = { 0, 0 }, nmodes = 1;                       // the k_transitions MODE values the job launches (see launch_steps)
     bool q4_ok = false; int np4 = 0;                           // kind 3: the 4-lanes-per-chain kernels run the job too, np4 pairs per lane
     bool slice_free = false; int slice_machines = KLARA_SLICEF_DEFAULT_NM;   // kind 3 slice sampler: lanes out of lockstep, element machines per lane
+    bool cov = false;                      // KLARA_MON_COVARIANCE: a consumer of the saved samples (klara_cov.h); stripped from the monitor word the kernels get
     int nparts = 1, family = 1;            // kind 3: chain partitions on streams of their own; kernel family of launches of several transitions (0: 4 lanes, 1: G, -1: KAuto)
     double auto_threshold = 0.06;   // acceptance above which a device-decided launch keeps resident sums (8 lanes) — the measured crossover: the 4-lane kernels' folds are atomic
                                     // adds since round 4 (flat to ~4.5 % acceptance: profiles/r4_acceptance_cost_atomic.txt; round 3's folds crossed at 0.12, r3_acceptance_cost_probe.txt)
@@ -100,8 +101,8 @@ static bool diagt_eligible(const klara_desc& d, const KlaraOverrides& o)
 // launch: the launch length and the kernel choice come from this one predicate)
 static bool slice_free_eligible(const klara_desc& d, const KlaraOverrides& o, bool plain)
 {
-    const uint32_t lane_local = KLARA_MON_ACCEPT | KLARA_MON_SUMMARIES | KLARA_MON_HISTORY | KLARA_MON_HIST_LT;
-    const bool values_kept = (d.monitor & KLARA_MON_HISTORY) != 0 || d.acov_maxlag > 0;       // (the log-target history is formed from the saved values)
+    const uint32_t lane_local = KLARA_MON_ACCEPT | KLARA_MON_SUMMARIES | KLARA_MON_HISTORY | KLARA_MON_HIST_LT | KLARA_MON_COVARIANCE;       // (the last one: a consumer's flag, no kernel sees it)
+    const bool values_kept = (d.monitor & KLARA_MON_HISTORY) != 0 || d.acov_maxlag > 0 || (d.monitor & KLARA_MON_COVARIANCE) != 0;       // (the log-target history is formed from the saved values)
     return diagt_eligible(d, o) && d.sampler == KLARA_SAMPLER_SLICE && plain && !o.slice_lockstep &&
            (d.monitor & ~lane_local) == 0 && (!(d.monitor & KLARA_MON_HIST_LT) || values_kept);
 }
@@ -292,7 +293,9 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     KlaraPlan& p = *out;
     p = KlaraPlan();
     klara_desc d = desc;
-    if (d.acov_maxlag > 0) d.monitor |= KLARA_MON_HISTORY;       // (the streaming autocovariances keep values: klara_create turns the value history on)
+    p.cov = (d.monitor & KLARA_MON_COVARIANCE) != 0;
+    d.monitor &= ~(uint32_t)KLARA_MON_COVARIANCE;                // (a consumer's flag: the kernels and the run-time compiler never see it)
+    if (d.acov_maxlag > 0 || p.cov) d.monitor |= KLARA_MON_HISTORY;       // (the streaming autocovariances and the pooled covariance keep values: klara_create turns the value history on)
     const int D = d.ndims;
     p.plain = !cnt_predicate(d) && d.tuner_mode == KLARA_TUNE_PER_CHAIN && d.tuner != KLARA_TUNER_DUAL_AVERAGING;
     // plain and nothing monitored -> MODE 3 and its one-transition-per-launch form 7; plain -> 1; general -> 0
@@ -301,6 +304,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     p.slice_free = slice_free_eligible(d, o, p.plain);
     p.slice_machines = o.slice_machines;
     p.steps_per_launch = d.steps_per_launch > 0 ? d.steps_per_launch : p.slice_free ? KLARA_DEFAULT_STEPS_PER_LAUNCH_SLICE : KLARA_DEFAULT_STEPS_PER_LAUNCH;
+    if (p.cov && D > KLARA_COV_MAX_DIMS) return KLARA_ERR_UNSUPPORTED;
 
     if (d.sampler == KLARA_SAMPLER_SMMALA && !smmala_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
     if (d.sampler == KLARA_SAMPLER_RAM && !ram_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
@@ -342,7 +346,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
         int np = groups >= 4096 ? 2 : 1;                       // >= one full round of wavefronts (4 per SIMD) per partition
         if (d.nstreams >= 1 && d.nstreams <= 4) np = d.nstreams;
         if (d.tuner_mode == KLARA_TUNE_POOLED) np = 1;         // the pooled tuner update sits between launches, on one stream
-        if (d.acov_maxlag > 0) np = 1;                         // ... and so does the consumer of the launch's saved samples
+        if (d.acov_maxlag > 0 || p.cov) np = 1;                // ... and so does the consumer of the launch's saved samples
         if (np > groups) np = (int)groups;
         p.nparts = np;
         // which kernel family runs a launch (q4_ok jobs: same bits either way); with running sums and no klara_desc.sparse_moves, the device decides

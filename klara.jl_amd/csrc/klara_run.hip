@@ -122,6 +122,11 @@ static klara_status init_common(klara_handle* h)
         HIPCHK(hipMemsetAsync(h->acov_total, 0, N * D * sizeof(double), st));
     }
     h->acov_n = 0;
+    if (h->cov_S) {
+        HIPCHK(hipMemsetAsync(h->cov_S, 0, klara_cov_S_elems(h->cov) * sizeof(double), st)); HIPCHK(hipMemsetAsync(h->cov_T, 0, klara_cov_T_elems(h->cov) * sizeof(double), st));
+        HIPCHK(hipMemsetAsync(h->cov_pivot, 0, D * sizeof(double), st));
+    }
+    h->cov_n = 0;
     // tuner_state: samplers.jl:29-45 — step per sampler, accepted = proposed = 0, totproposed = period
     const double step0 = sampler_step0(d);
     hipLaunchKernelGGL(k_fill_tune, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, st, h->tune_step,
@@ -435,11 +440,11 @@ struct RunCursor { long long steps_done, m_prop, m_tot, bm_count; };
 struct PlannedLaunch { long long k; int save_phase0; long long save_col0; bool tune_after, bm_close_after; long long saved; };
 
 // columns of the history ring of a job (0: every saved step is kept) — klara_desc.hist_ring_cols, or the 32-column value ring the
-// streaming autocovariances keep for themselves when no value history was asked for
+// streaming autocovariances and the pooled covariance keep for themselves when no value history was asked for
 static long long ring_cols(const klara_desc& d)
 {
     long long r = d.hist_ring_cols;
-    if (d.acov_maxlag > 0 && !(d.monitor & KLARA_MON_HISTORY) && r == 0) r = 32;
+    if ((d.acov_maxlag > 0 || (d.monitor & KLARA_MON_COVARIANCE)) && !(d.monitor & KLARA_MON_HISTORY) && r == 0) r = 32;
     const long long npost = (d.nsteps - d.burnin - 1) / d.thinning + 1;
     return (r > 0 && r < npost) ? r : 0;
 }
@@ -535,6 +540,13 @@ extern "C" klara_status klara_run_async(klara_handle* h, int64_t nsteps)
             err = launch_acov_update(h->stream, h->hist, h->acov_S, h->acov_head, h->acov_tail, h->acov_near, h->acov_total, h->acov_n, h->acov_W,
                                      (long long)d.nchains * d.ndims, pl.save_col0, pl.saved);
             h->acov_n += pl.saved;
+        }
+        if (err == hipSuccess && h->cov_S && pl.saved > 0) {                    // ... and so does the pooled covariance (klara_cov.h)
+            if (h->cov_n == 0)                                                  // the pivot: local chain 0's first saved sample, before the ring overwrites it
+                err = hipMemcpyAsync(h->cov_pivot, h->hist + (size_t)pl.save_col0 * (size_t)d.nchains * (size_t)d.ndims, (size_t)d.ndims * sizeof(double),
+                                     hipMemcpyDeviceToDevice, h->stream);
+            if (err == hipSuccess) err = klara_cov_launch_update(h->cov, h->hist, pl.save_col0, pl.saved, h->cov_pivot, h->cov_S, h->cov_T, h->stream);
+            h->cov_n += pl.saved;
         }
         if (err != hipSuccess) break;
         advance_cursor(d, cur, pl);

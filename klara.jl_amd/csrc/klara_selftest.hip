@@ -349,3 +349,100 @@ extern "C" klara_status klara_check_custom_target_softabs(const char* src, int32
 }
 
 extern "C" const char* klara_compile_log(void) { return klara_jit_log(); }
+
+// The pooled covariance kernels on a caller's value history: klara_cov_launch_update launch by launch with col0 running through the history, as klara_run
+// issues them (the pivot copied before the first, an empty launch skipped), then klara_cov_launch_finalize; (b) the same on every shard's own history and
+// the rank-local halves of klara_gather_covariance's between-rank merge, every all-reduce replaced by a host sum over the ranks in ascending order from 0.
+static hipError_t selftest_cov_one(DeviceArrays& mem, const double* hist, long long N, long long c0, long long Nr, int D, long long ncols, int nsplits,
+                                   const int64_t* splits, double* out, hipStream_t st)
+{
+    KCovGeom g;
+    if (!klara_cov_plan(Nr, D, &g)) return hipErrorInvalidValue;
+    const size_t nd = (size_t)Nr * D;
+    double *dh = nullptr, *S = nullptr, *T = nullptr, *pivot = nullptr;
+    hipError_t e = mem.alloc(&dh, (size_t)ncols * nd);
+    if (e == hipSuccess) e = mem.alloc(&S, klara_cov_S_elems(g));
+    if (e == hipSuccess) e = mem.alloc(&T, klara_cov_T_elems(g));
+    if (e == hipSuccess) e = mem.alloc(&pivot, (size_t)D);
+    // the shard's chains as a history of their own: column t at dh + t Nr D
+    if (e == hipSuccess) e = hipMemcpy2D(dh, nd * sizeof(double), hist + (size_t)c0 * D, (size_t)N * D * sizeof(double), nd * sizeof(double), (size_t)ncols,
+                                         hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(S, 0, klara_cov_S_elems(g) * sizeof(double));     // (what klara_set_state / klara_reset leave)
+    if (e == hipSuccess) e = hipMemset(T, 0, klara_cov_T_elems(g) * sizeof(double));
+    long long col0 = 0;
+    for (int j = 0; j < nsplits && e == hipSuccess; ++j) {
+        if (splits[j] > 0) {
+            if (col0 == 0) e = hipMemcpyAsync(pivot, dh, (size_t)D * sizeof(double), hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess) e = klara_cov_launch_update(g, dh, col0, (long long)splits[j], pivot, S, T, st);
+        }
+        col0 += splits[j];
+    }
+    if (e == hipSuccess) e = klara_cov_launch_finalize(g, S, T, pivot, (double)((unsigned long long)ncols * (unsigned long long)Nr), out, st);
+    return e;
+}
+
+extern "C" klara_status klara_selftest_covariance(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
+                                                  const int64_t* splits, int32_t nranks, const int64_t* bounds, double* mean, double* m2, double* ranks_mean,
+                                                  double* ranks_m2, uint64_t* ranks_counters)
+{
+    if (!hist || !splits || !bounds || nchains <= 0 || ndims < 1 || ndims > KLARA_COV_MAX_DIMS || ncols < 1 || nsplits <= 0 || nranks < 1) return KLARA_ERR_INVALID_ARG;
+    long long sum = 0;
+    for (int j = 0; j < nsplits; ++j) {
+        if (splits[j] < 0 || splits[j] > KLARA_COV_MAX_COLS) return KLARA_ERR_INVALID_ARG;
+        sum += splits[j];
+    }
+    if (sum != ncols) return KLARA_ERR_INVALID_ARG;
+    if (bounds[0] != 0 || bounds[nranks] != nchains) return KLARA_ERR_INVALID_ARG;
+    for (int r = 0; r < nranks; ++r) if (bounds[r + 1] <= bounds[r]) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    const size_t D = (size_t)ndims, DD = D * D, per = 3 * D + DD;        // per rank: mean_r, M_r, n_r mean_r, mean
+    const hipStream_t st = 0;
+    DeviceArrays mem;
+    double *out = nullptr, *rb = nullptr, *dw = nullptr; unsigned long long* dnt = nullptr;
+    hipError_t e = mem.alloc(&out, D + DD);
+    if (e == hipSuccess) e = mem.alloc(&rb, (size_t)nranks * per);
+    if (e == hipSuccess) e = mem.alloc(&dw, D);
+    if (e == hipSuccess) e = mem.alloc(&dnt, 1);
+    // (a)
+    if (e == hipSuccess) e = selftest_cov_one(mem, hist, nchains, 0, nchains, ndims, ncols, nsplits, splits, out, st);
+    // (b) every rank's mean_r, M_r and n_r mean_r
+    unsigned long long cnt[2] = { 0, 0 };
+    for (int r = 0; r < nranks && e == hipSuccess; ++r) {
+        const long long Nr = bounds[r + 1] - bounds[r];
+        double* b = rb + (size_t)r * per;
+        e = selftest_cov_one(mem, hist, nchains, bounds[r], Nr, ndims, ncols, nsplits, splits, b, st);
+        if (e == hipSuccess) e = moments_scale_async(st, b + D + DD, b, (double)((unsigned long long)ncols * (unsigned long long)Nr), ndims);
+        cnt[0] += (unsigned long long)ncols * (unsigned long long)Nr; cnt[1] += (unsigned long long)Nr;
+    }
+    std::vector<double> hout(D + DD), hrb((size_t)nranks * per), acc(DD);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(hout.data(), out, hout.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) {                                                                // the all-reduce of n_r mean_r (and of the counters: cnt)
+        for (size_t j = 0; j < D; ++j) acc[j] = 0.0;
+        for (int r = 0; r < nranks; ++r)
+            for (size_t j = 0; j < D; ++j) acc[j] = acc[j] + hrb[(size_t)r * per + D + DD + j];
+        e = hipMemcpy(dw, acc.data(), D * sizeof(double), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(dnt, &cnt[0], sizeof(cnt[0]), hipMemcpyHostToDevice);
+    for (int r = 0; r < nranks && e == hipSuccess; ++r) {
+        double* b = rb + (size_t)r * per;
+        e = klara_cov_launch_between(st, b + D, b, dw, dnt, (double)((unsigned long long)ncols * (unsigned long long)(bounds[r + 1] - bounds[r])), ndims,
+                                     b + 2 * D + DD);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
+    const bool clean = mem.release();
+    if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
+    if (mean) memcpy(mean, hout.data(), D * sizeof(double));
+    if (m2) memcpy(m2, hout.data() + D, DD * sizeof(double));
+    if (ranks_mean) memcpy(ranks_mean, hrb.data() + 2 * D + DD, D * sizeof(double));      // (every rank holds the same mean)
+    if (ranks_m2) {                                                                       // the all-reduce of M_r + n_r d d'
+        for (size_t j = 0; j < DD; ++j) acc[j] = 0.0;
+        for (int r = 0; r < nranks; ++r)
+            for (size_t j = 0; j < DD; ++j) acc[j] = acc[j] + hrb[(size_t)r * per + D + j];
+        memcpy(ranks_m2, acc.data(), DD * sizeof(double));
+    }
+    if (ranks_counters) { ranks_counters[0] = cnt[0]; ranks_counters[1] = cnt[1]; }
+    return KLARA_OK;
+}

@@ -199,6 +199,51 @@ def allreduce_moments(local: Dict[str, np.ndarray], group=None, device=None) -> 
     return out
 
 
+def gather_engine_covariance_klara(engine, comm: KlaraComm) -> Dict[str, np.ndarray]:
+    """The pooled covariance of every rank's chains through the C ABI alone: klara_gather_covariance(h, comm, ...) — the ranks' (n, mean, M)
+    merged by three RCCL all-reduces on the job's stream.  Keys: mean[D], m2[D, D], nsamples, nchains and, from two samples on, cov."""
+    mean, m2, ns, nc = engine.pooled_covariance(comm.handle)
+    out = {"mean": mean, "m2": m2, "nsamples": float(ns), "nchains": float(nc)}
+    if ns > 1:
+        out["cov"] = m2 / (ns - 1)
+    return out
+
+
+def allreduce_covariance(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
+    """Chan's merge of per-rank covariance accumulators, the D x D form of allreduce_moments: `local` holds mean[D], m2[D, D], nsamples (and
+    nchains) of this rank's chains (Engine.pooled_covariance without a communicator).  Three SUM all-reduces — the counters, n_r mean_r,
+    M_r + n_r d d' with d = mean_r - mean — in that order on every rank.  Works without torch.distributed initialised (single process)."""
+    import torch
+    import torch.distributed as dist
+
+    mean_l = np.asarray(local["mean"], dtype=np.float64).ravel()
+    D = mean_l.size
+    m2_l = np.asarray(local["m2"], dtype=np.float64).reshape(D, D)
+    n_l = float(local["nsamples"])
+    live = dist.is_available() and dist.is_initialized()
+    if live and device is None:
+        device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+
+    def reduce_sum(buf: np.ndarray) -> np.ndarray:
+        if not live:
+            return buf
+        t = torch.from_numpy(np.ascontiguousarray(buf)).to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        return t.cpu().numpy()
+
+    cnt = reduce_sum(np.array([n_l, float(local.get("nchains", 0.0))], dtype=np.float64))   # (exact below 2^53)
+    ns, nc = cnt
+    with np.errstate(all="ignore"):
+        wsum = reduce_sum(n_l * mean_l)
+        mean = wsum / ns if ns > 0 else np.zeros_like(wsum)
+        d = mean_l - mean
+        m2 = reduce_sum(m2_l + n_l * (d[:, None] * d[None, :]))
+    out = {"nsamples": ns, "nchains": nc, "mean": mean, "m2": m2}
+    if ns > 1:
+        out["cov"] = m2 / (ns - 1)
+    return out
+
+
 def allreduce_summaries(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
     """The same exchange for a caller that holds pooled RAW sums: `local` = sum[D], sumsq[D], naccept, ntransitions, nsamples of this
     rank's chains.  Returns the global sums plus the posterior moments (mean, var) and the acceptance rate; the variance comes from

@@ -425,6 +425,14 @@ class Engine:
                                                C.byref(nc)), "klara_gather_moments")
         return mean, m2, int(ns.value), int(na.value), int(nt.value), int(nc.value)
 
+    def pooled_covariance(self, comm=None):
+        """(mean[D], M[D, D], nsamples, nchains) over this handle's chains — or, with a klara_comm handle, over every rank's: M = sum (x - mean)(x - mean)'
+        over all chains and saved steps, accumulated while sampling (monitor bit MON_COVARIANCE, klara_gather_covariance); cov = M / (nsamples - 1)."""
+        mean = np.empty(self.ndims); m2 = np.empty((self.ndims, self.ndims))
+        ns, nc = C.c_uint64(0), C.c_uint64(0)
+        L.check(self._lib.klara_gather_covariance(self._h, comm, mean.ctypes.data, m2.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_covariance")
+        return mean, m2, int(ns.value), int(nc.value)
+
     def chain(self, local_chain: int) -> np.ndarray:
         """One chain's saved values in Klara's NState layout: (ndims, nsaved), column-major."""
         n = C.c_int64(0)

@@ -74,6 +74,14 @@ def iact(v, vtype: str = "imse", *args) -> float:
     return float(mcvar(v, vtype, *args) / mcvar(v, "iid"))
 
 
+def pooled_cov(values) -> np.ndarray:
+    """cov of the concatenated histories: `values` is (nchains, ndims, nsaved) — or a sequence of (ndims, nsaved) chains in NState layout —;
+    the literal NumPy form of what a job with covariance=True accumulates on the device (klara_gather_covariance's m2 / (n - 1))."""
+    x = np.concatenate([np.asarray(v, dtype=np.float64) for v in values], axis=1)      # (ndims, nchains * nsaved)
+    xc = x - x.mean(axis=1, keepdims=True)
+    return (xc @ xc.T) / (x.shape[1] - 1)
+
+
 def _per_dim(fn, value: np.ndarray, *args) -> np.ndarray:
     value = np.asarray(value)
     return np.array([fn(value[i, :], *args) for i in range(value.shape[0])])
