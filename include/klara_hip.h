@@ -566,8 +566,9 @@ klara_status klara_selftest_chain_stats(int32_t device, int64_t nchains, int32_t
  * (a) over all chains: pooled_sum, pooled_sumsq (ndims each; with_sums = 0 leaves the device's sum slots untouched: they start as the values these two
  * arrays hold on entry and are handed back as they are), accept_total, and the pooled moments mean, m2 (ndims each).
  * (b) the chains cut into nranks shards, rank r owning [bounds[r], bounds[r + 1]) with 0 = bounds[0] < ... < bounds[nranks] = nchains: every shard's
- * moments and the two rank-local steps of klara_gather_moments' between-rank merge, each all-reduce replaced by a host sum over the ranks in ascending
- * order starting from zero: ranks_mean, ranks_m2 (ndims each), ranks_counters[3] = accept total, saved samples, chains.
+ * moments staged as klara_gather_moments stages them, then that call's own between-rank merge — the one sequence the communicator path runs, over one
+ * staging buffer per simulated rank — with each all-reduce replaced by a host sum over the ranks in ascending order starting from zero, written back to
+ * every rank; read from rank 0: ranks_mean, ranks_m2 (ndims each), ranks_counters[3] = accept total, saved samples, chains.
  * Every output may be NULL.  KLARA_ERR_INVALID_ARG (before any launch) for a NULL input, nchains <= 0, ndims outside 1..1024, nsaved < 0 or bad bounds.
  * Tests compare the outputs bit for bit with a restatement of the order of operations and with exact rational arithmetic. */
 klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
@@ -580,8 +581,9 @@ klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndim
  * job path uses — launch j brings splits[j] saved steps (0..32 each), the splits sum to ncols — then finalized as klara_gather_covariance does:
  * (a) over all chains: mean (ndims), m2 (ndims x ndims).
  * (b) the chains cut into nranks shards, rank r owning [bounds[r], bounds[r + 1]) with 0 = bounds[0] < ... < bounds[nranks] = nchains: every shard accumulated
- * and finalized on its own (its pivot is its own first chain's first sample), then the between-rank merge with each all-reduce replaced by a host sum over
- * the ranks in ascending order starting from zero: ranks_mean (ndims), ranks_m2 (ndims x ndims), ranks_counters[2] = saved samples, chains.
+ * and finalized on its own (its pivot is its own first chain's first sample), then klara_gather_covariance's own between-rank merge (the same sequence, in
+ * its ndims x ndims form) with each all-reduce replaced by a host sum over the ranks in ascending order starting from zero, written back to every rank;
+ * read from rank 0: ranks_mean (ndims), ranks_m2 (ndims x ndims), ranks_counters[2] = saved samples, chains.
  * Every output may be NULL.  KLARA_ERR_INVALID_ARG (before any launch) for a NULL input, nchains <= 0, ndims outside 1..KLARA_COV_MAX_DIMS, ncols < 1, a
  * split outside 0..32, splits that do not sum to ncols or bad bounds. */
 klara_status klara_selftest_covariance(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,

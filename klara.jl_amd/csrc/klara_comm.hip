@@ -8,7 +8,7 @@ struct klara_comm {
     void* dl = nullptr;
     ncclComm_t comm = nullptr;
     int nranks = 0, rank = 0, device = 0;
-    double* buf = nullptr; size_t cap = 0;                      // device staging: 2D doubles + 4 u64
+    double* buf = nullptr; size_t cap = 0;                      // device staging of a gather call (klara_merge.h MergeLayout)
     ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
     ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
     ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
@@ -76,6 +76,43 @@ extern "C" klara_status klara_comm_destroy(klara_comm* c)
     delete c;
     return KLARA_OK;
 }
+// grow c->buf to n doubles
+static hipError_t comm_reserve(klara_comm* c, size_t n)
+{
+    if (c->cap >= n) return hipSuccess;
+    if (c->buf) (void)dfree(c->buf);
+    c->buf = nullptr; c->cap = 0;
+    const hipError_t e = dalloc(&c->buf, n);
+    if (e == hipSuccess) c->cap = n;
+    return e;
+}
+// A gather call's fixed sequence of collectives on c->buf: a rank that returned at its first local failure would leave the others waiting in
+// theirs.  Local errors are remembered, every collective is still entered, the status is reported after the last one (finish).
+struct CommSeq {
+    klara_comm* c; hipStream_t st; bool bad = false;
+    void H(hipError_t e) { if (e != hipSuccess) bad = true; }
+    bool reduce(size_t off, size_t n, bool is_u64)              // in-place all-reduce of c->buf[off, off + n) on the job's stream — latency-bound
+    {
+        void* p = c->buf + off;
+        const bool ok = c->AllReduce(p, p, n, is_u64 ? ncclUint64 : ncclDouble, ncclSum, c->comm, st) == ncclSuccess;
+        if (!ok) bad = true;
+        return ok;
+    }
+    bool finish(std::vector<double>& host)                      // the head of c->buf to the host; false: something failed on the way
+    {
+        H(hipMemcpyAsync(host.data(), c->buf, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        H(hipStreamSynchronize(st));
+        return !bad;
+    }
+};
+// the counters of a gather call in MergeLayout's slots (the accept total comes from the device)
+static void local_counters(const klara_handle* h, long long nsaved, unsigned long long cnt[MergeLayout::NCOUNTERS])
+{
+    const unsigned long long N = (unsigned long long)h->d.nchains;
+    cnt[MergeLayout::ACCEPTED] = 0; cnt[MergeLayout::TRANSITIONS] = (unsigned long long)h->steps_done * N;
+    cnt[MergeLayout::SAMPLES] = (unsigned long long)nsaved * N; cnt[MergeLayout::CHAINS] = N;
+}
+
 extern "C" klara_status klara_gather_summaries(klara_handle* h, klara_comm* c, double* sum, double* sumsq, uint64_t* naccept,
                                                uint64_t* ntransitions, uint64_t* nsamples, uint64_t* nchains)
 {
@@ -84,68 +121,66 @@ extern "C" klara_status klara_gather_summaries(klara_handle* h, klara_comm* c, d
     if ((sum || sumsq) && !h->sum) return KLARA_ERR_STATE;
     HIPCHK(hipSetDevice(h->d.device));
     const size_t D = (size_t)h->d.ndims;
-    if (c->cap < 2 * D + 4) {
-        if (c->buf) (void)dfree(c->buf);
-        c->buf = nullptr; c->cap = 0;
-        HIPCHK(dalloc(&c->buf, 2 * D + 4));
-        c->cap = 2 * D + 4;
-    }
-    // From here on every rank is inside a fixed sequence of collectives: a rank that returned at its first local failure would leave the others
-    // waiting in theirs.  Local errors are remembered, every collective is still entered, the status is reported after the last one.
-    bool bad = false;
-    const auto H = [&](hipError_t e) { if (e != hipSuccess) bad = true; };
-    H(hipMemsetAsync(c->buf, 0, (2 * D + 4) * sizeof(double), h->stream));
-    H(pool_summaries_async(h, h->sum != nullptr, c->buf));
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(c->buf + 2 * D);
-    const unsigned long long local[3] = { (unsigned long long)h->steps_done * (unsigned long long)h->d.nchains,
-                                          (unsigned long long)h->nsaved * (unsigned long long)h->d.nchains,
-                                          (unsigned long long)h->d.nchains };
-    H(hipMemcpyAsync(cnt + 1, local, sizeof(local), hipMemcpyHostToDevice, h->stream));
-    // two in-place all-reduces on the job's stream: 2D doubles, 4 counters — (2D + 4) x 8 B per rank, latency-bound
-    if (c->AllReduce(c->buf, c->buf, 2 * D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-    if (c->AllReduce(cnt, cnt, 4, ncclUint64, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-    std::vector<double> host(2 * D + 4);
-    H(hipMemcpyAsync(host.data(), c->buf, (2 * D + 4) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    H(hipStreamSynchronize(h->stream));
-    if (bad) return KLARA_ERR_HIP;
+    const MergeLayout L{ D, D };                                // no merge here: sum | sumsq | 4 counters, the layout's head up to wsum
+    HIPCHK(comm_reserve(c, L.wsum()));
+    CommSeq q{ c, h->stream };
+    q.H(hipMemsetAsync(c->buf, 0, L.wsum() * sizeof(double), h->stream));
+    q.H(pool_summaries_async(h, h->sum != nullptr, c->buf));
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    local_counters(h, h->nsaved, cnt);
+    q.H(hipMemcpyAsync(c->buf + L.counters() + 1, cnt + 1, 3 * sizeof(cnt[0]), hipMemcpyHostToDevice, h->stream));
+    q.reduce(0, L.counters(), false);
+    q.reduce(L.counters(), MergeLayout::NCOUNTERS, true);
+    std::vector<double> host(L.wsum());
+    if (!q.finish(host)) return KLARA_ERR_HIP;
     if (sum) memcpy(sum, host.data(), D * sizeof(double));
     if (sumsq) memcpy(sumsq, host.data() + D, D * sizeof(double));
-    unsigned long long out[4];
-    memcpy(out, host.data() + 2 * D, sizeof(out));
-    if (naccept) *naccept = out[0];
-    if (ntransitions) *ntransitions = out[1];
-    if (nsamples) *nsamples = out[2];
-    if (nchains) *nchains = out[3];
+    memcpy(cnt, host.data() + L.counters(), sizeof(cnt));
+    if (naccept) *naccept = cnt[MergeLayout::ACCEPTED];
+    if (ntransitions) *ntransitions = cnt[MergeLayout::TRANSITIONS];
+    if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
+    if (nchains) *nchains = cnt[MergeLayout::CHAINS];
     return KLARA_OK;
 }
 
-// the between-rank merge of the pooled moments (klara_monitors.hip pool_moments_async has each rank's): n_r mean_r, to be summed over the ranks ...
+// ---- the rank-local steps of the between-rank merge (klara_merge.h): n_r mean_r, to be summed over the ranks ...
 __global__ void k_scale(double* __restrict__ dst, const double* __restrict__ src, double f, int n)
 {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) dst[j] = f * src[j];
 }
-// rank-local part of the between-rank merge: buf[j] = mean_r -> M2_r + n_r (mean_r - mean)^2 with mean = wsum[j] / ntot
-__global__ void k_moments_between(double* __restrict__ m2, const double* mean_r, const double* __restrict__ wsum,
-                                  const unsigned long long* __restrict__ ntot, double n_r, int D, double* mean_out)   // (mean_out may be mean_r)
+// ... and, with wsum and ntot summed: mean = wsum / ntot, M += n_r d_i d_j with d = mean_r - mean.  K = D D: every (i, j) of the matrix; K = D: its
+// diagonal, d_i and d_j the same value
+__global__ __launch_bounds__(256) void k_merge_between(double* __restrict__ M, const double* __restrict__ mean_r, const double* __restrict__ wsum,
+                                                       const unsigned long long* __restrict__ ntot, double n_r, int D, int K, double* __restrict__ mean_out)
 {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= D) return;
-    const double nt = (double)*ntot;
-    const double mean = nt > 0.0 ? wsum[j] / nt : 0.0, d = mean_r[j] - mean;       // (no saved sample on any rank: zeros, as chan_merge leaves them without a communicator)
-    mean_out[j] = mean;
-    m2[j] = m2[j] + n_r * (d * d);
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= K) return;
+    const int i = K == D ? idx : idx / D, j = K == D ? idx : idx - i * D;
+    const double nt = (double)*ntot;                            // (no saved sample on any rank: zeros, as chan_merge leaves them without a communicator)
+    const double mi = nt > 0.0 ? wsum[i] / nt : 0.0, mj = nt > 0.0 ? wsum[j] / nt : 0.0;
+    const double di = mean_r[i] - mi, dj = mean_r[j] - mj;
+    if (i == j) mean_out[i] = mi;
+    M[idx] = M[idx] + n_r * (di * dj);
 }
-hipError_t moments_scale_async(hipStream_t stream, double* wsum, const double* mean_r, double n_r, int D)
+hipError_t merge_scale_async(hipStream_t st, const MergeLayout& L, double* buf, double n_r)
 {
-    hipLaunchKernelGGL(k_scale, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, stream, wsum, mean_r, n_r, D);
-    return hipGetLastError();
+    return klara_start(k_scale, dim3((unsigned)((L.D + 255) / 256)), dim3(256), 0, st, buf + L.wsum(), buf + L.mean_r(), n_r, (int)L.D);
 }
-hipError_t moments_between_async(hipStream_t stream, double* m2, const double* mean_r, const double* wsum, const unsigned long long* ntot, double n_r,
-                                 int D, double* mean_out)
+hipError_t merge_between_async(hipStream_t st, const MergeLayout& L, double* buf, double n_r)
 {
-    hipLaunchKernelGGL(k_moments_between, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, stream, m2, mean_r, wsum, ntot, n_r, D, mean_out);
-    return hipGetLastError();
+    const unsigned long long* ntot = reinterpret_cast<const unsigned long long*>(buf + L.counters()) + MergeLayout::SAMPLES;
+    return klara_start(k_merge_between, dim3((unsigned)((L.K + 255) / 256)), dim3(256), 0, st, buf + L.M(), buf + L.mean_r(), buf + L.wsum(), ntot, n_r,
+                       (int)L.D, (int)L.K, buf + L.mean());
+}
+// the merge of this rank's staged mean_r | M_r | counters in c->buf with the other ranks', then the whole buffer to the host and the summed counters to cnt
+static bool comm_merge(CommSeq& q, const MergeLayout& L, unsigned long long cnt[MergeLayout::NCOUNTERS], std::vector<double>& host)
+{
+    double* buf = q.c->buf;
+    const double n_r = (double)cnt[MergeLayout::SAMPLES];
+    if (!merge_ranks(q.st, L, 1, &buf, &n_r, [&](size_t off, size_t n, bool is_u64) { return q.reduce(off, n, is_u64); })) q.bad = true;
+    if (q.finish(host)) memcpy(cnt, host.data() + L.counters(), MergeLayout::NCOUNTERS * sizeof(cnt[0]));
+    return !q.bad;
 }
 
 extern "C" klara_status klara_gather_moments(klara_handle* h, klara_comm* c, double* mean, double* m2, uint64_t* nsamples,
@@ -155,63 +190,43 @@ extern "C" klara_status klara_gather_moments(klara_handle* h, klara_comm* c, dou
     if (!h->have_state || !h->sum) return KLARA_ERR_STATE;
     HIPCHK(hipSetDevice(h->d.device));
     const size_t D = (size_t)h->d.ndims;
-    unsigned long long cnt[4] = { 0, (unsigned long long)h->steps_done * (unsigned long long)h->d.nchains,
-                                  (unsigned long long)h->nsaved * (unsigned long long)h->d.nchains, (unsigned long long)h->d.nchains };
-    std::vector<double> host(2 * D + 1);
-    if (!c) {                                                               // this handle's chains only
+    const MergeLayout L{ D, D };
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    local_counters(h, h->nsaved, cnt);
+    std::vector<double> host(L.size());
+    if (!c) {                                                               // this handle's chains only: mean | M2 | accept total
         HIPCHK(pool_moments_async(h, h->pooled_out));
-        HIPCHK(hipMemcpyAsync(host.data(), h->pooled_out, (2 * D + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(host.data(), h->pooled_out, (L.counters() + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        memcpy(&cnt[0], host.data() + 2 * D, sizeof(cnt[0]));
+        memcpy(&cnt[0], host.data() + L.counters(), sizeof(cnt[0]));
     } else {
-        // device staging: [0, D) mean_r -> mean, [D, 2D) M2_r -> M2, [2D] accept total, then [2D+1, 2D+4) counters, [2D+4, 3D+4) n_r mean_r
-        if (c->cap < 3 * D + 4) {
-            if (c->buf) (void)dfree(c->buf);
-            c->buf = nullptr; c->cap = 0;
-            HIPCHK(dalloc(&c->buf, 3 * D + 4));
-            c->cap = 3 * D + 4;
-        }
-        // (as in klara_gather_summaries: once the sequence of collectives starts, every rank goes through all of it; errors are reported after the last)
-        bool bad = false;
-        const auto H = [&](hipError_t e) { if (e != hipSuccess) bad = true; };
-        H(pool_moments_async(h, c->buf));
-        unsigned long long* dcnt = reinterpret_cast<unsigned long long*>(c->buf + 2 * D);
-        H(hipMemcpyAsync(dcnt + 1, cnt + 1, 3 * sizeof(cnt[0]), hipMemcpyHostToDevice, h->stream));
-        double* wsum = c->buf + 2 * D + 4;
-        const double n_r = (double)cnt[2];
-        H(moments_scale_async(h->stream, wsum, c->buf, n_r, (int)D));
-        // three in-place all-reduces on the job's stream: 4 counters, D weighted means, D sums of squares — latency-bound
-        if (c->AllReduce(dcnt, dcnt, 4, ncclUint64, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        if (c->AllReduce(wsum, wsum, D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        H(moments_between_async(h->stream, c->buf + D, c->buf, wsum, dcnt + 2, n_r, (int)D, c->buf));
-        if (c->AllReduce(c->buf + D, c->buf + D, D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        std::vector<double> hostc(2 * D + 4);
-        H(hipMemcpyAsync(hostc.data(), c->buf, (2 * D + 4) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        H(hipStreamSynchronize(h->stream));
-        if (bad) return KLARA_ERR_HIP;
-        memcpy(host.data(), hostc.data(), 2 * D * sizeof(double));
-        memcpy(cnt, hostc.data() + 2 * D, sizeof(cnt));
+        HIPCHK(comm_reserve(c, L.size()));
+        CommSeq q{ c, h->stream };
+        q.H(pool_moments_async(h, c->buf));                                 // mean_r | M2_r | accept total = counter slot 0
+        q.H(hipMemcpyAsync(c->buf + L.counters() + 1, cnt + 1, 3 * sizeof(cnt[0]), hipMemcpyHostToDevice, h->stream));
+        if (!comm_merge(q, L, cnt, host)) return KLARA_ERR_HIP;
     }
-    if (mean) memcpy(mean, host.data(), D * sizeof(double));
-    if (m2) memcpy(m2, host.data() + D, D * sizeof(double));
-    if (naccept) *naccept = cnt[0];
-    if (ntransitions) *ntransitions = cnt[1];
-    if (nsamples) *nsamples = cnt[2];
-    if (nchains) *nchains = cnt[3];
+    if (mean) memcpy(mean, host.data() + (c ? L.mean() : L.mean_r()), D * sizeof(double));
+    if (m2) memcpy(m2, host.data() + L.M(), D * sizeof(double));
+    if (naccept) *naccept = cnt[MergeLayout::ACCEPTED];
+    if (ntransitions) *ntransitions = cnt[MergeLayout::TRANSITIONS];
+    if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
+    if (nchains) *nchains = cnt[MergeLayout::CHAINS];
     return KLARA_OK;
 }
 
-// The pooled covariance (klara_cov.h): this rank's (mean_r, M_r) from its accumulators, then — with a communicator — the D x D form of the merge above
+// The pooled covariance (klara_cov.h): this rank's (mean_r, M_r) from its accumulators, then — with a communicator — the D x D form of the same merge
 extern "C" klara_status klara_gather_covariance(klara_handle* h, klara_comm* c, double* mean, double* m2, uint64_t* nsamples, uint64_t* nchains)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;
     if (!h->have_state || !h->cov_S) return KLARA_ERR_STATE;
     HIPCHK(hipSetDevice(h->d.device));
     const size_t D = (size_t)h->d.ndims, DD = D * D;
-    unsigned long long cnt[4] = { 0, (unsigned long long)h->steps_done * (unsigned long long)h->d.nchains,
-                                  (unsigned long long)h->cov_n * (unsigned long long)h->d.nchains, (unsigned long long)h->d.nchains };
-    const double n_r = (double)cnt[2];
-    std::vector<double> host(D + DD);
+    const MergeLayout L{ D, DD };
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    local_counters(h, h->cov_n, cnt);
+    const double n_r = (double)cnt[MergeLayout::SAMPLES];
+    std::vector<double> host(L.size());
     // this rank's mean | M (before the first saved sample: zeros)
     const auto local = [&](double* out) -> hipError_t {
         if (h->cov_n == 0) return hipMemsetAsync(out, 0, (D + DD) * sizeof(double), h->stream);
@@ -222,38 +237,15 @@ extern "C" klara_status klara_gather_covariance(klara_handle* h, klara_comm* c, 
         HIPCHK(hipMemcpyAsync(host.data(), h->cov_out, (D + DD) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     } else {
-        // device staging: [0, D) mean_r, [D, D + DD) M_r -> M, 4 counters, [.. + D) n_r mean_r, [.. + D) mean
-        const size_t need = 3 * D + DD + 4;
-        if (c->cap < need) {
-            if (c->buf) (void)dfree(c->buf);
-            c->buf = nullptr; c->cap = 0;
-            HIPCHK(dalloc(&c->buf, need));
-            c->cap = need;
-        }
-        // (as in klara_gather_summaries: once the sequence of collectives starts, every rank goes through all of it; errors are reported after the last)
-        bool bad = false;
-        const auto H = [&](hipError_t e) { if (e != hipSuccess) bad = true; };
-        H(local(c->buf));
-        unsigned long long* dcnt = reinterpret_cast<unsigned long long*>(c->buf + D + DD);
-        H(hipMemcpyAsync(dcnt, cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream));
-        double* wsum = c->buf + D + DD + 4;
-        double* mean_out = wsum + D;
-        H(moments_scale_async(h->stream, wsum, c->buf, n_r, (int)D));
-        if (c->AllReduce(dcnt, dcnt, 4, ncclUint64, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        if (c->AllReduce(wsum, wsum, D, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        H(klara_cov_launch_between(h->stream, c->buf + D, c->buf, wsum, dcnt + 2, n_r, (int)D, mean_out));
-        if (c->AllReduce(c->buf + D, c->buf + D, DD, ncclDouble, ncclSum, c->comm, h->stream) != ncclSuccess) bad = true;
-        std::vector<double> hostc(need);
-        H(hipMemcpyAsync(hostc.data(), c->buf, need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        H(hipStreamSynchronize(h->stream));
-        if (bad) return KLARA_ERR_HIP;
-        memcpy(host.data(), hostc.data() + 2 * D + DD + 4, D * sizeof(double));
-        memcpy(host.data() + D, hostc.data() + D, DD * sizeof(double));
-        memcpy(cnt, hostc.data() + D + DD, sizeof(cnt));
+        HIPCHK(comm_reserve(c, L.size()));
+        CommSeq q{ c, h->stream };
+        q.H(local(c->buf));
+        q.H(hipMemcpyAsync(c->buf + L.counters(), cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream));
+        if (!comm_merge(q, L, cnt, host)) return KLARA_ERR_HIP;
     }
-    if (mean) memcpy(mean, host.data(), D * sizeof(double));
-    if (m2) memcpy(m2, host.data() + D, DD * sizeof(double));
-    if (nsamples) *nsamples = cnt[2];
-    if (nchains) *nchains = cnt[3];
+    if (mean) memcpy(mean, host.data() + (c ? L.mean() : L.mean_r()), D * sizeof(double));
+    if (m2) memcpy(m2, host.data() + L.M(), DD * sizeof(double));
+    if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
+    if (nchains) *nchains = cnt[MergeLayout::CHAINS];
     return KLARA_OK;
 }

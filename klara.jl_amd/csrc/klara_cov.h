@@ -53,6 +53,3 @@ hipError_t klara_cov_launch_update(const KCovGeom& g, const double* hist, long l
                                    hipStream_t st);
 // out = mean[D], M[D x D] from the accumulators of n = saved steps x N samples (n > 0)
 hipError_t klara_cov_launch_finalize(const KCovGeom& g, const double* S, const double* T, const double* pivot, double n, double* out, hipStream_t st);
-// rank-local part of the between-rank merge: M[i][j] += n_r d_i d_j with d = mean_r - mean, mean = wsum / ntot (0 when ntot is 0) -> mean_out
-hipError_t klara_cov_launch_between(hipStream_t st, double* M, const double* mean_r, const double* wsum, const unsigned long long* ntot, double n_r,
-                                    int D, double* mean_out);

@@ -199,24 +199,3 @@ hipError_t klara_cov_launch_finalize(const KCovGeom& g, const double* S, const d
     hipLaunchKernelGGL(k_cov_finalize, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, S, T, pivot, g.nslabs, g.D, g.MT, g.ntiles, n, out);
     return hipGetLastError();
 }
-
-// ------------------------------------------------------------------------------------------------------------------- between ranks
-__global__ __launch_bounds__(256) void k_cov_between(double* __restrict__ M, const double* __restrict__ mean_r, const double* __restrict__ wsum,
-                                                     const unsigned long long* __restrict__ ntot, double n_r, int D, double* __restrict__ mean_out)
-{
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= D * D) return;
-    const int i = idx / D, j = idx - i * D;
-    const double nt = (double)*ntot;
-    const double mi = nt > 0.0 ? wsum[i] / nt : 0.0, mj = nt > 0.0 ? wsum[j] / nt : 0.0;
-    const double di = mean_r[i] - mi, dj = mean_r[j] - mj;
-    if (i == j) mean_out[i] = mi;
-    M[idx] = M[idx] + n_r * (di * dj);
-}
-
-hipError_t klara_cov_launch_between(hipStream_t st, double* M, const double* mean_r, const double* wsum, const unsigned long long* ntot, double n_r,
-                                    int D, double* mean_out)
-{
-    hipLaunchKernelGGL(k_cov_between, dim3((unsigned)((D * D + 255) / 256)), dim3(256), 0, st, M, mean_r, wsum, ntot, n_r, D, mean_out);
-    return hipGetLastError();
-}

@@ -134,11 +134,8 @@ hipError_t pool_moments_async(hipStream_t stream, const double* sum, const doubl
 hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);      // ... with the handle's arrays, on its stream
 hipError_t pool_moments_async(klara_handle* h, double* out);
 
-// ---- klara_comm.hip: the rank-local halves of the between-rank merge of the pooled moments, around the all-reduces of klara_gather_moments
-// wsum[j] = n_r mean_r[j]
-hipError_t moments_scale_async(hipStream_t stream, double* wsum, const double* mean_r, double n_r, int D);
-// with wsum and *ntot summed over the ranks: mean_out[j] = wsum[j] / ntot (0 when ntot is 0), m2[j] = M2_r[j] + n_r (mean_r[j] - mean)^2  (mean_out may be mean_r)
-hipError_t moments_between_async(hipStream_t stream, double* m2, const double* mean_r, const double* wsum, const unsigned long long* ntot, double n_r,
-                                 int D, double* mean_out);
+// ---- klara_comm.hip: the between-rank merge of the pooled moments and the pooled covariance — its staging layout, its rank-local steps and the one
+// sequence of reductions that the gather calls and the simulated-rank self tests both run
+#include "klara_merge.h"
 
 #pragma GCC visibility pop

@@ -21,9 +21,8 @@ extern "C" klara_status klara_selftest_rocrand_blocks(int32_t device, uint64_t s
     HIPCHK(hipSetDevice(device));
     unsigned int* d = nullptr;
     HIPCHK(dalloc(&d, (size_t)4 * nblocks));
-    hipLaunchKernelGGL(k_rocrand_blocks, dim3((nblocks + 63) / 64), dim3(64), 0, 0, (unsigned long long)seed,
-                       (unsigned long long)subsequence, (unsigned long long)first_block, nblocks, d);
-    hipError_t e = hipGetLastError();
+    hipError_t e = klara_start(k_rocrand_blocks, dim3((nblocks + 63) / 64), dim3(64), 0, (hipStream_t)0, (unsigned long long)seed,
+                               (unsigned long long)subsequence, (unsigned long long)first_block, (int)nblocks, d);
     if (e == hipSuccess) e = hipMemcpy(out, d, sizeof(uint32_t) * 4 * (size_t)nblocks, hipMemcpyDeviceToHost);
     (void)dfree(d);
     return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
@@ -136,11 +135,8 @@ extern "C" klara_status klara_selftest_normal_tail(int32_t device, uint64_t seed
     if (e == hipSuccess) e = hipMemcpy(dthr, thr, sizeof(double) * (size_t)nthr, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(dc, 0, 8 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(dm, 0, 4 * sizeof(double));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_normal_tail, dim3((unsigned)((nchains + 255) / 256)), dim3(256), 0, 0, (unsigned long long)seed,
-                           (unsigned long long)first_chain, (long long)nchains, (long long)ntransitions, (int)nthr, dthr, dc, dm);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = klara_start(k_normal_tail, dim3((unsigned)((nchains + 255) / 256)), dim3(256), 0, (hipStream_t)0, (unsigned long long)seed,
+                                         (unsigned long long)first_chain, (long long)nchains, (long long)ntransitions, (int)nthr, dthr, dc, dm);
     if (e == hipSuccess) e = hipMemcpy(counts, dc, sizeof(uint64_t) * (size_t)nthr, hipMemcpyDeviceToHost);
     if (e == hipSuccess && moments) e = hipMemcpy(moments, dm, 4 * sizeof(double), hipMemcpyDeviceToHost);
     (void)dfree(dthr); (void)dfree(dc); (void)dfree(dm);
@@ -226,9 +222,56 @@ extern "C" klara_status klara_selftest_chain_stats(int32_t device, int64_t nchai
     return e == hipSuccess ? KLARA_OK : KLARA_ERR_HIP;
 }
 
+// The simulated ranks of the self tests below: one MergeLayout staging buffer per rank, all in one device array, merged by merge_ranks (klara_merge.h)
+// — the very sequence klara_gather_moments / klara_gather_covariance run — with every all-reduce replaced by a host sum of the ranks' slices in
+// ascending order of the ranks, starting from 0.0 / 0, written back to every rank.
+struct SimRanks {
+    MergeLayout L; hipStream_t st;
+    std::vector<double*> buf; std::vector<double> n_r;
+    hipError_t alloc(DeviceArrays& mem, int nranks)
+    {
+        double* rb = nullptr;
+        const hipError_t e = mem.alloc(&rb, (size_t)nranks * L.size());
+        for (int r = 0; r < nranks && e == hipSuccess; ++r) buf.push_back(rb + (size_t)r * L.size());
+        n_r.assign((size_t)nranks, 0.0);
+        return e;
+    }
+    // rank r's counters (has_accepted: slot 0 is on the device already, behind pool_moments_async's mean_r | M2_r)
+    hipError_t set_counters(int r, unsigned long long nsamples, unsigned long long nchains, bool has_accepted)
+    {
+        const unsigned long long cnt[MergeLayout::NCOUNTERS] = { 0, 0, nsamples, nchains };
+        const int first = has_accepted ? 1 : 0;
+        n_r[r] = (double)nsamples;
+        return hipMemcpy(buf[r] + L.counters() + first, cnt + first, (MergeLayout::NCOUNTERS - first) * sizeof(cnt[0]), hipMemcpyHostToDevice);
+    }
+    template <class T>
+    bool host_sum(size_t off, size_t n)
+    {
+        std::vector<T> part(n), total(n, T(0));
+        if (hipStreamSynchronize(st) != hipSuccess) return false;
+        for (double* b : buf) {
+            if (hipMemcpy(part.data(), b + off, n * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess) return false;
+            for (size_t j = 0; j < n; ++j) total[j] = total[j] + part[j];
+        }
+        for (double* b : buf)
+            if (hipMemcpy(b + off, total.data(), n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
+        return true;
+    }
+    bool reduce(size_t off, size_t n, bool is_u64) { return is_u64 ? host_sum<unsigned long long>(off, n) : host_sum<double>(off, n); }
+    // the merge; then rank 0's buffer — M, the counters and the mean are the same on every rank — to the host
+    hipError_t merge(std::vector<double>& host)
+    {
+        if (!merge_ranks(st, L, (int)buf.size(), buf.data(), n_r.data(), [&](size_t off, size_t n, bool is_u64) { return reduce(off, n, is_u64); }))
+            return hipErrorUnknown;
+        host.resize(L.size());
+        const hipError_t e = hipStreamSynchronize(st);
+        return e != hipSuccess ? e : hipMemcpy(host.data(), buf[0], L.size() * sizeof(double), hipMemcpyDeviceToHost);
+    }
+};
+
 // The across-chain reductions on a caller's per-chain sums, through the launch functions of the job path: (a) pool_summaries_async and pool_moments_async
-// over all the chains; (b) the chains cut into nranks shards, pool_moments_async on every shard's slice and the rank-local halves of klara_gather_moments'
-// between-rank merge around it, every all-reduce replaced by a host sum over the ranks in ascending order, starting from 0.
+// over all the chains; (b) the chains cut into nranks shards, pool_moments_async on every shard's slice staged as klara_gather_moments stages it, and
+// that call's between-rank merge over the simulated ranks (SimRanks).
 extern "C" klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
                                               const double* X, const int64_t* held, const uint64_t* naccept, int32_t nranks, const int64_t* bounds,
                                               int32_t with_sums, double* pooled_sum, double* pooled_sumsq, uint64_t* accept_total, double* mean, double* m2,
@@ -238,11 +281,13 @@ extern "C" klara_status klara_selftest_pooled(int32_t device, int64_t nchains, i
     if (bounds[0] != 0 || bounds[nranks] != nchains) return KLARA_ERR_INVALID_ARG;
     for (int r = 0; r < nranks; ++r) if (bounds[r + 1] <= bounds[r]) return KLARA_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(device));
-    const size_t D = (size_t)ndims, nd = (size_t)nchains * D, per = 3 * D + 4;       // per rank, as klara_gather_moments stages it: mean_r, M2_r, accept total, 3 counters, n_r mean_r
+    const size_t D = (size_t)ndims, nd = (size_t)nchains * D;
     const long long N = nchains;
+    const hipStream_t st = 0;
     DeviceArrays mem;
-    double *dsum = nullptr, *dsumsq = nullptr, *dX = nullptr, *partial = nullptr, *out = nullptr, *rb = nullptr, *dw = nullptr;
-    long long* dheld = nullptr; unsigned long long *dacc = nullptr, *dnt = nullptr;
+    SimRanks sim{ MergeLayout{ D, D }, st };
+    double *dsum = nullptr, *dsumsq = nullptr, *dX = nullptr, *partial = nullptr, *out = nullptr;
+    long long* dheld = nullptr; unsigned long long* dacc = nullptr;
     hipError_t e = mem.alloc(&dsum, nd);
     if (e == hipSuccess) e = mem.alloc(&dsumsq, nd);
     if (e == hipSuccess) e = mem.alloc(&dX, nd);
@@ -250,9 +295,7 @@ extern "C" klara_status klara_selftest_pooled(int32_t device, int64_t nchains, i
     if (e == hipSuccess) e = mem.alloc(&dacc, (size_t)N);
     if (e == hipSuccess) e = mem.alloc(&partial, (size_t)1024 * (2 * D + 1));            // (as klara_create sizes pool_partial)
     if (e == hipSuccess) e = mem.alloc(&out, 2 * (2 * D + 1));
-    if (e == hipSuccess) e = mem.alloc(&rb, (size_t)nranks * per);
-    if (e == hipSuccess) e = mem.alloc(&dw, D);
-    if (e == hipSuccess) e = mem.alloc(&dnt, 1);
+    if (e == hipSuccess) e = sim.alloc(mem, nranks);
     if (e == hipSuccess) e = hipMemcpy(dsum, sum, nd * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dsumsq, sumsq, nd * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(dX, X, nd * sizeof(double), hipMemcpyHostToDevice);
@@ -262,44 +305,19 @@ extern "C" klara_status klara_selftest_pooled(int32_t device, int64_t nchains, i
     if (e == hipSuccess) e = hipMemset(out, 0, 2 * (2 * D + 1) * sizeof(double));
     if (e == hipSuccess && pooled_sum) e = hipMemcpy(out, pooled_sum, D * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && pooled_sumsq) e = hipMemcpy(out + D, pooled_sumsq, D * sizeof(double), hipMemcpyHostToDevice);
-    const hipStream_t st = 0;
     double* outm = out + 2 * D + 1;
     // (a)
     if (e == hipSuccess) e = pool_summaries_async(st, with_sums ? dsum : nullptr, dsumsq, dX, dheld, dacc, N, ndims, partial, out);
     if (e == hipSuccess) e = pool_moments_async(st, dsum, dsumsq, dX, dheld, dacc, N, ndims, (long long)nsaved, partial, outm);
-    // (b) every rank's moments and n_r mean_r
+    // (b) every rank's mean_r | M2_r | accept total (counter slot 0) and its other counters, then the merge
     for (int r = 0; r < nranks && e == hipSuccess; ++r) {
         const long long c0 = bounds[r], Nr = bounds[r + 1] - bounds[r];
-        double* b = rb + (size_t)r * per;
-        e = pool_moments_async(st, dsum + c0 * D, dsumsq + c0 * D, dX + c0 * D, dheld + c0, dacc + c0, Nr, ndims, (long long)nsaved, partial, b);
-        if (e == hipSuccess) e = moments_scale_async(st, b + 2 * D + 4, b, (double)((unsigned long long)nsaved * (unsigned long long)Nr), ndims);
+        e = pool_moments_async(st, dsum + c0 * D, dsumsq + c0 * D, dX + c0 * D, dheld + c0, dacc + c0, Nr, ndims, (long long)nsaved, partial, sim.buf[r]);
+        if (e == hipSuccess) e = sim.set_counters(r, (unsigned long long)nsaved * (unsigned long long)Nr, (unsigned long long)Nr, true);
     }
-    std::vector<double> hout(2 * (2 * D + 1)), hrb((size_t)nranks * per), acc(D);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    std::vector<double> hout(2 * (2 * D + 1)), hr;
+    if (e == hipSuccess) e = sim.merge(hr);
     if (e == hipSuccess) e = hipMemcpy(hout.data(), out, hout.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
-    // the all-reduce of the counters and of n_r mean_r
-    unsigned long long cnt[3] = { 0, 0, 0 };                                              // accept total, saved samples, chains
-    if (e == hipSuccess) {
-        for (size_t j = 0; j < D; ++j) acc[j] = 0.0;
-        for (int r = 0; r < nranks; ++r) {
-            const double* b = hrb.data() + (size_t)r * per;
-            unsigned long long a;
-            memcpy(&a, b + 2 * D, sizeof(a));
-            cnt[0] += a;
-            cnt[1] += (unsigned long long)nsaved * (unsigned long long)(bounds[r + 1] - bounds[r]);
-            cnt[2] += (unsigned long long)(bounds[r + 1] - bounds[r]);
-            for (size_t j = 0; j < D; ++j) acc[j] = acc[j] + b[2 * D + 4 + j];
-        }
-        e = hipMemcpy(dw, acc.data(), D * sizeof(double), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(dnt, &cnt[1], sizeof(cnt[1]), hipMemcpyHostToDevice);
-    for (int r = 0; r < nranks && e == hipSuccess; ++r) {
-        double* b = rb + (size_t)r * per;
-        e = moments_between_async(st, b + D, b, dw, dnt, (double)((unsigned long long)nsaved * (unsigned long long)(bounds[r + 1] - bounds[r])), ndims, b);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
     const bool clean = mem.release();
     if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
     if (pooled_sum) memcpy(pooled_sum, hout.data(), D * sizeof(double));
@@ -307,14 +325,11 @@ extern "C" klara_status klara_selftest_pooled(int32_t device, int64_t nchains, i
     if (accept_total) memcpy(accept_total, hout.data() + 2 * D, sizeof(uint64_t));
     if (mean) memcpy(mean, hout.data() + 2 * D + 1, D * sizeof(double));
     if (m2) memcpy(m2, hout.data() + 3 * D + 1, D * sizeof(double));
-    if (ranks_mean) memcpy(ranks_mean, hrb.data(), D * sizeof(double));                   // (every rank holds the same mean)
-    if (ranks_m2) {                                                                       // the all-reduce of M2_r + n_r (mean_r - mean)^2
-        for (size_t j = 0; j < D; ++j) acc[j] = 0.0;
-        for (int r = 0; r < nranks; ++r)
-            for (size_t j = 0; j < D; ++j) acc[j] = acc[j] + hrb[(size_t)r * per + D + j];
-        memcpy(ranks_m2, acc.data(), D * sizeof(double));
-    }
-    if (ranks_counters) { ranks_counters[0] = cnt[0]; ranks_counters[1] = cnt[1]; ranks_counters[2] = cnt[2]; }
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    memcpy(cnt, hr.data() + sim.L.counters(), sizeof(cnt));
+    if (ranks_mean) memcpy(ranks_mean, hr.data() + sim.L.mean(), D * sizeof(double));
+    if (ranks_m2) memcpy(ranks_m2, hr.data() + sim.L.M(), D * sizeof(double));
+    if (ranks_counters) { ranks_counters[0] = cnt[MergeLayout::ACCEPTED]; ranks_counters[1] = cnt[MergeLayout::SAMPLES]; ranks_counters[2] = cnt[MergeLayout::CHAINS]; }
     return KLARA_OK;
 }
 
@@ -352,7 +367,7 @@ extern "C" const char* klara_compile_log(void) { return klara_jit_log(); }
 
 // The pooled covariance kernels on a caller's value history: klara_cov_launch_update launch by launch with col0 running through the history, as klara_run
 // issues them (the pivot copied before the first, an empty launch skipped), then klara_cov_launch_finalize; (b) the same on every shard's own history and
-// the rank-local halves of klara_gather_covariance's between-rank merge, every all-reduce replaced by a host sum over the ranks in ascending order from 0.
+// klara_gather_covariance's between-rank merge over the simulated ranks (SimRanks).
 static hipError_t selftest_cov_one(DeviceArrays& mem, const double* hist, long long N, long long c0, long long Nr, int D, long long ncols, int nsplits,
                                    const int64_t* splits, double* out, hipStream_t st)
 {
@@ -395,54 +410,32 @@ extern "C" klara_status klara_selftest_covariance(int32_t device, int64_t nchain
     if (bounds[0] != 0 || bounds[nranks] != nchains) return KLARA_ERR_INVALID_ARG;
     for (int r = 0; r < nranks; ++r) if (bounds[r + 1] <= bounds[r]) return KLARA_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(device));
-    const size_t D = (size_t)ndims, DD = D * D, per = 3 * D + DD;        // per rank: mean_r, M_r, n_r mean_r, mean
+    const size_t D = (size_t)ndims, DD = D * D;
     const hipStream_t st = 0;
     DeviceArrays mem;
-    double *out = nullptr, *rb = nullptr, *dw = nullptr; unsigned long long* dnt = nullptr;
+    SimRanks sim{ MergeLayout{ D, DD }, st };
+    double* out = nullptr;
     hipError_t e = mem.alloc(&out, D + DD);
-    if (e == hipSuccess) e = mem.alloc(&rb, (size_t)nranks * per);
-    if (e == hipSuccess) e = mem.alloc(&dw, D);
-    if (e == hipSuccess) e = mem.alloc(&dnt, 1);
+    if (e == hipSuccess) e = sim.alloc(mem, nranks);
     // (a)
     if (e == hipSuccess) e = selftest_cov_one(mem, hist, nchains, 0, nchains, ndims, ncols, nsplits, splits, out, st);
-    // (b) every rank's mean_r, M_r and n_r mean_r
-    unsigned long long cnt[2] = { 0, 0 };
+    // (b) every rank's mean_r | M_r and its counters, then the merge
     for (int r = 0; r < nranks && e == hipSuccess; ++r) {
         const long long Nr = bounds[r + 1] - bounds[r];
-        double* b = rb + (size_t)r * per;
-        e = selftest_cov_one(mem, hist, nchains, bounds[r], Nr, ndims, ncols, nsplits, splits, b, st);
-        if (e == hipSuccess) e = moments_scale_async(st, b + D + DD, b, (double)((unsigned long long)ncols * (unsigned long long)Nr), ndims);
-        cnt[0] += (unsigned long long)ncols * (unsigned long long)Nr; cnt[1] += (unsigned long long)Nr;
+        e = selftest_cov_one(mem, hist, nchains, bounds[r], Nr, ndims, ncols, nsplits, splits, sim.buf[r], st);
+        if (e == hipSuccess) e = sim.set_counters(r, (unsigned long long)ncols * (unsigned long long)Nr, (unsigned long long)Nr, false);
     }
-    std::vector<double> hout(D + DD), hrb((size_t)nranks * per), acc(DD);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    std::vector<double> hout(D + DD), hr;
+    if (e == hipSuccess) e = sim.merge(hr);
     if (e == hipSuccess) e = hipMemcpy(hout.data(), out, hout.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {                                                                // the all-reduce of n_r mean_r (and of the counters: cnt)
-        for (size_t j = 0; j < D; ++j) acc[j] = 0.0;
-        for (int r = 0; r < nranks; ++r)
-            for (size_t j = 0; j < D; ++j) acc[j] = acc[j] + hrb[(size_t)r * per + D + DD + j];
-        e = hipMemcpy(dw, acc.data(), D * sizeof(double), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipMemcpy(dnt, &cnt[0], sizeof(cnt[0]), hipMemcpyHostToDevice);
-    for (int r = 0; r < nranks && e == hipSuccess; ++r) {
-        double* b = rb + (size_t)r * per;
-        e = klara_cov_launch_between(st, b + D, b, dw, dnt, (double)((unsigned long long)ncols * (unsigned long long)(bounds[r + 1] - bounds[r])), ndims,
-                                     b + 2 * D + DD);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(hrb.data(), rb, hrb.size() * sizeof(double), hipMemcpyDeviceToHost);
     const bool clean = mem.release();
     if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
     if (mean) memcpy(mean, hout.data(), D * sizeof(double));
     if (m2) memcpy(m2, hout.data() + D, DD * sizeof(double));
-    if (ranks_mean) memcpy(ranks_mean, hrb.data() + 2 * D + DD, D * sizeof(double));      // (every rank holds the same mean)
-    if (ranks_m2) {                                                                       // the all-reduce of M_r + n_r d d'
-        for (size_t j = 0; j < DD; ++j) acc[j] = 0.0;
-        for (int r = 0; r < nranks; ++r)
-            for (size_t j = 0; j < DD; ++j) acc[j] = acc[j] + hrb[(size_t)r * per + D + j];
-        memcpy(ranks_m2, acc.data(), DD * sizeof(double));
-    }
-    if (ranks_counters) { ranks_counters[0] = cnt[0]; ranks_counters[1] = cnt[1]; }
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    memcpy(cnt, hr.data() + sim.L.counters(), sizeof(cnt));
+    if (ranks_mean) memcpy(ranks_mean, hr.data() + sim.L.mean(), D * sizeof(double));
+    if (ranks_m2) memcpy(ranks_m2, hr.data() + sim.L.M(), DD * sizeof(double));
+    if (ranks_counters) { ranks_counters[0] = cnt[MergeLayout::SAMPLES]; ranks_counters[1] = cnt[MergeLayout::CHAINS]; }
     return KLARA_OK;
 }

@@ -1,5 +1,5 @@
 """References for the pooled posterior covariance (klara_cov.hip: k_cov_update behind every launch of a job with KLARA_MON_COVARIANCE, k_cov_finalize
-and k_cov_between behind klara_gather_covariance).
+behind klara_gather_covariance, then between ranks klara_comm.hip's k_scale / k_merge_between in the one sequence of klara_merge.h merge_ranks).
 
   exact(hist, pairs)              mean (all dimensions) and M_ij = sum x_i x_j - (sum x_i)(sum x_j) / n on the (i, j) pairs in exact integer arithmetic (every
                                   double is a dyadic rational; nothing is rounded before the final conversion)

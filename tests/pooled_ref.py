@@ -1,5 +1,6 @@
 """References for the across-chain reductions (klara_monitors.hip: k_pool_stage1 / k_pool_stage2 behind klara_get_pooled_summaries, k_moments_stage1 /
-k_moments_stage2 with chan_merge behind klara_gather_moments; klara_comm.hip: k_scale / k_moments_between, the rank-local halves of the between-rank merge).
+k_moments_stage2 with chan_merge behind klara_gather_moments; klara_comm.hip: k_scale / k_merge_between, the rank-local steps of the one between-rank merge, klara_merge.h merge_ranks, that the gather calls and the
+simulated-rank self tests both run).
 
   chain_view(inp)                 every chain's sums as the device views them: part + held * x in two f64 operations (what klara_get_chain_sums returns)
   exact(inp, cols)                pooled S, Q, mean = S / n, M2 = Q - S^2 / n, the accept total and the smallest per-chain q_c - s_c^2 / nsaved from those doubles
@@ -252,7 +253,7 @@ def between_ranks(means, m2s, counts):
         m2 = np.zeros(D)
         for mr, qr, nr in zip(means, m2s, counts):
             d = mr - mean
-            m2 = m2 + (qr + float(nr) * (d * d))   # k_moments_between
+            m2 = m2 + (qr + float(nr) * (d * d))   # k_merge_between (the diagonal form)
     return mean, m2, ntot
 
 

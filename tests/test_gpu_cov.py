@@ -1,8 +1,8 @@
-"""The pooled posterior covariance (klara_cov.hip: k_cov_update after every launch of a job with KLARA_MON_COVARIANCE, k_cov_finalize / k_cov_between
-behind klara_gather_covariance) against tests/cov_ref.py: bit for bit against the NumPy restatement of the order of operations on every element, and,
+"""The pooled posterior covariance (klara_cov.hip: k_cov_update after every launch of a job with KLARA_MON_COVARIANCE, k_cov_finalize
+behind klara_gather_covariance, klara_comm.hip's k_merge_between between ranks) against tests/cov_ref.py: bit for bit against the NumPy restatement of the order of operations on every element, and,
 so that the mirror is never the only yardstick, against exact rational arithmetic within the derived bound on a fixed handful of (i, j) pairs that
 includes both sides of the tile edges.  The kernels run on synthetic histories through klara_selftest_covariance (the launch functions of the job
-path; the between-rank all-reduces as ordered host sums) and in small jobs of every save path through the API.  The synthetic inputs are those
+path; klara_gather_covariance's own between-rank sequence, merge_ranks, with only the all-reduces swapped for ordered host sums) and in small jobs of every save path through the API.  The synthetic inputs are those
 tests/test_cov_host.py checks on the CPU."""
 import ctypes as C
 import os

@@ -1,8 +1,8 @@
 """The across-chain reductions (klara_monitors.hip: k_pool_stage1 / k_pool_stage2, k_moments_stage1 / k_moments_stage2 with chan_merge; klara_comm.hip:
-k_scale / k_moments_between) against tests/pooled_ref.py: bit for bit against the NumPy restatement of their order of operations (mirror, mirror_ranks)
+k_scale / k_merge_between) against tests/pooled_ref.py: bit for bit against the NumPy restatement of their order of operations (mirror, mirror_ranks)
 and, so that the mirror is never the only yardstick, against exact rational arithmetic within the derived bound.  The kernels run on synthetic per-chain
-sums through klara_selftest_pooled (the launch functions of the job path; the between-rank all-reduces as ordered host sums, which is what lets
-mean_r - mean differ from zero on one GPU), and in small jobs through the API.  The inputs are those tests/test_pooled_host.py checks on the CPU."""
+sums through klara_selftest_pooled (the launch functions of the job path; klara_gather_moments' own between-rank sequence, merge_ranks, over simulated
+ranks with only the all-reduces swapped for ordered host sums, which is what lets mean_r - mean differ from zero on one GPU), and in small jobs through the API.  The inputs are those tests/test_pooled_host.py checks on the CPU."""
 import ctypes as C
 
 import numpy as np
@@ -110,7 +110,7 @@ def test_selftest_saved_steps(nsaved):
 @pytest.mark.parametrize("name", list(R.splits(2051)))
 def test_selftest_ranks(name):
     """2,051 chains over 1, 2, 3 and 5 simulated ranks as shard_chains cuts them, and unequal shards (1 | N - 1, N - 1 | 1, 1 | 1 | N - 2, 1025 | rest),
-    at 1e4 sd: n_r (mean_r - mean)^2 is far from zero, so a wrong weight in k_scale or k_moments_between changes the result."""
+    at 1e4 sd: n_r (mean_r - mean)^2 is far from zero, so a wrong weight in k_scale or k_merge_between, or a wrong offset, count or counter slot in merge_ranks, changes the result."""
     inp, ex = case(2051, 3, 200, 1e4)
     b = R.splits(2051)[name]
     out = check_case(inp, ex, f"ranks {name}", b)
