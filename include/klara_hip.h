@@ -389,6 +389,24 @@ klara_status klara_gather_moments(klara_handle* h, klara_comm* comm, double* mea
  * first saved sample: zeros, as klara_gather_moments.  klara_set_state and klara_reset clear the accumulators. */
 klara_status klara_gather_covariance(klara_handle* h, klara_comm* comm, double* mean, double* m2, uint64_t* nsamples, uint64_t* nchains);
 
+/* The Gelman–Rubin diagnostic over all chains: do the chains agree with each other?  Per dimension, over m chains of n saved samples each with chain mean
+ * mu_j and M2_j = sum_t (x_jt - mu_j)^2:
+ *   wsum = sum_j M2_j,  mean = (1 / m) sum_j mu_j,  bsum = sum_j (mu_j - mean)^2,
+ *   W = wsum / (m (n - 1)),  B / n = bsum / (m - 1),  var+ = (n - 1) / n W + B / n,  rhat = sqrt(var+ / W)
+ * (Gelman & Rubin 1992; the reference has no counterpart: one BasicMCJob is one chain).  m < 2 or n < 2: NaN; otherwise plain IEEE division: wsum = 0 with
+ * bsum > 0 gives +inf, both zero NaN; nothing is clamped.  split = 0 works from the running sums (requires KLARA_MON_SUMMARIES; no history needed): every
+ * chain's (mu_j, M2_j) is formed as klara_gather_moments forms it, then (chains, mean of means, bsum) go through the same two-stage Chan reduction at unit
+ * weight per chain and wsum through a plain sum — no floating-point atomics, the same bits for a given chain count.  split != 0 is the split form (BDA3
+ * section 11.4) from the stored value history (requires KLARA_MON_HISTORY without a ring and at least 4 saved steps, else KLARA_ERR_STATE): with
+ * h = floor(n / 2), every chain gives the two half-chains of samples [0, h) and [n - h, n) — an odd n drops the middle sample — and the formulas run
+ * with m -> 2 m and n -> h; the history is read once.  rhat, mean, wsum, bsum: D each; *nchains and *nper are the units the formulas ran on (split: the
+ * half-chains and h).  comm = NULL: this handle's chains only; otherwise collective over the ranks: (m_r, mean_r, bsum_r) merge as the samples, means and
+ * m2 of klara_gather_moments do, wsum is one more sum — four all-reduces, entered by every rank whatever happens locally.  All ranks must hold the same
+ * number of saved steps: if they do not, every rank returns KLARA_ERR_STATE.  Any output pointer may be NULL.  Before the first saved sample: NaN for rhat,
+ * zeros for the other outputs, KLARA_OK.  The call only reads the job's state: a job that goes on after it produces the same bits as one that never called it. */
+klara_status klara_gather_rhat(klara_handle* h, klara_comm* comm, int32_t split, double* rhat, double* mean, double* wsum, double* bsum,
+                               uint64_t* nchains, int64_t* nper);
+
 /* Memory-safety aid (tests only).  With KLARA_DEBUG_CANARY=1 in the environment every device array the library allocates lies between
  * two 4 KiB canaries of a signalling-NaN pattern; klara_destroy returns KLARA_ERR_STATE when a kernel of the job wrote into one, and this
  * call checks the canaries of everything alive: *nalloc = arrays checked, *ncorrupt = arrays whose canaries were damaged (they are
@@ -589,6 +607,18 @@ klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndim
 klara_status klara_selftest_covariance(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
                                        const int64_t* splits, int32_t nranks, const int64_t* bounds, double* mean, double* m2, double* ranks_mean,
                                        double* ranks_m2, uint64_t* ranks_counters);
+
+/* Self-test hook: the R-hat kernels on a caller's data, through the launch functions klara_gather_rhat uses.  Unsplit: the per-chain running sums sum,
+ * sumsq, X (nchains x ndims, ndims 1..1024) and held (nchains) over nsaved (>= 1) saved steps, as for klara_selftest_pooled; all four NULL: skipped.
+ * Split: hist, ncols (>= 2) saved steps of nchains x ndims values (column t at hist + t * nchains * ndims); NULL: skipped.  For each of the two:
+ * (a) over all chains; (b) the chains cut into nranks shards, rank r owning [bounds[r], bounds[r + 1]) with 0 = bounds[0] < ... < bounds[nranks] = nchains,
+ * every shard staged as klara_gather_rhat stages it, then that call's own between-rank merge with each all-reduce replaced by a host sum over the ranks in
+ * ascending order starting from zero.  out, ranks_out (unsplit (a), (b)) and split_out, split_ranks_out: 4 x ndims doubles each, rhat | mean | wsum | bsum;
+ * counters[8]: (units, samples per unit) of the four in that order.  Every output may be NULL.  KLARA_ERR_INVALID_ARG (before any launch) for neither
+ * input, an incomplete set of sums, nchains <= 0, ndims outside 1..1024, nsaved < 1, ncols < 2 or bad bounds. */
+klara_status klara_selftest_rhat(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
+                                 const double* X, const int64_t* held, int64_t ncols, const double* hist, int32_t nranks, const int64_t* bounds,
+                                 double* out, double* ranks_out, double* split_out, double* split_ranks_out, uint64_t* counters);
 
 /* Self-test hook, no device needed: the launches a sequence of klara_run calls of the given lengths issues on a fresh job of
  * this descriptor — transitions per launch k[i], the save-rule bookkeeping handed to the kernels (columns already saved,

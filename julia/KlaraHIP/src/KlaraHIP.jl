@@ -38,7 +38,7 @@ import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
        check_custom_target_softabs, SoftAbs, ramfactor,
-       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, KlaraDesc, klara_desc
+       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
 # ---------------------------------------------------------------- Julia 0.6 / >= 0.7 compatibility (the only version-dependent code)
@@ -572,5 +572,25 @@ function pooledcovariance(job::HIPMCJob)
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{UInt64}),
                 job.handle, C_NULL, m, m2, ns, nc), "klara_gather_covariance")
     (m, reshape(m2, job.ndims, job.ndims) ./ (Float64(ns[]) - 1.0), ns[], nc[])
+end
+# The Gelman–Rubin diagnostic over all chains (klara_gather_rhat; Klara has no counterpart: its job is one chain): (rhat, mean of the chain means, wsum =
+# sum of the chains' M2, bsum = sum (chain mean - mean)^2, units, samples per unit).  split=false works from the running sums; split=true is the split
+# form from the stored history — every chain cut into its halves [0, h) and [n - h, n), h = div(n, 2) — and the units are the half-chains.
+function gather_rhat(job::HIPMCJob, comm::HIPComm; split::Bool=false)
+    r = newarray(Float64, job.ndims); m = similar(r); w = similar(r); b = similar(r)
+    nc = Ref{UInt64}(0); np = Ref{Int64}(0)
+    check(ccall((:klara_gather_rhat, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{Int64}),
+                job.handle, comm.handle, Int32(split), r, m, w, b, nc, np), "klara_gather_rhat")
+    (r, m, w, b, nc[], np[])
+end
+# ... and of this job's chains alone (no communicator, no RCCL)
+function rhat(job::HIPMCJob; split::Bool=false)
+    r = newarray(Float64, job.ndims); m = similar(r); w = similar(r); b = similar(r)
+    nc = Ref{UInt64}(0); np = Ref{Int64}(0)
+    check(ccall((:klara_gather_rhat, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{Int64}),
+                job.handle, C_NULL, Int32(split), r, m, w, b, nc, np), "klara_gather_rhat")
+    (r, m, w, b, nc[], np[])
 end
 end # module

@@ -85,6 +85,7 @@ EXPORTS = [
     "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_get_ram_factor", "klara_set_ram_factor", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
     "klara_selftest_rocrand_blocks", "klara_selftest_math", "klara_selftest_normal_tail", "klara_selftest_transition_normals", "klara_selftest_mfma_f64", "klara_selftest_mfma_f64_4x4x4", "klara_selftest_chain_stats", "klara_selftest_pooled", "klara_strerror",
     "klara_comm_unique_id", "klara_comm_init", "klara_comm_info", "klara_comm_destroy", "klara_gather_summaries", "klara_gather_moments", "klara_gather_covariance", "klara_selftest_covariance",
+    "klara_gather_rhat", "klara_selftest_rhat",
     "klara_check_custom_target", "klara_check_custom_target_softabs", "klara_compile_log", "klara_selftest_plan", "klara_selftest_canary", "klara_abi_version",
 ]
 
@@ -155,6 +156,9 @@ def load() -> C.CDLL:
         "klara_gather_covariance": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
         "klara_selftest_covariance": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "klara_gather_rhat": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+        "klara_selftest_rhat": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_selftest_canary": [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
         "klara_check_custom_target": [C.c_char_p, C.c_int32, C.c_int32],
         "klara_check_custom_target_softabs": [C.c_char_p, C.c_int32],

@@ -474,6 +474,14 @@ def pooled_cov(job_or_chains, comm=None) -> np.ndarray:
     return m2 / (ns - 1)
 
 
+def rhat(job_or_chains, split: bool = False, comm=None) -> np.ndarray:
+    """The potential scale reduction factor R-hat (Gelman & Rubin 1992) per dimension over all chains of a job, formed on the device (Engine.rhat):
+    from the running sums, or with split=True the split form (BDA3 section 11.4) from the stored history; `comm`: a klara_comm handle, to take every
+    rank's chains.  Values near 1 say the chains agree; the reference has no counterpart (its job is one chain)."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    return job.engine.rhat(split=split, comm=comm)["rhat"]
+
+
 def pooled_cor(job_or_chains, comm=None) -> np.ndarray:
     """The correlations of pooled_cov: cov_ij / sqrt(cov_ii cov_jj) (NaN where a coordinate never moved)."""
     c = pooled_cov(job_or_chains, comm)

@@ -1,8 +1,10 @@
-// klara_comm.hip — RCCL summary all-reduce behind the C ABI (librccl.so loaded lazily; see include/klara_hip.h)
+// klara_comm.hip — RCCL summary all-reduce behind the C ABI (librccl.so loaded lazily; see include/klara_hip.h): the gather calls of the pooled
+// summaries, moments, covariance and R-hat, and the rank-local steps of their one between-rank merge (klara_merge.h)
 #include <rccl/rccl.h>      // types only: librccl.so is dlopen'ed on first use (klara_comm_*)
 #include <dlfcn.h>
 #include <new>
 #include "klara_handle.h"
+#include "klara_rhat.h"
 
 struct klara_comm {
     void* dl = nullptr;
@@ -248,4 +250,73 @@ extern "C" klara_status klara_gather_covariance(klara_handle* h, klara_comm* c, 
     if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
     if (nchains) *nchains = cnt[MergeLayout::CHAINS];
     return KLARA_OK;
+}
+
+// ---- the Gelman–Rubin diagnostic (klara_rhat.h): the same merge with units (chains, or half-chains) where the samples stand — rank r stages the mean of
+// its units' means, Bsum_r and Wsum_r — and, after it, R-hat from the totals on the host
+void rhat_counters(unsigned long long m, unsigned long long n, unsigned long long cnt[MergeLayout::NCOUNTERS])
+{
+    cnt[MergeLayout::UNIT_SAMPLES] = m * n; cnt[MergeLayout::UNIT_SAMPLES_SQ] = m * n * n; cnt[MergeLayout::UNITS] = m; cnt[MergeLayout::CHAINS] = 0;
+}
+klara_status rhat_finish(size_t D, const double* host, bool merged, double* rhat, double* mean, double* wsum, double* bsum, uint64_t* units, int64_t* nper)
+{
+    const MergeLayout L{ D, D, D };
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    memcpy(cnt, host + L.counters(), sizeof(cnt));
+    const unsigned long long m = cnt[MergeLayout::UNITS], sn = cnt[MergeLayout::UNIT_SAMPLES], sn2 = cnt[MergeLayout::UNIT_SAMPLES_SQ];
+    // every rank evaluates this on the same three sums: the same status everywhere
+    if ((unsigned __int128)sn * sn != (unsigned __int128)m * sn2) return KLARA_ERR_STATE;
+    const unsigned long long n = m ? sn / m : 0;
+    const bool none = n == 0;                                               // before the first saved sample: NaN and zeros
+    const double* mu = host + (merged ? L.mean() : L.mean_r());
+    for (size_t j = 0; j < D; ++j) {
+        if (rhat) rhat[j] = none ? (double)NAN : rhat_value(host[L.extra() + j], host[L.M() + j], (double)m, (double)n);
+        if (mean) mean[j] = none ? 0.0 : mu[j];
+        if (wsum) wsum[j] = none ? 0.0 : host[L.extra() + j];
+        if (bsum) bsum[j] = none ? 0.0 : host[L.M() + j];
+    }
+    if (units) *units = none ? 0 : m;
+    if (nper) *nper = (int64_t)n;
+    return KLARA_OK;
+}
+
+extern "C" klara_status klara_gather_rhat(klara_handle* h, klara_comm* c, int32_t split, double* rhat, double* mean, double* wsum, double* bsum,
+                                          uint64_t* nchains, int64_t* nper)
+{
+    if (!h) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    if (split ? (!h->hist || h->ring || !(h->d.monitor & KLARA_MON_HISTORY)) : !h->sum) return KLARA_ERR_STATE;   // (split: needs every saved step)
+    HIPCHK(hipSetDevice(h->d.device));
+    const int D = h->d.ndims;
+    const long long N = h->d.nchains;
+    const MergeLayout L{ (size_t)D, (size_t)D, (size_t)D };
+    if (!h->rhat_ws) HIPCHK(h->mem.alloc(&h->rhat_ws, klara_rhat_partial_elems(D) + L.size()));
+    if (split && !h->rhat_half) HIPCHK(h->mem.alloc(&h->rhat_half, (size_t)4 * (size_t)N * (size_t)D));
+    // units and samples per unit.  A split of 1 to 3 saved steps is refused, but only after the reductions: no rank leaves the others waiting in theirs
+    const long long nsaved = h->nsaved, n = split ? nsaved / 2 : nsaved;
+    const bool too_short = split && nsaved > 0 && nsaved < 4;
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    rhat_counters((unsigned long long)(split ? 2 * N : N), (unsigned long long)n, cnt);
+    const auto stage = [&](double* buf) -> hipError_t {                     // zeros | this rank's mean_r, Bsum_r, Wsum_r | its counters
+        hipError_t e = hipMemsetAsync(buf, 0, L.size() * sizeof(double), h->stream);
+        if (e == hipSuccess && n > 0 && !too_short)
+            e = split ? rhat_split_async(h->stream, h->hist, nsaved, N, D, h->rhat_half, h->rhat_ws, buf + L.mean_r(), buf + L.extra())
+                      : rhat_sums_async(h->stream, h->sum, h->sumsq, h->X, h->held, N, D, nsaved, h->rhat_ws, buf + L.mean_r(), buf + L.extra());
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + L.counters(), cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream);
+        return e;
+    };
+    std::vector<double> host(L.size());
+    if (!c) {
+        double* buf = h->rhat_ws + klara_rhat_partial_elems(D);
+        HIPCHK(stage(buf));
+        HIPCHK(hipMemcpyAsync(host.data(), buf, L.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    } else {
+        HIPCHK(comm_reserve(c, L.size()));
+        CommSeq q{ c, h->stream };
+        q.H(stage(c->buf));
+        if (!comm_merge(q, L, cnt, host)) return KLARA_ERR_HIP;
+    }
+    const klara_status st = rhat_finish((size_t)D, host.data(), c != nullptr, rhat, mean, wsum, bsum, nchains, nper);
+    return st != KLARA_OK ? st : too_short ? KLARA_ERR_STATE : KLARA_OK;
 }

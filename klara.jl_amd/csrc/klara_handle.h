@@ -73,6 +73,7 @@ struct klara_handle {
            *hY = nullptr, *hxc = nullptr;
     double* pooled_out = nullptr;   // 2*D doubles + 1 u64 scratch for pooled summaries
     double* pool_partial = nullptr; // KLARA_POOL_BLOCKS x (2 D doubles + 1 u64): stage-1 partials of the pooled summaries
+    double *rhat_ws = nullptr, *rhat_half = nullptr;   // klara_gather_rhat's workspace, allocated at its first call: stage-1 partials and the staging buffer; the halves' (mean, M2) of the split form
     double* cdata = nullptr; KlaraJit* jit = nullptr;   // user-defined target: data block, run-time compiled kernels
     // RAM: the chains' factors (D (D + 1) / 2 planes of nchains doubles, KParams::ram_S), the packed lower triangle of klara_desc.ram_S0 they restart from, the skipped-update counter
     double *ram_S = nullptr, *ram_S0 = nullptr; unsigned long long* ram_skipped = nullptr;
@@ -134,7 +135,7 @@ hipError_t pool_moments_async(hipStream_t stream, const double* sum, const doubl
 hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);      // ... with the handle's arrays, on its stream
 hipError_t pool_moments_async(klara_handle* h, double* out);
 
-// ---- klara_comm.hip: the between-rank merge of the pooled moments and the pooled covariance — its staging layout, its rank-local steps and the one
+// ---- klara_comm.hip: the between-rank merge of the pooled moments, the pooled covariance and R-hat — its staging layout, its rank-local steps and the one
 // sequence of reductions that the gather calls and the simulated-rank self tests both run
 #include "klara_merge.h"
 

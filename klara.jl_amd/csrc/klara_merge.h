@@ -2,20 +2,26 @@
 // covariance.  Rank r holds (mean_r, M_r) over its n_r samples; over the ranks mean = sum n_r mean_r / sum n_r, M = sum M_r + n_r (mean_r - mean)(mean_r - mean)'.
 // One staging layout and one sequence of three reductions: klara_gather_moments / klara_gather_covariance run it on one buffer with RCCL all-reduces,
 // klara_selftest_pooled / klara_selftest_covariance on one buffer per simulated rank with host sums — the same code, only the collective swapped.
+// klara_gather_rhat / klara_selftest_rhat run it too, with chains where the samples stand: rank r holds (mean of its m_r units' means, Bsum_r) and the
+// merge is the same; its Wsum_r are X = D further doubles that are only summed over the ranks, in a fourth reduction that a layout with X = 0 never enters.
 #pragma once
 
 // One rank's staging buffer, in doubles, for D means and K second-moment elements (K = D: the diagonal, the pooled moments; K = D D: the matrix):
-//   [0, D) mean_r | [D, D + K) M_r -> M | 4 u64 counters | D doubles n_r mean_r -> their sum | D doubles mean
+//   [0, D) mean_r | [D, D + K) M_r -> M | 4 u64 counters | D doubles n_r mean_r -> their sum | D doubles mean | X doubles, plain sums over the ranks
 // pool_moments_async's output (mean_r, M2_r, the u64 accept total) is the head of the K = D form as it stands: the accept total is counter slot 0.
 struct MergeLayout {
-    size_t D, K;
+    size_t D, K, X = 0;
     enum { ACCEPTED = 0, TRANSITIONS = 1, SAMPLES = 2, CHAINS = 3, NCOUNTERS = 4 };   // the counter slots; SAMPLES summed over the ranks is the merge's ntot
+    // R-hat's use of the slots: the merge's samples are its units, so UNITS sits where SAMPLES does; the other two carry the check that every rank holds
+    // the same number n_r of samples per unit: (sum m_r n_r)^2 = sum m_r * sum m_r n_r^2 exactly when the n_r are all equal
+    enum { UNIT_SAMPLES = 0, UNIT_SAMPLES_SQ = 1, UNITS = 2 };
     size_t mean_r() const { return 0; }
     size_t M() const { return D; }
     size_t counters() const { return D + K; }
     size_t wsum() const { return counters() + NCOUNTERS; }
     size_t mean() const { return wsum() + D; }
-    size_t size() const { return mean() + D; }
+    size_t extra() const { return mean() + D; }
+    size_t size() const { return extra() + X; }
 };
 
 // ---- klara_comm.hip: the rank-local steps on one staging buffer
@@ -36,5 +42,6 @@ static bool merge_ranks(hipStream_t st, const MergeLayout& L, int nlocal, double
     ok &= reduce(L.wsum(), L.D, false);
     for (int r = 0; r < nlocal; ++r) ok &= merge_between_async(st, L, buf[r], n_r[r]) == hipSuccess;
     ok &= reduce(L.M(), L.K, false);
+    if (L.X) ok &= reduce(L.extra(), L.X, false);
     return ok;
 }

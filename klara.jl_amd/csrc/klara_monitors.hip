@@ -1,6 +1,7 @@
 // klara_monitors.hip — what a job accumulates and how it is read back: batch means, streaming autocovariances, pooled summaries and moments,
 // histories, tuner state, layout and kernel queries.
 #include "klara_handle.h"
+#include "klara_rhat.h"
 
 // Closes one batch of every (chain, dimension) series in [i0, i1): batch mean from the running sums at the two batch
 // boundaries, then Welford's update of the mean and the sum of squared deviations of the batch means (count = batches closed
@@ -403,15 +404,7 @@ extern "C" klara_status klara_get_pooled_summaries(klara_handle* h, double* sum,
 // digits).  Here every chain's raw sums become (n_c, mean_c, M2_c) with the one cancelling subtraction, q - s^2/n, carried in
 // double-double (s^2 = p + pe exactly by fma, the quotient's remainder by fma), and chains, blocks and ranks are merged by
 // Chan's update — sums of non-negative terms only.  Fixed shapes => deterministic for a given chain count.
-__device__ inline void chan_merge(double& n, double& mean, double& m2, double nb, double meanb, double m2b)
-{
-    const double nt = n + nb;
-    if (!(nt > 0.0)) return;
-    const double delta = meanb - mean, w = nb / nt;
-    mean = mean + delta * w;
-    m2 = (m2 + m2b) + (delta * delta) * (n * w);
-    n = nt;
-}
+// (chan_merge and the per-chain (mean, M2) live in klara_rhat.h: the R-hat reduction forms and merges them with the same code)
 __global__ __launch_bounds__(256) void k_moments_stage1(const double* __restrict__ sum, const double* __restrict__ sumsq,
                                                         const double* __restrict__ X, const long long* __restrict__ held,
                                                         long long N, int D, int nb, double nsaved, double* __restrict__ partial)
@@ -420,16 +413,9 @@ __global__ __launch_bounds__(256) void k_moments_stage1(const double* __restrict
     for (int j = threadIdx.x; j < D; j += 256) {
         double n = 0.0, mean = 0.0, m2 = 0.0;
         for (long long c = b; c < N; c += nb) {                             // (a chain's sums over its saved steps: part + held * x)
-            const long long hd = held[c];
-            const double x = X[c * D + j];
-            const double s = hd > 0 ? sum[c * D + j] + (double)hd * x : sum[c * D + j];
-            const double q = hd > 0 ? sumsq[c * D + j] + (double)hd * (x * x) : sumsq[c * D + j];
-            const double p = s * s, pe = fma(s, s, -p);                    // s^2 = p + pe
-            const double qh = p / nsaved, r = fma(-qh, nsaved, p);         // p = qh * nsaved + r
-            const double ql = (r + pe) / nsaved;                           // s^2 / nsaved = qh + ql (+ O(2^-105))
-            double m2c = (q - qh) - ql;
-            if (m2c < 0.0) m2c = 0.0;
-            chan_merge(n, mean, m2, nsaved, s / nsaved, m2c);
+            double mc, m2c;
+            chain_moments(sum, sumsq, X, held, c, D, j, nsaved, mc, m2c);
+            chan_merge(n, mean, m2, nsaved, mc, m2c);
         }
         partial[(long long)b * 2 * D + j] = mean;
         partial[(long long)b * 2 * D + D + j] = m2;

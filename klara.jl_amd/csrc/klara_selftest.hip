@@ -1,7 +1,8 @@
 // klara_selftest.hip — self tests: the device's random blocks, math, normals and matrix-core probes as the kernels see them; the chain statistics kernels on a
-// caller's series; the across-chain reductions on a caller's chain sums; compile checks of user targets.
+// caller's series; the across-chain reductions and the R-hat kernels on a caller's chain sums and histories; compile checks of user targets.
 #include <rocrand/rocrand_kernel.h>
 #include "klara_handle.h"
+#include "klara_rhat.h"
 
 __global__ void k_rocrand_blocks(unsigned long long seed, unsigned long long subseq,
                                  unsigned long long first_block, int nblocks, unsigned int* out)
@@ -223,7 +224,7 @@ extern "C" klara_status klara_selftest_chain_stats(int32_t device, int64_t nchai
 }
 
 // The simulated ranks of the self tests below: one MergeLayout staging buffer per rank, all in one device array, merged by merge_ranks (klara_merge.h)
-// — the very sequence klara_gather_moments / klara_gather_covariance run — with every all-reduce replaced by a host sum of the ranks' slices in
+// — the very sequence klara_gather_moments / klara_gather_covariance / klara_gather_rhat run — with every all-reduce replaced by a host sum of the ranks' slices in
 // ascending order of the ranks, starting from 0.0 / 0, written back to every rank.
 struct SimRanks {
     MergeLayout L; hipStream_t st;
@@ -243,6 +244,14 @@ struct SimRanks {
         const int first = has_accepted ? 1 : 0;
         n_r[r] = (double)nsamples;
         return hipMemcpy(buf[r] + L.counters() + first, cnt + first, (MergeLayout::NCOUNTERS - first) * sizeof(cnt[0]), hipMemcpyHostToDevice);
+    }
+    // rank r's counters of the R-hat form: m units of n samples each
+    hipError_t set_rhat_counters(int r, unsigned long long m, unsigned long long n)
+    {
+        unsigned long long cnt[MergeLayout::NCOUNTERS];
+        rhat_counters(m, n, cnt);
+        n_r[r] = (double)m;
+        return hipMemcpy(buf[r] + L.counters(), cnt, sizeof(cnt), hipMemcpyHostToDevice);
     }
     template <class T>
     bool host_sum(size_t off, size_t n)
@@ -438,4 +447,96 @@ extern "C" klara_status klara_selftest_covariance(int32_t device, int64_t nchain
     if (ranks_m2) memcpy(ranks_m2, hr.data() + sim.L.M(), DD * sizeof(double));
     if (ranks_counters) { ranks_counters[0] = cnt[MergeLayout::SAMPLES]; ranks_counters[1] = cnt[MergeLayout::CHAINS]; }
     return KLARA_OK;
+}
+
+// The R-hat kernels (klara_rhat.h) on a caller's per-chain sums (unsplit) and / or a caller's value history (split), through the launch functions of the job
+// path: the chains [c0, c0 + Nr) staged into buf as klara_gather_rhat stages them (zeros | mean_r, Bsum_r, Wsum_r | the counters are the caller's)
+static hipError_t selftest_rhat_one(DeviceArrays& mem, const MergeLayout& L, bool split, const double* dsum, const double* dsumsq, const double* dX,
+                                    const long long* dheld, long long nsaved, const double* hist, long long ncols, long long N, long long c0, long long Nr,
+                                    int D, double* partial, double* buf, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(buf, 0, L.size() * sizeof(double), st);
+    if (e != hipSuccess) return e;
+    if (!split) return rhat_sums_async(st, dsum + c0 * D, dsumsq + c0 * D, dX + c0 * D, dheld + c0, Nr, D, nsaved, partial, buf + L.mean_r(), buf + L.extra());
+    // the shard's chains as a history of their own: column t at dh + t Nr D
+    const size_t nd = (size_t)Nr * D;
+    double *dh = nullptr, *half = nullptr;
+    e = mem.alloc(&dh, (size_t)ncols * nd);
+    if (e == hipSuccess) e = mem.alloc(&half, 4 * nd);
+    if (e == hipSuccess) e = hipMemcpy2D(dh, nd * sizeof(double), hist + (size_t)c0 * D, (size_t)N * D * sizeof(double), nd * sizeof(double), (size_t)ncols,
+                                         hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rhat_split_async(st, dh, ncols, Nr, D, half, partial, buf + L.mean_r(), buf + L.extra());
+    return e;
+}
+
+extern "C" klara_status klara_selftest_rhat(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
+                                            const double* X, const int64_t* held, int64_t ncols, const double* hist, int32_t nranks, const int64_t* bounds,
+                                            double* out, double* ranks_out, double* split_out, double* split_ranks_out, uint64_t* counters)
+{
+    const bool sums = sum || sumsq || X || held;
+    if (!bounds || nchains <= 0 || ndims < 1 || ndims > 1024 || nranks < 1 || (!sums && !hist)) return KLARA_ERR_INVALID_ARG;
+    if (sums && (!sum || !sumsq || !X || !held || nsaved < 1)) return KLARA_ERR_INVALID_ARG;
+    if (hist && ncols < 2) return KLARA_ERR_INVALID_ARG;
+    if (bounds[0] != 0 || bounds[nranks] != nchains) return KLARA_ERR_INVALID_ARG;
+    for (int r = 0; r < nranks; ++r) if (bounds[r + 1] <= bounds[r]) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    const size_t D = (size_t)ndims, nd = (size_t)nchains * D;
+    const long long N = nchains;
+    const hipStream_t st = 0;
+    const MergeLayout L{ D, D, D };
+    DeviceArrays mem;
+    double *dsum = nullptr, *dsumsq = nullptr, *dX = nullptr, *partial = nullptr, *one = nullptr;
+    long long* dheld = nullptr;
+    hipError_t e = mem.alloc(&partial, klara_rhat_partial_elems(ndims));
+    if (e == hipSuccess) e = mem.alloc(&one, L.size());
+    if (sums) {
+        if (e == hipSuccess) e = mem.alloc(&dsum, nd);
+        if (e == hipSuccess) e = mem.alloc(&dsumsq, nd);
+        if (e == hipSuccess) e = mem.alloc(&dX, nd);
+        if (e == hipSuccess) e = mem.alloc(&dheld, (size_t)N);
+        if (e == hipSuccess) e = hipMemcpy(dsum, sum, nd * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dsumsq, sumsq, nd * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dX, X, nd * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dheld, held, (size_t)N * sizeof(long long), hipMemcpyHostToDevice);
+    }
+    klara_status status = KLARA_OK;
+    for (int split = 0; split < 2 && e == hipSuccess && status == KLARA_OK; ++split) {
+        if (split ? !hist : !sums) continue;
+        const unsigned long long n = (unsigned long long)(split ? ncols / 2 : nsaved), per = split ? 2 : 1;     // samples per unit; units per chain
+        double* dst[2] = { split ? split_out : out, split ? split_ranks_out : ranks_out };
+        uint64_t* cdst = counters ? counters + 4 * split : nullptr;
+        std::vector<double> host(L.size());
+        // (a) all the chains: one staging buffer, no merge
+        unsigned long long cnt[MergeLayout::NCOUNTERS];
+        rhat_counters(per * (unsigned long long)N, n, cnt);
+        e = selftest_rhat_one(mem, L, split != 0, dsum, dsumsq, dX, dheld, (long long)nsaved, hist, (long long)ncols, N, 0, N, ndims, partial, one, st);
+        if (e == hipSuccess) e = hipMemcpy(one + L.counters(), cnt, sizeof(cnt), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) e = hipMemcpy(host.data(), one, L.size() * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) break;
+        uint64_t units = 0; int64_t nper = 0;
+        double* o = dst[0];
+        status = rhat_finish(D, host.data(), false, o, o ? o + D : nullptr, o ? o + 2 * D : nullptr, o ? o + 3 * D : nullptr, &units, &nper);
+        if (cdst) { cdst[0] = units; cdst[1] = (uint64_t)nper; }
+        if (status != KLARA_OK) break;
+        // (b) every rank's mean_r | Bsum_r | Wsum_r and its counters, then the merge
+        SimRanks sim{ L, st };
+        e = sim.alloc(mem, nranks);
+        for (int r = 0; r < nranks && e == hipSuccess; ++r) {
+            const long long Nr = bounds[r + 1] - bounds[r];
+            e = selftest_rhat_one(mem, L, split != 0, dsum, dsumsq, dX, dheld, (long long)nsaved, hist, (long long)ncols, N, bounds[r], Nr, ndims, partial,
+                                  sim.buf[r], st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = sim.set_rhat_counters(r, per * (unsigned long long)Nr, n);
+        }
+        std::vector<double> hr;
+        if (e == hipSuccess) e = sim.merge(hr);
+        if (e != hipSuccess) break;
+        o = dst[1];
+        status = rhat_finish(D, hr.data(), true, o, o ? o + D : nullptr, o ? o + 2 * D : nullptr, o ? o + 3 * D : nullptr, &units, &nper);
+        if (cdst) { cdst[2] = units; cdst[3] = (uint64_t)nper; }
+    }
+    const bool clean = mem.release();
+    if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
+    return status;
 }

@@ -244,6 +244,63 @@ def allreduce_covariance(local: Dict[str, np.ndarray], group=None, device=None) 
     return out
 
 
+def gather_engine_rhat_klara(engine, comm: KlaraComm, split: bool = False) -> Dict[str, np.ndarray]:
+    """R-hat over every rank's chains through the C ABI alone: klara_gather_rhat(h, comm, ...) — the ranks' (chains, mean of chain means, bsum) merged as
+    the moments are and wsum summed, four RCCL all-reduces on the job's stream.  Keys as Engine.rhat."""
+    return engine.rhat(split=split, comm=comm.handle)
+
+
+def rhat_from_sums(wsum, bsum, m, n):
+    """R-hat from wsum = sum of the units' M2 and bsum = sum (unit mean - mean)^2 over m units of n samples each, as klara_gather_rhat evaluates it:
+    NaN for m < 2 or n < 2, plain IEEE division otherwise (wsum = 0 with bsum > 0: inf; both zero: NaN)."""
+    wsum = np.asarray(wsum, dtype=np.float64); bsum = np.asarray(bsum, dtype=np.float64)
+    if m < 2 or n < 2:
+        return np.full(wsum.shape, np.nan)
+    m, n = float(m), float(n)
+    with np.errstate(all="ignore"):
+        W = wsum / (m * (n - 1.0)); Bn = bsum / (m - 1.0)
+        return np.sqrt((((n - 1.0) / n) * W + Bn) / W)
+
+
+def allreduce_rhat(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
+    """klara_gather_rhat's between-rank merge through torch.distributed, for a host that brings its own transport: `local` is this rank's
+    Engine.rhat() (mean[D], wsum[D], bsum[D], nchains, nper).  Four SUM all-reduces in the library's order — the counters (m_r n_r, m_r n_r^2, m_r),
+    m_r mean_r, bsum_r + m_r (mean_r - mean)^2, wsum_r — entered by every rank whatever its values are.  Raises ValueError, on every rank, when the
+    ranks do not hold the same number of samples per chain.  Works without torch.distributed initialised (single process)."""
+    import torch
+    import torch.distributed as dist
+
+    mean_l = np.asarray(local["mean"], dtype=np.float64).ravel(); b_l = np.asarray(local["bsum"], dtype=np.float64).ravel()
+    w_l = np.asarray(local["wsum"], dtype=np.float64).ravel()
+    m_l, n_l = int(local["nchains"]), int(local["nper"])
+    live = dist.is_available() and dist.is_initialized()
+    if live and device is None:
+        device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+
+    def reduce_sum(buf: np.ndarray) -> np.ndarray:
+        if not live:
+            return buf
+        t = torch.from_numpy(np.ascontiguousarray(buf)).to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        return t.cpu().numpy()
+
+    cnt = reduce_sum(np.array([m_l * n_l, m_l * n_l * n_l, m_l], dtype=np.int64))
+    sn, sn2, m = (int(v) for v in cnt)
+    with np.errstate(all="ignore"):
+        wmean = reduce_sum(float(m_l) * mean_l)
+        mean = wmean / float(m) if m > 0 else np.zeros_like(wmean)
+        d = mean_l - mean
+        bsum = reduce_sum(b_l + float(m_l) * (d * d))
+        wsum = reduce_sum(w_l)
+    if sn * sn != m * sn2:                                   # the n_r are all equal exactly when (sum m n)^2 = sum m * sum m n^2
+        raise ValueError("allreduce_rhat: the ranks hold different numbers of saved steps")
+    n = sn // m if m else 0
+    if n == 0:
+        z = np.zeros_like(mean)
+        return {"rhat": np.full(mean.shape, np.nan), "mean": z, "wsum": z.copy(), "bsum": z.copy(), "nchains": 0, "nper": 0}
+    return {"rhat": rhat_from_sums(wsum, bsum, m, n), "mean": mean, "wsum": wsum, "bsum": bsum, "nchains": m, "nper": n}
+
+
 def allreduce_summaries(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
     """The same exchange for a caller that holds pooled RAW sums: `local` = sum[D], sumsq[D], naccept, ntransitions, nsamples of this
     rank's chains.  Returns the global sums plus the posterior moments (mean, var) and the acceptance rate; the variance comes from

@@ -433,6 +433,18 @@ class Engine:
         L.check(self._lib.klara_gather_covariance(self._h, comm, mean.ctypes.data, m2.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_covariance")
         return mean, m2, int(ns.value), int(nc.value)
 
+    def rhat(self, split: bool = False, comm=None):
+        """The Gelman–Rubin diagnostic over this handle's chains — or, with a klara_comm handle, over every rank's (klara_gather_rhat): dict of rhat[D],
+        mean[D] (the mean of the chain means), wsum[D] (sum of the chains' M2), bsum[D] (sum of (chain mean - mean)^2), nchains and nper (the units the
+        formulas ran on).  split=False works from the running sums (MON_SUMMARIES); split=True is the split form from the stored history (MON_HISTORY,
+        no ring, at least 4 saved steps): nchains is then the number of half-chains and nper their length."""
+        out = {k: np.empty(self.ndims) for k in ("rhat", "mean", "wsum", "bsum")}
+        nc, npu = C.c_uint64(0), C.c_int64(0)
+        L.check(self._lib.klara_gather_rhat(self._h, comm, 1 if split else 0, out["rhat"].ctypes.data, out["mean"].ctypes.data, out["wsum"].ctypes.data,
+                                            out["bsum"].ctypes.data, C.byref(nc), C.byref(npu)), "klara_gather_rhat")
+        out["nchains"], out["nper"] = int(nc.value), int(npu.value)
+        return out
+
     def chain(self, local_chain: int) -> np.ndarray:
         """One chain's saved values in Klara's NState layout: (ndims, nsaved), column-major."""
         n = C.c_int64(0)

@@ -82,6 +82,27 @@ def pooled_cov(values) -> np.ndarray:
     return (xc @ xc.T) / (x.shape[1] - 1)
 
 
+def rhat(values, split: bool = False) -> np.ndarray:
+    """The Gelman–Rubin potential scale reduction factor per dimension: `values` is (m chains, n samples, D).  With W the mean of the chains' sample
+    variances and B / n the sample variance of the chain means, R-hat = sqrt(((n - 1) / n W + B / n) / W) (Gelman & Rubin 1992).  split=True cuts every
+    chain into the halves [0, h) and [n - h, n), h = n // 2 (an odd n drops the middle sample), and takes them as 2 m chains of h samples (BDA3 section
+    11.4).  NaN for fewer than 2 chains or 2 samples per chain; plain IEEE division otherwise.  The literal NumPy form of klara_gather_rhat."""
+    x = np.asarray(values, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if split:
+        h = x.shape[1] // 2
+        x = np.stack([x[:, :h], x[:, x.shape[1] - h:]], axis=1).reshape(2 * x.shape[0], h, x.shape[2])
+    m, n, D = x.shape
+    if m < 2 or n < 2:
+        return np.full(D, np.nan)
+    mu = x.mean(axis=1)                                          # (m, D)
+    W = ((x - mu[:, None, :]) ** 2).sum(axis=1).sum(axis=0) / (m * (n - 1))
+    Bn = ((mu - mu.mean(axis=0)) ** 2).sum(axis=0) / (m - 1)
+    with np.errstate(all="ignore"):
+        return np.sqrt(((n - 1) / n * W + Bn) / W)
+
+
 def _per_dim(fn, value: np.ndarray, *args) -> np.ndarray:
     value = np.asarray(value)
     return np.array([fn(value[i, :], *args) for i in range(value.shape[0])])
