@@ -291,6 +291,14 @@ typedef struct klara_desc {
                                     (RAM.jl:100).  Required for KLARA_SAMPLER_RAM; NULL for every other sampler (else KLARA_ERR_INVALID_ARG) */
     double   ram_targetrate;     /* RAM: target acceptance rate, in (0, 1) (RAM.jl:101); 0 for every other sampler */
     double   ram_gamma;          /* RAM: exponent of the step size eta = min(1, D count^-gamma), in (0.5, 1] (RAM.jl:102); 0 for every other sampler */
+    const double* marg_lo;       /* pooled marginal histograms (klara_gather_histogram), switched on by marg_nbins > 0: the lower bounds, D doubles, copied at create */
+    const double* marg_hi;       /* ... and the upper bounds, D doubles, lo[d] < hi[d], all finite.  Both NULL when marg_nbins = 0 (else KLARA_ERR_INVALID_ARG) */
+    int64_t  marg_nbins;         /* 0: off (nothing changes); 1..KLARA_MARG_MAX_BINS: after every launch the saved samples of all chains are counted per dimension
+                                    into marg_nbins equal bins over [lo[d], hi[d]) plus an underflow and an overflow slot (the rule is stated at
+                                    klara_gather_histogram).  A consumer of the saved samples, as acov_maxlag and KLARA_MON_COVARIANCE are: the values are kept
+                                    (a 32-column ring of its own when no value history was asked for), the job runs as one chain partition, and a job that cannot
+                                    keep a value history is refused as with KLARA_MON_HISTORY.  Every sampler, target and ndims the library accepts.  The transition
+                                    kernels never see the field: the chains of a job are the same bits with and without it. */
 
     uint64_t seed;               /* Philox key                                                       */
     uint32_t monitor;            /* KLARA_MON_* bits                                                 */
@@ -406,6 +414,33 @@ klara_status klara_gather_covariance(klara_handle* h, klara_comm* comm, double* 
  * zeros for the other outputs, KLARA_OK.  The call only reads the job's state: a job that goes on after it produces the same bits as one that never called it. */
 klara_status klara_gather_rhat(klara_handle* h, klara_comm* comm, int32_t split, double* rhat, double* mean, double* wsum, double* bsum,
                                uint64_t* nchains, int64_t* nper);
+
+/* The pooled marginal histograms (requires klara_desc.marg_nbins > 0, else KLARA_ERR_STATE): what credible intervals, medians and tail probabilities are
+ * read from when the job is too large to keep its values.  With nbins = marg_nbins and, per dimension d, lo = marg_lo[d], hi = marg_hi[d] and
+ * inv_w = nbins / (hi - lo) (formed once on the host, in double), a saved sample x of dimension d is counted in one of nbins + 2 slots:
+ *   slot 0 (underflow)        if x < lo;
+ *   slot nbins + 1 (overflow) if !(x < hi): x >= hi, +inf and NaN;
+ *   slot 1 + min(nbins - 1, (int)floor((x - lo) * inv_w)) otherwise.
+ * (x - lo) * inv_w is a subtraction followed by a multiplication: nothing in it can contract to an fma, on any layer.  This index formula is the contract;
+ * the edges lo + k (hi - lo) / nbins that the bindings report are documentation and may differ from it by an ulp at a boundary.
+ * counts is ndims x (nbins + 2) row-major, uint64, over all chains of the handle and all saved steps: integer sums, exact in any order — the same result for
+ * every cut of the steps into launches.  *nsamples = chains x saved steps (= every row's total), *nchains = chains.  Counted after every launch from the value
+ * ring (klara.jl_amd/csrc/klara_marg.h); this call only reads.  comm = NULL: this handle's chains only; otherwise collective: every rank calls it, on handles
+ * of the same ndims (a rank that fails the argument and state checks above returns before the collectives, as with the other gather calls).  First an integer
+ * maximum all-reduce over nbins and the bit patterns of lo and hi and their complements, which every rank enters and waits for: ranks whose (nbins, lo, hi)
+ * differ then ALL return KLARA_ERR_STATE, before anything whose length depends on nbins is exchanged.  Otherwise the counts merge by one 64-bit integer sum
+ * all-reduce.  Any output pointer may be NULL.  Before the first saved sample: zeros.  klara_set_state and klara_reset clear the counts. */
+#define KLARA_MARG_MAX_BINS 1024
+klara_status klara_gather_histogram(klara_handle* h, klara_comm* comm, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains);
+
+/* Quantiles from such counts: pure host code, no device — the one statement of the rule for C, Python and Julia callers.  counts is ndims x (nbins + 2) as
+ * above, lo and hi ndims each, probs nprobs values in (0, 1], out ndims x nprobs row-major.  Per dimension, n = the row's total and w = (hi - lo) / nbins:
+ *   k = max(1, ceil(p n));  b = the first slot whose cumulative count reaches k;
+ *   b = 0: -inf;  b = nbins + 1: +inf;  otherwise  (lo + (b - 1) w) + w (k - cum_before) / count_b.
+ * A range chosen badly shows up as infinities and as the two outer counts, never as a silently clipped number.  n = 0: NaN.
+ * KLARA_ERR_INVALID_ARG for a NULL argument, ndims < 1, nbins outside 1..KLARA_MARG_MAX_BINS, nprobs < 1 or a p outside (0, 1]. */
+klara_status klara_histogram_quantiles(const uint64_t* counts, int32_t ndims, int64_t nbins, const double* lo, const double* hi, int32_t nprobs,
+                                       const double* probs, double* out);
 
 /* Memory-safety aid (tests only).  With KLARA_DEBUG_CANARY=1 in the environment every device array the library allocates lies between
  * two 4 KiB canaries of a signalling-NaN pattern; klara_destroy returns KLARA_ERR_STATE when a kernel of the job wrote into one, and this
@@ -607,6 +642,20 @@ klara_status klara_selftest_pooled(int32_t device, int64_t nchains, int32_t ndim
 klara_status klara_selftest_covariance(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
                                        const int64_t* splits, int32_t nranks, const int64_t* bounds, double* mean, double* m2, double* ranks_mean,
                                        double* ranks_m2, uint64_t* ranks_counters);
+
+/* Self-test hook: the marginal histogram kernel on a caller's value history.  hist holds ncols (>= 1) saved steps of nchains x ndims values as the device
+ * keeps a value history (column t at hist + t * nchains * ndims), ndims 1..1024; it is fed launch by launch through the launch function the job path uses —
+ * launch j brings splits[j] saved steps (0..32 each), the splits sum to ncols — and the table is read back as klara_gather_histogram reads it: counts,
+ * ndims x (nbins + 2).  KLARA_ERR_INVALID_ARG (before any HIP call) for a NULL argument, nchains <= 0, ndims outside 1..1024, ncols < 1, nbins outside
+ * 1..KLARA_MARG_MAX_BINS, a bound that is not finite, lo >= hi, a split outside 0..32 or splits that do not sum to ncols. */
+klara_status klara_selftest_marginals(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
+                                      const int64_t* splits, int64_t nbins, const double* lo, const double* hi, uint64_t* counts);
+
+/* Self-test hook, no device needed: the agreement step of klara_gather_histogram over simulated ranks.  Rank r holds nbins[r], lo[r * ndims ..] and
+ * hi[r * ndims ..]; every rank's words are formed as that call stages them, the maximum all-reduce is replaced by a host maximum over the ranks, and the
+ * verdict every rank reaches is returned: KLARA_OK when all ranks hold the same (nbins, lo, hi) bit for bit, KLARA_ERR_STATE otherwise (-0.0 and 0.0 differ).
+ * KLARA_ERR_INVALID_ARG for a NULL argument, nranks < 1 or ndims outside 1..1024. */
+klara_status klara_selftest_histogram_ranks(int32_t nranks, int32_t ndims, const int64_t* nbins, const double* lo, const double* hi);
 
 /* Self-test hook: the R-hat kernels on a caller's data, through the launch functions klara_gather_rhat uses.  Unsplit: the per-chain running sums sum,
  * sumsq, X (nchains x ndims, ndims 1..1024) and held (nchains) over nsaved (>= 1) saved steps, as for klara_selftest_pooled; all four NULL: skipped.

@@ -38,7 +38,8 @@ import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
        check_custom_target_softabs, SoftAbs, ramfactor,
-       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat, KlaraDesc, klara_desc
+       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat,
+       pooledhistogram, pooledquantiles, gather_histogram, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
 # ---------------------------------------------------------------- Julia 0.6 / >= 0.7 compatibility (the only version-dependent code)
@@ -60,6 +61,7 @@ const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
 const MON_ACCEPT, MON_HISTORY, MON_SUMMARIES, MON_HIST_LT, MON_HIST_GRAD, MON_HIST_LLLP = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
+const MARG_MAX_BINS = 1024             # KLARA_MARG_MAX_BINS
 const MON_COVARIANCE = 0x40            # KLARA_MON_COVARIANCE: the pooled D x D cross-products, accumulated while sampling (pooledcovariance)
 
 # struct klara_desc — field order/types exactly as include/klara_hip.h
@@ -81,6 +83,7 @@ struct KlaraDesc
     hist_ring_cols::Int64; acov_maxlag::Int32; sparse_moves::Int32
     smmala_softabs::Float64
     ram_S0::Ptr{Float64}; ram_targetrate::Float64; ram_gamma::Float64
+    marg_lo::Ptr{Float64}; marg_hi::Ptr{Float64}; marg_nbins::Int64
     seed::UInt64; monitor::UInt32; steps_per_launch::Int32; stream::Ptr{Cvoid}
 end
 
@@ -99,6 +102,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
                     custom_src=Cstring(C_NULL), custom_data=Ptr{Float64}(C_NULL), custom_ndata=0, bm_batchlen=0,
                     hist_ring_cols=0, acov_maxlag=0, sparse_moves=0, smmala_softabs=0.0,
                     ram_S0=Ptr{Float64}(C_NULL), ram_targetrate=0.0, ram_gamma=0.0,
+                    marg_lo=Ptr{Float64}(C_NULL), marg_hi=Ptr{Float64}(C_NULL), marg_nbins=0,
                     seed=UInt64(0), monitor=UInt32(0), steps_per_launch=0, stream=C_NULL)
     KlaraDesc(UInt32(sizeof(KlaraDesc)), KLARA_ABI_VERSION,
               sampler, target, tuner, tuner_mode,
@@ -116,6 +120,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               custom_src, custom_data, custom_ndata, bm_batchlen,
               hist_ring_cols, acov_maxlag, sparse_moves, smmala_softabs,
               ram_S0, ram_targetrate, ram_gamma,
+              marg_lo, marg_hi, marg_nbins,
               seed, monitor, steps_per_launch, stream)
 end
 
@@ -236,7 +241,7 @@ end
 function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
                   tuner=nothing, outopts::Dict=Dict{Symbol, Any}(), pooled::Bool=false, nchains::Integer=1,
                   seed::Integer=rand(UInt64), chain_offset::Integer=0, device::Integer=0, steps_per_launch::Integer=0,
-                  summaries::Bool=true, bm_batchlen::Integer=0, covariance::Bool=false)
+                  summaries::Bool=true, bm_batchlen::Integer=0, covariance::Bool=false, marginals=nothing)
     X0 = startmatrix(v0[parameter.key], nchains)                          # D x N: column = chain == N x D row-major
     D, N = size(X0)
     t = parameter.target
@@ -335,6 +340,15 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         (m == :loglikelihood || m == :logprior) && (mon |= MON_HIST_LLLP)
     end
     kw[:monitor] = mon
+    if marginals !== nothing                                              # (nbins, lo, hi): the pooled marginal histograms; lo, hi scalars or D values
+        nb, mlo, mhi = marginals
+        vlo = isa(mlo, Number) ? fill(Float64(mlo), D) : convert(Vector{Float64}, mlo)
+        vhi = isa(mhi, Number) ? fill(Float64(mhi), D) : convert(Vector{Float64}, mhi)
+        (length(vlo) == D && length(vhi) == D) || error("marginals: lo and hi must be scalars or have one entry per dimension")
+        push!(keep, vlo); push!(keep, vhi)
+        kw[:marg_lo] = pointer(vlo); kw[:marg_hi] = pointer(vhi); kw[:marg_nbins] = Int64(nb)
+        oo[:marginals] = (Int64(nb), vlo, vhi)
+    end
     desc = klara_desc(; kw...)
     h = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:klara_create, lib), Cint, (Ref{KlaraDesc}, Ref{Ptr{Cvoid}}), desc, h), "klara_create")
@@ -572,6 +586,41 @@ function pooledcovariance(job::HIPMCJob)
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{UInt64}),
                 job.handle, C_NULL, m, m2, ns, nc), "klara_gather_covariance")
     (m, reshape(m2, job.ndims, job.ndims) ./ (Float64(ns[]) - 1.0), ns[], nc[])
+end
+# the (nbins, lo, hi) a job was built with, the documented edges, and the one call behind pooledhistogram / gather_histogram (comm: a communicator's handle or C_NULL)
+function marginals_of(job::HIPMCJob)
+    haskey(job.outopts, :marginals) || error("the job was built without marginals=(nbins, lo, hi)")
+    job.outopts[:marginals]
+end
+function histogram_edges(nb, lo, hi)
+    Float64[lo[d] + k * ((hi[d] - lo[d]) / nb) for k in 0:nb, d in 1:length(lo)]
+end
+function histogram_of(job::HIPMCJob, comm::Ptr{Cvoid})
+    nb, lo, hi = marginals_of(job)
+    counts = zeros(UInt64, nb + 2, job.ndims)
+    ns = Ref{UInt64}(0); nc = Ref{UInt64}(0)
+    check(ccall((:klara_gather_histogram, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt64}, Ref{UInt64}, Ref{UInt64}),
+                job.handle, comm, counts, ns, nc), "klara_gather_histogram")
+    (counts, histogram_edges(nb, lo, hi), ns[], nc[])
+end
+# The pooled marginal histograms of a job built with marginals=(nbins, lo, hi) (klara_gather_histogram): per dimension, the saved samples of all chains
+# counted after every launch into nbins equal bins over [lo, hi) plus an underflow and an overflow slot; no history is stored.  (counts, edges, nsamples,
+# chains): counts is (nbins + 2) x D (column d = dimension d: the C table's rows), edges (nbins + 1) x D with edges[k + 1, d] = lo[d] + k (hi[d] - lo[d]) / nbins
+# — documentation: the index formula of include/klara_hip.h is the contract.  Over every chain of every GPU (the ranks' jobs built with the same marginals):
+gather_histogram(job::HIPMCJob, comm::HIPComm) = histogram_of(job, comm.handle)
+# ... and of this job's chains alone (no communicator, no RCCL)
+pooledhistogram(job::HIPMCJob) = histogram_of(job, Ptr{Cvoid}(C_NULL))
+# Quantiles from those counts (klara_histogram_quantiles, host code): length(probs) x D, probs in (0, 1]; -Inf / Inf where the order statistic lies outside
+# [lo, hi) — a range chosen badly is never clipped silently —, NaN before the first saved sample
+function pooledquantiles(job::HIPMCJob, probs)
+    nb, lo, hi = marginals_of(job)
+    counts = pooledhistogram(job)[1]
+    p = convert(Vector{Float64}, collect(probs))
+    out = newarray(Float64, length(p), job.ndims)
+    check(ccall((:klara_histogram_quantiles, lib), Cint,
+                (Ptr{UInt64}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
+                counts, Int32(job.ndims), Int64(nb), lo, hi, Int32(length(p)), p, out), "klara_histogram_quantiles")
+    out
 end
 # The Gelman–Rubin diagnostic over all chains (klara_gather_rhat; Klara has no counterpart: its job is one chain): (rhat, mean of the chain means, wsum =
 # sum of the chains' M2, bsum = sum (chain mean - mean)^2, units, samples per unit).  split=false works from the running sums; split=true is the split

@@ -31,6 +31,7 @@ TUNE_PER_CHAIN, TUNE_POOLED = 0, 1
 MON_ACCEPT, MON_HISTORY, MON_SUMMARIES, MON_HIST_LT, MON_HIST_GRAD, MON_HIST_LLLP = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
 MON_COVARIANCE = 0x40            # KLARA_MON_COVARIANCE: the pooled D x D cross-products, accumulated while sampling (klara_gather_covariance)
 COV_MAX_DIMS = 256                # KLARA_COV_MAX_DIMS
+MARG_MAX_BINS = 1024              # KLARA_MARG_MAX_BINS
 
 ZV_LINEAR, ZV_QUADRATIC, ZV_MAX_TERMS = 1, 2, 128      # KLARA_ZV_*
 
@@ -59,6 +60,7 @@ class KlaraDesc(C.Structure):
         ("hist_ring_cols", C.c_int64), ("acov_maxlag", C.c_int32), ("sparse_moves", C.c_int32),
         ("smmala_softabs", C.c_double),
         ("ram_S0", _dp), ("ram_targetrate", C.c_double), ("ram_gamma", C.c_double),
+        ("marg_lo", _dp), ("marg_hi", _dp), ("marg_nbins", C.c_int64),
         ("seed", C.c_uint64), ("monitor", C.c_uint32), ("steps_per_launch", C.c_int32),
         ("stream", C.c_void_p),
     ]
@@ -86,6 +88,7 @@ EXPORTS = [
     "klara_selftest_rocrand_blocks", "klara_selftest_math", "klara_selftest_normal_tail", "klara_selftest_transition_normals", "klara_selftest_mfma_f64", "klara_selftest_mfma_f64_4x4x4", "klara_selftest_chain_stats", "klara_selftest_pooled", "klara_strerror",
     "klara_comm_unique_id", "klara_comm_init", "klara_comm_info", "klara_comm_destroy", "klara_gather_summaries", "klara_gather_moments", "klara_gather_covariance", "klara_selftest_covariance",
     "klara_gather_rhat", "klara_selftest_rhat",
+    "klara_gather_histogram", "klara_histogram_quantiles", "klara_selftest_marginals", "klara_selftest_histogram_ranks",
     "klara_check_custom_target", "klara_check_custom_target_softabs", "klara_compile_log", "klara_selftest_plan", "klara_selftest_canary", "klara_abi_version",
 ]
 
@@ -159,6 +162,11 @@ def load() -> C.CDLL:
         "klara_gather_rhat": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
         "klara_selftest_rhat": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "klara_gather_histogram": [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+        "klara_histogram_quantiles": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+        "klara_selftest_marginals": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p],
+        "klara_selftest_histogram_ranks": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_selftest_canary": [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
         "klara_check_custom_target": [C.c_char_p, C.c_int32, C.c_int32],
         "klara_check_custom_target_softabs": [C.c_char_p, C.c_int32],

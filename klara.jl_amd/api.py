@@ -25,7 +25,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _lib as L
-from .engine import CustomTarget, Engine, GaussDenseTarget, GaussDiagTarget, HierNormalTarget, LogisticTarget
+from .engine import CustomTarget, Engine, GaussDenseTarget, GaussDiagTarget, HierNormalTarget, LogisticTarget, Marginals, histogram_quantiles
 
 
 # ------------------------------------------------------------------ range (src/ranges/BasicMCRange.jl)
@@ -474,6 +474,23 @@ def pooled_cov(job_or_chains, comm=None) -> np.ndarray:
     return m2 / (ns - 1)
 
 
+def pooled_hist(job_or_chains, comm=None):
+    """(counts[D, nbins + 2], edges[D, nbins + 1]) of a job run with marginals=: every dimension's saved samples over all chains, counted while sampling
+    (Engine.pooled_histogram); columns 0 and nbins + 1 are the underflow and the overflow.  `comm`: a klara_comm handle, to pool over every rank's chains."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    counts, edges, _, _ = job.engine.pooled_histogram(comm)
+    return counts, edges
+
+
+def pooled_quantiles(job_or_chains, probs, comm=None) -> np.ndarray:
+    """(D, len(probs)) posterior quantiles from pooled_hist's counts (klara_histogram_quantiles): within one bin width of the order statistic; -inf / +inf
+    where it lies outside the job's [lo, hi) — a range chosen badly is never clipped silently."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    m = job.engine.marginals
+    counts, _, _, _ = job.engine.pooled_histogram(comm)
+    return histogram_quantiles(counts, m.nbins, m.lo, m.hi, probs)
+
+
 def rhat(job_or_chains, split: bool = False, comm=None) -> np.ndarray:
     """The potential scale reduction factor R-hat (Gelman & Rubin 1992) per dimension over all chains of a job, formed on the device (Engine.rhat):
     from the running sums, or with split=True the split form (BDA3 section 11.4) from the stored history; `comm`: a klara_comm handle, to take every
@@ -533,13 +550,14 @@ class BasicMCJob:
     the first chain), `device`, `seed` (default: a fresh key per job, see "random streams of jobs" above), `steps_per_launch`; `bm_batchlen` > 0 keeps streaming batch means so that
     `chain_mcvar(chain, "bm", bm_batchlen)` needs no stored history (destination "none"); `acov_maxlag` > 0 does the same for
     `chain_mcvar(chain, "imse" | "ipse", maxlag=acov_maxlag)` (autocovariances accumulated while sampling); `covariance=True` accumulates the
-    pooled D x D cross-products of all chains' saved samples on the matrix cores (`pooled_cov`, `pooled_cor`), again with no stored history.
+    pooled D x D cross-products of all chains' saved samples on the matrix cores (`pooled_cov`, `pooled_cor`), again with no stored history;
+    `marginals=Marginals(nbins, lo, hi)` counts every dimension's saved samples into bins (`pooled_hist`, `pooled_quantiles`), likewise.
     """
 
     def __init__(self, model: GenericModel, sampler: MCSampler, mcrange: BasicMCRange, v0: Dict[str, Sequence],
                  tuner: Optional[MCTuner] = None, outopts: Optional[dict] = None, *, seed: Optional[int] = None,
                  chain_offset: int = 0, device: int = 0, steps_per_launch: int = 0, summaries: bool = True,
-                 bm_batchlen: int = 0, acov_maxlag: int = 0, sparse_moves: int = 0, covariance: bool = False):
+                 bm_batchlen: int = 0, acov_maxlag: int = 0, sparse_moves: int = 0, covariance: bool = False, marginals=None):
         self.model, self.sampler, self.range = model, sampler, mcrange
         self.seed = _next_job_seed() if seed is None else int(seed)
         seed = self.seed
@@ -595,7 +613,7 @@ class BasicMCJob:
                   burnin=mcrange.burnin, thinning=mcrange.thinning, tuner=self.tuner.kind,
                   period=self.tuner.period, verbose=self.tuner.verbose, seed=seed, chain_offset=chain_offset,
                   device=device, monitor=monitor, steps_per_launch=steps_per_launch, bm_batchlen=int(bm_batchlen),
-                  acov_maxlag=int(acov_maxlag), sparse_moves=int(sparse_moves),
+                  acov_maxlag=int(acov_maxlag), sparse_moves=int(sparse_moves), marginals=marginals,
                   hist_ring_cols=int(self.outopts["chunk"]) if self.outopts["destination"] == "iostream" else 0)
         self.bm_batchlen, self.acov_maxlag = int(bm_batchlen), int(acov_maxlag)
         if isinstance(sampler, MH):

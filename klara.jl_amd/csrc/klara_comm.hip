@@ -5,6 +5,7 @@
 #include <new>
 #include "klara_handle.h"
 #include "klara_rhat.h"
+#include "klara_marg_host.h"
 
 struct klara_comm {
     void* dl = nullptr;
@@ -93,16 +94,22 @@ static hipError_t comm_reserve(klara_comm* c, size_t n)
 struct CommSeq {
     klara_comm* c; hipStream_t st; bool bad = false;
     void H(hipError_t e) { if (e != hipSuccess) bad = true; }
-    bool reduce(size_t off, size_t n, bool is_u64)              // in-place all-reduce of c->buf[off, off + n) on the job's stream — latency-bound
+    bool reduce(size_t off, size_t n, bool is_u64, ncclRedOp_t op = ncclSum)     // in-place all-reduce of c->buf[off, off + n) on the job's stream — latency-bound
     {
         void* p = c->buf + off;
-        const bool ok = c->AllReduce(p, p, n, is_u64 ? ncclUint64 : ncclDouble, ncclSum, c->comm, st) == ncclSuccess;
+        const bool ok = c->AllReduce(p, p, n, is_u64 ? ncclUint64 : ncclDouble, op, c->comm, st) == ncclSuccess;
         if (!ok) bad = true;
         return ok;
     }
     bool finish(std::vector<double>& host)                      // the head of c->buf to the host; false: something failed on the way
     {
         H(hipMemcpyAsync(host.data(), c->buf, host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        H(hipStreamSynchronize(st));
+        return !bad;
+    }
+    bool finish(void* host, size_t bytes)                       // ... the same for a buffer of 64-bit integer words
+    {
+        H(hipMemcpyAsync(host, c->buf, bytes, hipMemcpyDeviceToHost, st));
         H(hipStreamSynchronize(st));
         return !bad;
     }
@@ -249,6 +256,47 @@ extern "C" klara_status klara_gather_covariance(klara_handle* h, klara_comm* c, 
     if (m2) memcpy(m2, host.data() + L.M(), DD * sizeof(double));
     if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
     if (nchains) *nchains = cnt[MergeLayout::CHAINS];
+    return KLARA_OK;
+}
+
+// The pooled marginal histograms (klara_marg.h): the table is only read.  With a communicator the staging buffer is, in 64-bit words,
+//   v [NV] | ~v [NV] | counts [D (nbins + 2)] | saved samples, chains,     NV = 2 D + 1, v = nbins and the bit patterns of lo and hi (klara_marg_host.h)
+// and the call is two steps.  (1) An integer maximum all-reduce over v | ~v, read back and waited for: max(~v) = ~min(v), so the ranks' parameters are the
+// same exactly when max(v) = ~max(~v) in every word (klara_marg_words_agree).  Every rank evaluates that on the same reduced values, so either all go on or
+// all return KLARA_ERR_STATE here — before the sum, whose length D (nbins + 2) would differ between ranks that differ in nbins.  (2) The 64-bit integer sum
+// of the counts and the two counters.  A local HIP failure before (1) is remembered and (1) is still entered; a rank that cannot read (1)'s result back
+// cannot know what the others decided and returns KLARA_ERR_HIP without entering (2).  NV comes from this rank's D: ranks of different ndims are not one job.
+extern "C" klara_status klara_gather_histogram(klara_handle* h, klara_comm* c, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains)
+{
+    if (!h) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state || !h->marg_counts) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    const size_t D = (size_t)h->d.ndims, K = klara_marg_count_elems(h->marg), NV = 2 * D + 1;
+    const uint64_t cnt[2] = { (uint64_t)h->marg_n * (uint64_t)h->d.nchains, (uint64_t)h->d.nchains };
+    std::vector<uint64_t> host(K + 2);                          // counts | saved samples, chains
+    if (!c) {
+        HIPCHK(hipMemcpyAsync(host.data(), h->marg_counts, K * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        memcpy(host.data() + K, cnt, sizeof(cnt));
+    } else {
+        HIPCHK(comm_reserve(c, 2 * NV + K + 2));
+        std::vector<uint64_t> v(2 * NV);
+        klara_marg_agreement_words(h->marg.nbins, h->marg_host.data(), h->marg_host.data() + D, (int32_t)D, v.data());
+        CommSeq q{ c, h->stream };
+        q.H(hipMemcpyAsync(c->buf, v.data(), v.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
+        q.reduce(0, 2 * NV, true, ncclMax);
+        if (!q.finish(v.data(), v.size() * sizeof(uint64_t))) return KLARA_ERR_HIP;
+        if (!klara_marg_words_agree(v.data(), NV)) return KLARA_ERR_STATE;      // the same verdict on every rank: none enters the sum
+        q.H(hipMemcpyAsync(c->buf + 2 * NV, h->marg_counts, K * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+        q.H(hipMemcpyAsync(c->buf + 2 * NV + K, cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream));
+        q.reduce(2 * NV, K + 2, true);
+        q.H(hipMemcpyAsync(host.data(), c->buf + 2 * NV, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        q.H(hipStreamSynchronize(h->stream));
+        if (q.bad) return KLARA_ERR_HIP;
+    }
+    if (counts) memcpy(counts, host.data(), K * sizeof(uint64_t));
+    if (nsamples) *nsamples = host[K];
+    if (nchains) *nchains = host[K + 1];
     return KLARA_OK;
 }
 

@@ -73,6 +73,11 @@ static klara_status validate_fields(const klara_desc* d)
     if (d->smmala_softabs > 0.0 && d->sampler != KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
     if (d->smmala_softabs > 0.0 && d->target != KLARA_TARGET_CUSTOM) return KLARA_ERR_UNSUPPORTED;
     if (d->sampler != KLARA_SAMPLER_RAM && (d->ram_S0 != nullptr || d->ram_targetrate != 0.0 || d->ram_gamma != 0.0)) return KLARA_ERR_INVALID_ARG;
+    // pooled marginal histograms: 0 = off and no pointers; 1 .. KLARA_MARG_MAX_BINS with finite lo[d] < hi[d]
+    if (d->marg_nbins < 0 || d->marg_nbins > KLARA_MARG_MAX_BINS) return KLARA_ERR_INVALID_ARG;
+    if (d->marg_nbins == 0 ? (d->marg_lo != nullptr || d->marg_hi != nullptr) : (!d->marg_lo || !d->marg_hi)) return KLARA_ERR_INVALID_ARG;
+    for (int i = 0; d->marg_nbins > 0 && i < d->ndims; ++i)
+        if (!std::isfinite(d->marg_lo[i]) || !std::isfinite(d->marg_hi[i]) || !(d->marg_lo[i] < d->marg_hi[i])) return KLARA_ERR_INVALID_ARG;
     if (d->steps_per_launch < 0 || d->tuner_score < 0 || d->tuner_score > 1) return KLARA_ERR_INVALID_ARG;   // (int32: a launch length always fits KLaunch::nsteps)
     return KLARA_OK;
 }
@@ -305,7 +310,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
         h->accept_cap = desc->nsteps;
         HIPCHK(mem.alloc(&h->accept, (size_t)desc->nsteps * N));
     }
-    const bool acov = desc->acov_maxlag > 0, cov = plan.cov, keeps = acov || cov;      // the consumers of the saved samples keep values
+    const bool acov = desc->acov_maxlag > 0, cov = plan.cov, marg = desc->marg_nbins > 0, keeps = acov || cov || marg;      // the consumers of the saved samples keep values
     if ((desc->monitor & (KLARA_MON_HISTORY | KLARA_MON_HIST_LT | KLARA_MON_HIST_GRAD | KLARA_MON_HIST_LLLP)) || keeps) {
         // npoststeps = length((burnin+1):thinning:nsteps)  (BasicMCRange.jl:26)
         h->hist_cols = (desc->nsteps - desc->burnin - 1) / desc->thinning + 1;
@@ -324,6 +329,16 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
             if (!klara_cov_plan((long long)N, (int)D, &h->cov)) return KLARA_ERR_UNSUPPORTED;
             HIPCHK(mem.alloc(&h->cov_S, klara_cov_S_elems(h->cov))); HIPCHK(mem.alloc(&h->cov_T, klara_cov_T_elems(h->cov)));
             HIPCHK(mem.alloc(&h->cov_pivot, D)); HIPCHK(mem.alloc(&h->cov_out, D + D * D));
+        }
+        if (marg) {
+            if (!klara_marg_plan((long long)N, (int)D, desc->marg_nbins, &h->marg)) return KLARA_ERR_UNSUPPORTED;
+            h->marg_host.assign(desc->marg_lo, desc->marg_lo + D);
+            h->marg_host.insert(h->marg_host.end(), desc->marg_hi, desc->marg_hi + D);
+            std::vector<double> par(h->marg_host);
+            for (size_t i = 0; i < D; ++i) par.push_back(klara_marg_inv_w(desc->marg_nbins, desc->marg_lo[i], desc->marg_hi[i]));
+            KCHK(upload(mem, &h->marg_par, par.data(), par.size()));
+            HIPCHK(mem.alloc(&h->marg_counts, klara_marg_count_elems(h->marg)));
+            HIPCHK(hipMemset(h->marg_counts, 0, klara_marg_count_elems(h->marg) * sizeof(unsigned long long)));
         }
         if (desc->monitor & KLARA_MON_HIST_LT) HIPCHK(mem.alloc(&h->hist_lt, (size_t)h->hist_cols * N));
         if (desc->monitor & KLARA_MON_HIST_LLLP) { HIPCHK(mem.alloc(&h->hist_ll, (size_t)h->hist_cols * N)); HIPCHK(mem.alloc(&h->hist_lp, (size_t)h->hist_cols * N)); }
@@ -373,7 +388,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     // the descriptor's host pointers are not retained
     h->d.mh_sigma = nullptr; h->d.slice_widths = nullptr; h->d.gauss_w = nullptr; h->d.gauss_mu = nullptr;
     h->d.gauss_prec = nullptr; h->d.logit_X = nullptr; h->d.logit_y = nullptr; h->d.hier_Y = nullptr; h->d.hier_xc = nullptr; h->d.stream = nullptr;
-    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr;
+    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
     {   // static kernel parameters live in device memory (read with scalar loads at the point of use)
         const KParams hp = make_params(h);
         HIPCHK(mem.alloc(&h->d_params, 1));

@@ -10,6 +10,7 @@
 #include <vector>
 #include "klara_plan.h"
 #include "klara_cov.h"
+#include "klara_marg.h"
 
 #define HIPCHK(expr)                                                                   \
     do {                                                                               \
@@ -65,6 +66,9 @@ struct klara_handle {
     int acov_W = 0; double *acov_S = nullptr, *acov_head = nullptr, *acov_tail = nullptr, *acov_total = nullptr, *acov_near = nullptr; long long acov_n = 0;
     // pooled covariance (KLARA_MON_COVARIANCE, klara_cov.h): the slabs' cross-products and sums, the pivot, the finalized mean | M; saved steps consumed
     KCovGeom cov = {}; double *cov_S = nullptr, *cov_T = nullptr, *cov_pivot = nullptr, *cov_out = nullptr; long long cov_n = 0;
+    // pooled marginal histograms (klara_desc.marg_nbins > 0, klara_marg.h): lo | hi | inv_w, the uint64 [D][nbins + 2] table; saved steps consumed
+    KMargGeom marg = {}; double* marg_par = nullptr; unsigned long long* marg_counts = nullptr; long long marg_n = 0;
+    std::vector<double> marg_host;  // lo | hi as given at create: what klara_gather_histogram compares between ranks
     double *hist_lt = nullptr, *hist_g = nullptr, *hist_ll = nullptr, *hist_lp = nullptr;
     unsigned long long* clock_probe = nullptr;        // pair-transposed kernels: (s_memtime, s_memrealtime) at the end / start of one workgroup of the last launch
     bool pair_enqueued = false;                       // a launch of this handle has enqueued both kernel families (their one-time scratch set-up is behind us)

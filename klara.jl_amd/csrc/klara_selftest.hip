@@ -449,6 +449,51 @@ extern "C" klara_status klara_selftest_covariance(int32_t device, int64_t nchain
     return KLARA_OK;
 }
 
+// The marginal histogram kernel (klara_marg.h) on a caller's value history: klara_marg_launch_update launch by launch with col0 running through the history,
+// as klara_run issues them (an empty launch skipped), then the table as klara_gather_histogram reads it.  Every argument check comes before any HIP call.
+extern "C" klara_status klara_selftest_marginals(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
+                                                 const int64_t* splits, int64_t nbins, const double* lo, const double* hi, uint64_t* counts)
+{
+    if (!hist || !splits || !lo || !hi || !counts || nchains <= 0 || ndims < 1 || ndims > 1024 || ncols < 1 || nsplits <= 0 || nbins < 1 ||
+        nbins > KLARA_MARG_MAX_BINS)
+        return KLARA_ERR_INVALID_ARG;
+    long long sum = 0;
+    for (int j = 0; j < nsplits; ++j) {
+        if (splits[j] < 0 || splits[j] > KLARA_MARG_MAX_COLS) return KLARA_ERR_INVALID_ARG;
+        sum += splits[j];
+    }
+    if (sum != ncols) return KLARA_ERR_INVALID_ARG;
+    for (int i = 0; i < ndims; ++i) if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i])) return KLARA_ERR_INVALID_ARG;
+    KMargGeom g;
+    if (!klara_marg_plan(nchains, ndims, nbins, &g)) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    const size_t D = (size_t)ndims, nd = (size_t)nchains * D, K = klara_marg_count_elems(g);
+    const hipStream_t st = 0;
+    std::vector<double> par(lo, lo + D);
+    par.insert(par.end(), hi, hi + D);
+    for (size_t i = 0; i < D; ++i) par.push_back(klara_marg_inv_w(nbins, lo[i], hi[i]));
+    DeviceArrays mem;
+    double *dh = nullptr, *dpar = nullptr; unsigned long long* dc = nullptr;
+    hipError_t e = mem.alloc(&dh, (size_t)ncols * nd);
+    if (e == hipSuccess) e = mem.alloc(&dpar, par.size());
+    if (e == hipSuccess) e = mem.alloc(&dc, K);
+    if (e == hipSuccess) e = hipMemcpy(dh, hist, (size_t)ncols * nd * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dpar, par.data(), par.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dc, 0, K * sizeof(unsigned long long));       // (what klara_set_state / klara_reset leave)
+    long long col0 = 0;
+    for (int j = 0; j < nsplits && e == hipSuccess; ++j) {
+        if (splits[j] > 0) e = klara_marg_launch_update(g, dh, col0, (long long)splits[j], dpar, dc, st);
+        col0 += splits[j];
+    }
+    std::vector<uint64_t> hc(K);
+    if (e == hipSuccess) e = hipMemcpyAsync(hc.data(), dc, K * sizeof(uint64_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const bool clean = mem.release();
+    if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
+    memcpy(counts, hc.data(), K * sizeof(uint64_t));
+    return KLARA_OK;
+}
+
 // The R-hat kernels (klara_rhat.h) on a caller's per-chain sums (unsplit) and / or a caller's value history (split), through the launch functions of the job
 // path: the chains [c0, c0 + Nr) staged into buf as klara_gather_rhat stages them (zeros | mean_r, Bsum_r, Wsum_r | the counters are the caller's)
 static hipError_t selftest_rhat_one(DeviceArrays& mem, const MergeLayout& L, bool split, const double* dsum, const double* dsumsq, const double* dX,

@@ -244,6 +244,25 @@ def allreduce_covariance(local: Dict[str, np.ndarray], group=None, device=None) 
     return out
 
 
+def allreduce_histogram(counts, group=None, device=None) -> np.ndarray:
+    """The pooled marginal histogram of every rank's chains for hosts with their own transport: `counts` is this rank's (D, nbins + 2) table
+    (Engine.pooled_histogram without a communicator; every rank built with the same marginals=).  One SUM all-reduce of 64-bit integers — exact in any
+    order, so the result is the unsharded table; gloo works.  Works without torch.distributed initialised (single process)."""
+    import torch
+    import torch.distributed as dist
+
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    if np.any(c >> np.uint64(63)):
+        raise ValueError("counts beyond 2^63 cannot travel as int64")
+    if not (dist.is_available() and dist.is_initialized()):
+        return c.copy()
+    if device is None:
+        device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+    t = torch.from_numpy(c.view(np.int64).copy()).to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64).reshape(c.shape)
+
+
 def gather_engine_rhat_klara(engine, comm: KlaraComm, split: bool = False) -> Dict[str, np.ndarray]:
     """R-hat over every rank's chains through the C ABI alone: klara_gather_rhat(h, comm, ...) — the ranks' (chains, mean of chain means, bsum) merged as
     the moments are and wsum summed, four RCCL all-reduces on the job's stream.  Keys as Engine.rhat."""

@@ -247,6 +247,40 @@ class HierNormalTarget:
         return th
 
 
+# ------------------------------------------------------------------ pooled marginal histograms
+class Marginals:
+    """Marginals(nbins, lo, hi): per dimension, `nbins` (1 .. 1024) equal bins over [lo, hi) plus an underflow and an overflow slot; lo and hi are scalars
+    (every dimension the same) or D values, finite, lo < hi.  Handed to Engine / BasicMCJob as marginals=: the saved samples of all chains are then
+    counted after every launch (Engine.pooled_histogram, K.pooled_hist, K.pooled_quantiles) — no stored history."""
+
+    def __init__(self, nbins: int, lo, hi):
+        self.nbins = int(nbins)
+        self.lo, self.hi = lo, hi
+
+    def bounds(self, ndims: int):
+        lo = _f64(np.broadcast_to(_f64(self.lo).ravel(), (ndims,)))
+        hi = _f64(np.broadcast_to(_f64(self.hi).ravel(), (ndims,)))
+        return lo, hi
+
+    def edges(self, ndims: int) -> np.ndarray:
+        lo, hi = self.bounds(ndims)
+        return lo[:, None] + np.arange(self.nbins + 1)[None, :] * ((hi - lo) / self.nbins)[:, None]
+
+
+def histogram_quantiles(counts, nbins: int, lo, hi, probs) -> np.ndarray:
+    """klara_histogram_quantiles: (D, len(probs)) quantiles from (D, nbins + 2) counts — the library's one statement of the rule (host code, no device)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    D = counts.shape[0]
+    if counts.ndim != 2 or counts.shape[1] != int(nbins) + 2:
+        raise ValueError(f"counts must be (D, nbins + 2), not {counts.shape}")
+    lo, hi = Marginals(nbins, lo, hi).bounds(D)
+    p = _f64(np.atleast_1d(probs).ravel())
+    out = np.empty((D, p.size))
+    L.check(L.load().klara_histogram_quantiles(counts.ctypes.data, D, int(nbins), lo.ctypes.data, hi.ctypes.data, p.size, p.ctypes.data, out.ctypes.data),
+            "klara_histogram_quantiles")
+    return out
+
+
 # ------------------------------------------------------------------ engine
 class Engine:
     def __init__(self, *, sampler: int, target, nchains: int, nsteps: int, burnin: int = 0, thinning: int = 1,
@@ -259,7 +293,7 @@ class Engine:
                  seed: int = 20260927, chain_offset: int = 0, device: int = 0, monitor: int = 0,
                  steps_per_launch: int = 0, stream: int = 0, nstreams: int = 0, bm_batchlen: int = 0, hist_ring_cols: int = 0,
                  acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0,
-                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0):
+                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None):
         self._lib = L.load()
         self.target = target
         self.ndims = int(target.ndims)
@@ -325,6 +359,13 @@ class Engine:
                 raise ValueError(f"ram_S0 must be {self.ndims} x {self.ndims} (or its diagonal), not {a.shape}")
             keep.append(a); d.ram_S0 = _ptr(a)
         d.ram_targetrate, d.ram_gamma = float(ram_targetrate), float(ram_gamma)
+        # pooled marginal histograms (klara_desc.marg_lo / marg_hi / marg_nbins): a Marginals, or (nbins, lo, hi)
+        self.marginals = None
+        if marginals is not None:
+            m = marginals if isinstance(marginals, Marginals) else Marginals(*marginals)
+            lo, hi = m.bounds(self.ndims)
+            keep.extend((lo, hi)); d.marg_lo, d.marg_hi, d.marg_nbins = _ptr(lo), _ptr(hi), m.nbins
+            self.marginals = Marginals(m.nbins, lo.copy(), hi.copy())
         d.stream = C.c_void_p(int(stream)) if stream else None
         self._h = C.c_void_p()
         L.check(self._lib.klara_create(C.byref(d), C.byref(self._h)), "klara_create")
@@ -432,6 +473,18 @@ class Engine:
         ns, nc = C.c_uint64(0), C.c_uint64(0)
         L.check(self._lib.klara_gather_covariance(self._h, comm, mean.ctypes.data, m2.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_covariance")
         return mean, m2, int(ns.value), int(nc.value)
+
+    def pooled_histogram(self, comm=None):
+        """(counts[D, nbins + 2] uint64, edges[D, nbins + 1], nsamples, nchains) over this handle's chains — or, with a klara_comm handle, over every
+        rank's: the saved samples of every dimension counted into the job's `marginals` bins, columns 0 and nbins + 1 the underflow and the overflow
+        (klara_gather_histogram).  edges[d, k] = lo[d] + k (hi[d] - lo[d]) / nbins is documentation: the index formula is the contract."""
+        if self.marginals is None:
+            raise ValueError("the job was built without marginals=")
+        m = self.marginals
+        counts = np.zeros((self.ndims, m.nbins + 2), dtype=np.uint64)
+        ns, nc = C.c_uint64(0), C.c_uint64(0)
+        L.check(self._lib.klara_gather_histogram(self._h, comm, counts.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_histogram")
+        return counts, m.edges(self.ndims), int(ns.value), int(nc.value)
 
     def rhat(self, split: bool = False, comm=None):
         """The Gelman–Rubin diagnostic over this handle's chains — or, with a klara_comm handle, over every rank's (klara_gather_rhat): dict of rhat[D],

@@ -82,6 +82,68 @@ def pooled_cov(values) -> np.ndarray:
     return (xc @ xc.T) / (x.shape[1] - 1)
 
 
+def hist_slots(x, nbins: int, lo, hi) -> np.ndarray:
+    """The slot of every value of x (..., D) among the nbins + 2 of its dimension — the index formula of klara_gather_histogram, operation for operation:
+    inv_w = nbins / (hi - lo); 0 if x < lo; nbins + 1 if not x < hi (x >= hi, +inf, NaN); else 1 + min(nbins - 1, floor((x - lo) * inv_w)) — a subtraction
+    followed by a multiplication, nothing that could fuse."""
+    x = np.asarray(x, dtype=np.float64)
+    D = x.shape[-1]
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float64).ravel(), (D,)); hi = np.broadcast_to(np.asarray(hi, dtype=np.float64).ravel(), (D,))
+    inv_w = float(nbins) / (hi - lo)
+    with np.errstate(all="ignore"):
+        f = np.floor((x - lo) * inv_w)
+        inner = 1 + np.fmin(float(nbins - 1), f)                 # (the minimum in double before the conversion, as the device takes it)
+    under, over = x < lo, ~(x < hi)
+    inner = np.where(under | over, 0.0, inner)                   # (the outer slots are decided first, as on the device: nothing of those values is converted)
+    slot = np.where(under, 0, np.where(over, nbins + 1, inner.astype(np.int64)))
+    return slot.astype(np.int64)
+
+
+def pooled_hist(values, nbins: int, lo, hi) -> np.ndarray:
+    """counts (D, nbins + 2) uint64 of `values` (..., D) — any leading axes: saved steps, chains — per dimension over everything else: the literal NumPy
+    form of what a job with marginals= counts on the device (klara_gather_histogram).  Column 0 is the underflow, column nbins + 1 the overflow."""
+    x = np.asarray(values, dtype=np.float64)
+    D = x.shape[-1]
+    slot = hist_slots(x, nbins, lo, hi).reshape(-1, D)
+    counts = np.zeros((D, nbins + 2), dtype=np.uint64)
+    for d in range(D):
+        counts[d] = np.bincount(slot[:, d], minlength=nbins + 2).astype(np.uint64)
+    return counts
+
+
+def hist_quantiles(counts, nbins: int, lo, hi, probs) -> np.ndarray:
+    """(D, len(probs)) quantiles from (D, nbins + 2) counts — klara_histogram_quantiles restated operation for operation: n = the row's total,
+    w = (hi - lo) / nbins, k = max(1, ceil(p n)), b = the first slot whose cumulative count reaches k; slot 0: -inf, slot nbins + 1: +inf, otherwise
+    (lo + (b - 1) w) + w (k - cum_before) / count_b; NaN for n = 0."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    D = counts.shape[0]
+    lo = np.broadcast_to(np.asarray(lo, dtype=np.float64).ravel(), (D,)); hi = np.broadcast_to(np.asarray(hi, dtype=np.float64).ravel(), (D,))
+    probs = np.atleast_1d(np.asarray(probs, dtype=np.float64)).ravel()
+    if np.any(~((probs > 0.0) & (probs <= 1.0))):
+        raise ValueError("probabilities must lie in (0, 1]")
+    out = np.empty((D, probs.size))
+    for d in range(D):
+        c = [int(v) for v in counts[d]]
+        n = sum(c)
+        w = np.float64(hi[d] - lo[d]) / np.float64(nbins)
+        for j, p in enumerate(probs):
+            if n == 0:
+                out[d, j] = np.nan
+                continue
+            k = min(max(1, int(np.ceil(np.float64(p) * np.float64(n)))), n)
+            cum, b = 0, 0
+            while cum + c[b] < k:
+                cum += c[b]; b += 1
+            if b == 0:
+                out[d, j] = -np.inf
+            elif b == nbins + 1:
+                out[d, j] = np.inf
+            else:
+                left = np.float64(lo[d]) + np.float64(b - 1) * w
+                out[d, j] = left + w * np.float64(k - cum) / np.float64(c[b])
+    return out
+
+
 def rhat(values, split: bool = False) -> np.ndarray:
     """The Gelman–Rubin potential scale reduction factor per dimension: `values` is (m chains, n samples, D).  With W the mean of the chains' sample
     variances and B / n the sample variance of the chain means, R-hat = sqrt(((n - 1) / n W + B / n) / W) (Gelman & Rubin 1992).  split=True cuts every
