@@ -67,7 +67,7 @@ typedef enum klara_status {
     KLARA_ERR_COMPILE = 8          /* CUSTOM target: the user's source did not compile (klara_compile_log) */
 } klara_status;
 
-/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM}.jl */
+/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM,AM}.jl */
 typedef enum klara_sampler {
     KLARA_SAMPLER_MH = 0,      /* MH(sigma): symmetric normal random walk, MH.jl:63-66            */
     KLARA_SAMPLER_MALA = 1,    /* MALA(driftstep), MALA.jl:61-70                                   */
@@ -91,7 +91,21 @@ typedef enum klara_sampler {
      * more lanes per chain and D >= 9 are KLARA_ERR_UNSUPPORTED.  Only KLARA_TUNER_VANILLA (verbose or not: it counts as for MH);
      * another tuner is KLARA_ERR_UNSUPPORTED.  S lives on the device per chain (klara_get_ram_factor / klara_set_ram_factor);
      * klara_set_state and klara_reset put S = klara_desc.ram_S0 and restart the count.  DESIGN.md section 2, R1-R4. */
-    KLARA_SAMPLER_RAM = 6
+    KLARA_SAMPLER_RAM = 6,
+    /* (7 is reserved like 5: klara_create and klara_check_custom_target refuse it with KLARA_ERR_INVALID_ARG) */
+    /* AM(C0; corescale, minorscale, c, t0), AM.jl:131-154, iterate/AM.jl:77-152 (Haario, Saksman and Tamminen 2001 with the mixture proposal of
+     * Roberts and Rosenthal 2009): every chain keeps the running mean of its states and a covariance C that starts at C0.  Up to transition t0
+     * it proposes x' = x + sqrt(minorscale) z.  From transition t0 + 1 on (count = t + 1 > t0) it first brings C up to date from its state and the
+     * last two running means (stats/covariance.jl:6-19, k = count - 2), then proposes from the mixture of N(x, corescale C), weight 1 - c, and
+     * N(x, minorscale I), weight c.  Draws what MH draws (D normals and one accept uniform per transition); the component is chosen by a uniform
+     * from the two unused words of the accept block, so the stream does not move.  Needs no gradient.  Scope and tuners as for
+     * KLARA_SAMPLER_RAM: KLARA_TARGET_LOGISTIC with D <= 8 (layout kinds 0 and 2), KLARA_TARGET_CUSTOM whole-vector closures (plain or
+     * likelihood + prior form) with D <= 8 at one chain per lane, KLARA_TUNER_VANILLA per chain; everything else is KLARA_ERR_UNSUPPORTED.
+     * am_t0 = 1 is KLARA_ERR_UNSUPPORTED too: it makes k = 0 at the first update and divides by zero.  The proposal log-densities of
+     * iterate/AM.jl:102-106 cancel and are not formed; where corescale C does not factor the chain proposes from the minor component and the
+     * handle counts it (klara_get_am_state).  klara_set_state and klara_reset put C = am_C0, both means = the start value and restart the
+     * count.  DESIGN.md section 2, A1-A5. */
+    KLARA_SAMPLER_AM = 8
 } klara_sampler;
 
 /* Target families evaluated on device (stand-ins for the user closures of
@@ -287,6 +301,13 @@ typedef struct klara_desc {
                                     KLARA_TARGET_LOGISTIC with a > 0 is KLARA_ERR_UNSUPPORTED: its metric X' diag(r (1 - r)) X + I / lambda is positive
                                     definite by construction and has no use for the transform.  Negative or non-finite, or a > 0 with another sampler:
                                     KLARA_ERR_INVALID_ARG. */
+    const double* am_C0;         /* AM: the initial covariance, D x D row-major, symmetric; the upper triangle is read and must be finite (AM.jl:132).
+                                    Required for KLARA_SAMPLER_AM; NULL for every other sampler (else KLARA_ERR_INVALID_ARG) */
+    double   am_corescale;       /* AM: scaling of C in the core mixture component, > 0 (AM.jl:139); 0 for every other sampler */
+    double   am_minorscale;      /* AM: variance of the stabilising component N(x, minorscale I), > 0 (AM.jl:140); 0 for every other sampler */
+    double   am_c;               /* AM: weight of the stabilising component, in [0, 1) (AM.jl:141; 1 - c > 0, AM.jl:107-109); 0 for every other sampler */
+    int64_t  am_t0;              /* AM: transitions before the adaptation starts, >= 2 (AM.jl:142; 1 is KLARA_ERR_UNSUPPORTED: k = count - 2 = 0 divides
+                                    by zero at the first update, stats/covariance.jl:18); 0 for every other sampler */
     const double* ram_S0;        /* RAM: the initial factor, D x D row-major; the lower triangle is read and its diagonal must be > 0
                                     (RAM.jl:100).  Required for KLARA_SAMPLER_RAM; NULL for every other sampler (else KLARA_ERR_INVALID_ARG) */
     double   ram_targetrate;     /* RAM: target acceptance rate, in (0, 1) (RAM.jl:101); 0 for every other sampler */
@@ -519,6 +540,11 @@ klara_status klara_get_ram_factor(klara_handle* h, double* S, int64_t* skipped);
 /* KLARA_SAMPLER_RAM: per-chain factors for a warm start (nchains x D x D row-major, the lower triangles are read); the transition
  * count is kept.  A diagonal entry that is not a finite positive number: KLARA_ERR_INVALID_ARG; before klara_set_state: KLARA_ERR_STATE. */
 klara_status klara_set_ram_factor(klara_handle* h, const double* S);
+/* KLARA_SAMPLER_AM: the chains' current covariances C (nchains x D x D row-major, full symmetric), running means lastmean and secondlastmean
+ * (nchains x D each), and the number of transitions since klara_set_state / klara_reset at which corescale C did not factor and the chain
+ * proposed from the minor component instead.  Any pointer may be NULL.  KLARA_ERR_INVALID_ARG on a handle of
+ * another sampler. */
+klara_status klara_get_am_state(klara_handle* h, double* C, double* lastmean, double* secondlastmean, int64_t* fallbacks);
 
 /* Measurement: duration (ms, HIP events on the launch stream) and launch count of the transition
  * kernels enqueued by the last klara_run / klara_run_async (after synchronisation). */

@@ -29,7 +29,7 @@
 # `finalizer(f, obj)`): the three differences are confined to the compatibility block below, everything else is common syntax.
 module KlaraHIP
 import Klara
-import Klara: output, MCJob, MH, MALA, SMMALA, RAM, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
+import Klara: output, MCJob, MH, MALA, SMMALA, RAM, AM, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
               BasicContMuvParameterState, BasicContMuvParameterNState, erf_rate_score, logistic_rate_score,
               Parameter, GenericModel, VariableState, VariableStateVector, DiffOptions
 import Distributions
@@ -37,7 +37,7 @@ import Distributions: Continuous, Multivariate
 import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
-       check_custom_target_softabs, SoftAbs, ramfactor,
+       check_custom_target_softabs, SoftAbs, ramfactor, amstate,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat,
        pooledhistogram, pooledquantiles, gather_histogram, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
@@ -57,6 +57,7 @@ const KLARA_ABI_VERSION = UInt32(6)
 const SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE = Int32(0), Int32(1), Int32(2), Int32(3)
 const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothing or SoftAbs(a); the logistic target or a CustomTarget's tensor, D <= 8
 const SAMPLER_RAM = Int32(6)         # RAM(S0; targetrate, γ): the logistic target or a CustomTarget's whole-vector closure, D <= 8 (5 is reserved)
+const SAMPLER_AM = Int32(8)          # AM(C0; corescale, minorscale, c, t0): RAM's targets, D <= 8 (7 is reserved)
 const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
@@ -82,6 +83,7 @@ struct KlaraDesc
     custom_src::Cstring; custom_data::Ptr{Float64}; custom_ndata::Int64; bm_batchlen::Int64
     hist_ring_cols::Int64; acov_maxlag::Int32; sparse_moves::Int32
     smmala_softabs::Float64
+    am_C0::Ptr{Float64}; am_corescale::Float64; am_minorscale::Float64; am_c::Float64; am_t0::Int64
     ram_S0::Ptr{Float64}; ram_targetrate::Float64; ram_gamma::Float64
     marg_lo::Ptr{Float64}; marg_hi::Ptr{Float64}; marg_nbins::Int64
     seed::UInt64; monitor::UInt32; steps_per_launch::Int32; stream::Ptr{Cvoid}
@@ -101,6 +103,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
                     hier_prior_prec=1e-4, hier_gamma_a=1e-3, hier_gamma_b=1e-3,
                     custom_src=Cstring(C_NULL), custom_data=Ptr{Float64}(C_NULL), custom_ndata=0, bm_batchlen=0,
                     hist_ring_cols=0, acov_maxlag=0, sparse_moves=0, smmala_softabs=0.0,
+                    am_C0=Ptr{Float64}(C_NULL), am_corescale=0.0, am_minorscale=0.0, am_c=0.0, am_t0=0,
                     ram_S0=Ptr{Float64}(C_NULL), ram_targetrate=0.0, ram_gamma=0.0,
                     marg_lo=Ptr{Float64}(C_NULL), marg_hi=Ptr{Float64}(C_NULL), marg_nbins=0,
                     seed=UInt64(0), monitor=UInt32(0), steps_per_launch=0, stream=C_NULL)
@@ -119,6 +122,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               hier_prior_prec, hier_gamma_a, hier_gamma_b,
               custom_src, custom_data, custom_ndata, bm_batchlen,
               hist_ring_cols, acov_maxlag, sparse_moves, smmala_softabs,
+              am_C0, am_corescale, am_minorscale, am_c, am_t0,
               ram_S0, ram_targetrate, ram_gamma,
               marg_lo, marg_hi, marg_nbins,
               seed, monitor, steps_per_launch, stream)
@@ -204,6 +208,7 @@ rowmajor(A::Matrix{Float64}) = collect(transpose(A))       # Julia is column-maj
 #   MALA.driftstep                         samplers/MALA.jl:61-70
 #   SMMALA.driftstep, .transform (nothing or SoftAbs(a)) samplers/SMMALA.jl:127-137
 #   RAM.S0, .targetrate, .γ                samplers/RAM.jl:94-111
+#   AM.C0, .corescale, .minorscale, .c, .t0 samplers/AM.jl:131-136
 #   HMC.leapstep, HMC.nleaps               samplers/HMC.jl:89-100
 #   SliceSampler.widths, .stepout          samplers/SliceSampler.jl:22-34
 #   MH.setproposal (sigma is inside the closure: MH(sigma) = MH(x -> MvNormal(x, sigma)))   samplers/MH.jl:46-66
@@ -261,6 +266,12 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         size(S0) == (D, D) || error("RAM: S0 must be D x D")
         kw[:sampler] = SAMPLER_RAM; kw[:ram_S0] = pointer(S0)
         kw[:ram_targetrate] = Float64(sampler.targetrate); kw[:ram_gamma] = Float64(sampler.γ)
+    elseif isa(sampler, AM)                                 # samplers/AM.jl:131-136: the initial covariance (symmetric), the two scalings, the weight and t0
+        C0 = rowmajor(convert(Matrix{Float64}, sampler.C0)); push!(keep, C0)
+        size(C0) == (D, D) || error("AM: C0 must be D x D")
+        kw[:sampler] = SAMPLER_AM; kw[:am_C0] = pointer(C0)
+        kw[:am_corescale] = Float64(sampler.corescale); kw[:am_minorscale] = Float64(sampler.minorscale)
+        kw[:am_c] = Float64(sampler.c); kw[:am_t0] = Int64(sampler.t0)
     elseif isa(sampler, MALA)
         kw[:sampler] = SAMPLER_MALA; kw[:driftstep] = Float64(sampler.driftstep)
     elseif isa(sampler, HMC)
@@ -275,7 +286,7 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         sig = sqrt.(Distributions.var(prop)); push!(keep, sig)
         kw[:sampler] = SAMPLER_MH; kw[:mh_sigma] = pointer(sig)
     else
-        error("sampler $(typeof(sampler)) is not on the device path (MH, RAM, MALA, SMMALA, HMC, SliceSampler are)")
+        error("sampler $(typeof(sampler)) is not on the device path (MH, RAM, AM, MALA, SMMALA, HMC, SliceSampler are)")
     end
     # --- tuner
     tn = tuner === nothing ? VanillaMCTuner() : tuner
@@ -396,6 +407,19 @@ function show(io::IO, job::HIPMCJob)                     # BasicMCJob.jl:281-295
     print(io, "\n  "); show(io, job.sampler)
     print(io, "\n  "); show(io, job.tuner)
     print(io, "\n  "); show(io, job.range)
+end
+
+# amstate(job): (C, lastmean, secondlastmean, fallbacks) of an AM job — C[:, :, c] is chain c's current covariance (sstate.C of iterate/AM.jl:87-91),
+# lastmean[:, c] and secondlastmean[:, c] its running means (:134-135), fallbacks the number of transitions at which corescale * C did not factor and the
+# chain proposed from the stabilising component instead
+function amstate(job::HIPMCJob)
+    Cm = newarray(Float64, job.ndims, job.ndims, job.nchains)       # symmetric: row-major == column-major
+    m = newarray(Float64, job.ndims, job.nchains)
+    m2 = newarray(Float64, job.ndims, job.nchains)
+    fallbacks = Ref{Clonglong}(0)
+    check(ccall((:klara_get_am_state, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Clonglong}), job.handle, Cm, m, m2, fallbacks),
+          "klara_get_am_state")
+    (Cm, m, m2, Int(fallbacks[]))
 end
 
 # value matrix of chain c exactly as BasicContMuvParameterNState.value (D x npoststeps)

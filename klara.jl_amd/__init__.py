@@ -7,7 +7,7 @@ from . import _lib  # noqa: F401
 from ._lib import KlaraError  # noqa: F401
 from .engine import CustomTarget, Engine, GaussDenseTarget, GaussDiagTarget, HierNormalTarget, LogisticTarget, Marginals, histogram_quantiles  # noqa: F401
 from .api import (  # noqa: F401
-    HMC, MALA, MH, RAM, SMMALA, SoftAbs, AcceptanceRateMCTuner, DualAveragingMCTuner, DiffOptions, BasicContMuvParameter, BasicMCJob, BasicMCRange, GenericModel,
+    AM, HMC, MALA, MH, RAM, SMMALA, SoftAbs, AcceptanceRateMCTuner, DualAveragingMCTuner, DiffOptions, BasicContMuvParameter, BasicMCJob, BasicMCRange, GenericModel,
     MuvChains, SliceSampler, VanillaMCTuner, acceptance, chain_ess, chain_iact, chain_mcvar, erf_rate_score, likelihood_model, logistic, logistic_rate_score,
     mcvar_iid, mean, output, reset, run, chain_lzv, chain_qzv, lzv, qzv, pooled_cov, pooled_cor, rhat, pooled_hist, pooled_quantiles,
 )

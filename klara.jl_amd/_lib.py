@@ -23,6 +23,7 @@ OK, ERR_INVALID_ARG, ERR_NONFINITE_INIT, ERR_HIP, ERR_NOMEM, ERR_UNSUPPORTED, ER
 # klara_sampler
 SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE, SAMPLER_SMMALA = range(5)
 SAMPLER_RAM = 6                   # (5 is reserved: the library refuses it)
+SAMPLER_AM = 8                    # (7 is reserved too)
 # klara_target
 TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = range(5)
 # klara_tuner / mode
@@ -59,6 +60,7 @@ class KlaraDesc(C.Structure):
         ("custom_src", C.c_char_p), ("custom_data", _dp), ("custom_ndata", C.c_int64), ("bm_batchlen", C.c_int64),
         ("hist_ring_cols", C.c_int64), ("acov_maxlag", C.c_int32), ("sparse_moves", C.c_int32),
         ("smmala_softabs", C.c_double),
+        ("am_C0", _dp), ("am_corescale", C.c_double), ("am_minorscale", C.c_double), ("am_c", C.c_double), ("am_t0", C.c_int64),
         ("ram_S0", _dp), ("ram_targetrate", C.c_double), ("ram_gamma", C.c_double),
         ("marg_lo", _dp), ("marg_hi", _dp), ("marg_nbins", C.c_int64),
         ("seed", C.c_uint64), ("monitor", C.c_uint32), ("steps_per_launch", C.c_int32),
@@ -84,7 +86,7 @@ EXPORTS = [
     "klara_create", "klara_destroy", "klara_set_state", "klara_init_state_normal", "klara_run",
     "klara_run_async", "klara_synchronize", "klara_reset", "klara_stream_key", "klara_get_state", "klara_get_accept_mask", "klara_get_accept_rows",
     "klara_get_accept_counts", "klara_get_chain_sums", "klara_get_pooled_summaries", "klara_get_chain",
-    "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_get_ram_factor", "klara_set_ram_factor", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
+    "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_get_ram_factor", "klara_set_ram_factor", "klara_get_am_state", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
     "klara_selftest_rocrand_blocks", "klara_selftest_math", "klara_selftest_normal_tail", "klara_selftest_transition_normals", "klara_selftest_mfma_f64", "klara_selftest_mfma_f64_4x4x4", "klara_selftest_chain_stats", "klara_selftest_pooled", "klara_strerror",
     "klara_comm_unique_id", "klara_comm_init", "klara_comm_info", "klara_comm_destroy", "klara_gather_summaries", "klara_gather_moments", "klara_gather_covariance", "klara_selftest_covariance",
     "klara_gather_rhat", "klara_selftest_rhat",
@@ -132,6 +134,7 @@ def load() -> C.CDLL:
         "klara_get_dual_averaging": [H, C.c_void_p, C.c_void_p],
         "klara_get_ram_factor": [H, C.c_void_p, i64p],
         "klara_set_ram_factor": [H, C.c_void_p],
+        "klara_get_am_state": [H, C.c_void_p, C.c_void_p, C.c_void_p, i64p],
         "klara_last_run_ms": [H, C.POINTER(C.c_double), i64p],
         "klara_device_ptrs": [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
         "klara_get_layout": [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],

@@ -127,6 +127,29 @@ class RAM(MCSampler):
         self.S0, self.targetrate, self.gamma = a.copy(), float(targetrate), float(gamma)
 
 
+class AM(MCSampler):
+    """AM(C0::Matrix) / AM(C0::Vector) / AM(C0::Real, d=1), keywords corescale=1., minorscale=1., c=0.05, t0=10 — AM.jl:131-154: the adaptive
+    Metropolis sampler of Haario, Saksman and Tamminen (2001) with the mixture proposal of Roberts and Rosenthal (2009).  C0 is the initial
+    covariance (a vector: its diagonal; a number: that number d times).  Up to transition t0 a chain proposes from N(x, minorscale I); after it,
+    from the mixture of N(x, corescale C), weight 1 - c, and N(x, minorscale I), weight c, with C the covariance of its own states so far.  On the
+    device for D <= 8, on RAM's targets; t0 = 1 and c >= 1 are refused by the library (BasicMCJob.engine.am_state())."""
+    kind = L.SAMPLER_AM
+
+    def __init__(self, C0, d: int = 1, *, corescale: float = 1.0, minorscale: float = 1.0, c: float = 0.05, t0: int = 10):
+        a = np.asarray(C0, dtype=np.float64)
+        if a.ndim == 0:
+            a = np.full(int(d), float(a))                        # AM(C0::Real, d::Integer=1) = AM(fill(C0, d))
+        if a.ndim == 1:
+            a = np.diag(a)                                       # AM(C0::RealVector) = AM(diagm(C0))
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("AM: C0 must be a square matrix, a vector (its diagonal) or a number")
+        assert 0 < corescale, f"Constant corescale must be positive, got {corescale}"
+        assert 0 < minorscale, f"Constant minorscale must be positive, got {minorscale}"
+        assert 0 <= c, "Constant c must be non-negative"
+        assert t0 > 0, "t0 is not positive"
+        self.C0, self.corescale, self.minorscale, self.c, self.t0 = a.copy(), float(corescale), float(minorscale), float(c), int(t0)
+
+
 class HMC(MCSampler):
     """HMC(leapstep=0.1, nleaps=10) — HMC.jl:89-100."""
     kind = L.SAMPLER_HMC
@@ -628,6 +651,11 @@ class BasicMCJob:
             if not isinstance(self.tuner, VanillaMCTuner):
                 raise NotImplementedError("RAM adapts by itself: only VanillaMCTuner (which counts proposals when verbose) is accepted")
             kw["ram_S0"], kw["ram_targetrate"], kw["ram_gamma"] = sampler.S0, sampler.targetrate, sampler.gamma
+        elif isinstance(sampler, AM):                                                  # AM.jl:131-154; the tuner only counts (iterate/AM.jl:80-82)
+            if not isinstance(self.tuner, VanillaMCTuner):
+                raise NotImplementedError("AM adapts by itself: only VanillaMCTuner (which counts proposals when verbose) is accepted")
+            kw["am_C0"], kw["am_corescale"], kw["am_minorscale"] = sampler.C0, sampler.corescale, sampler.minorscale
+            kw["am_c"], kw["am_t0"] = sampler.c, sampler.t0
         elif isinstance(sampler, HMC):
             kw["leapstep"], kw["nleaps"] = sampler.leapstep, sampler.nleaps
         elif isinstance(sampler, SliceSampler):

@@ -49,6 +49,18 @@ static klara_status validate_fields(const klara_desc* d)
         // the tuner only counts proposals (iterate/RAM.jl:68-69, 107-121): VanillaMCTuner, per chain
         if (d->tuner != KLARA_TUNER_VANILLA || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
         break;
+    case KLARA_SAMPLER_AM:                                       // AM.jl:138-143, AM.jl:107-109 (w[1] = 1 - c > 0)
+        if (!d->am_C0) return KLARA_ERR_INVALID_ARG;
+        if (d->ndims <= 8) {                                     // (beyond: KLARA_ERR_UNSUPPORTED from the planner, whatever the matrix)
+            for (int i = 0; i < d->ndims; ++i)
+                for (int j = i; j < d->ndims; ++j) if (!std::isfinite(d->am_C0[i * d->ndims + j])) return KLARA_ERR_INVALID_ARG;
+        }
+        if (!(d->am_corescale > 0.0) || !std::isfinite(d->am_corescale) || !(d->am_minorscale > 0.0) || !std::isfinite(d->am_minorscale)) return KLARA_ERR_INVALID_ARG;
+        if (!(d->am_c >= 0.0 && d->am_c < 1.0) || d->am_t0 <= 0) return KLARA_ERR_INVALID_ARG;
+        if (d->am_t0 == 1) return KLARA_ERR_UNSUPPORTED;         // k = count - 2 = 0 at the first update: a division by zero
+        // the tuner only counts proposals (iterate/AM.jl:80-82, 123-125, 137-151): VanillaMCTuner, per chain
+        if (d->tuner != KLARA_TUNER_VANILLA || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
+        break;
     default:                                                     // SliceSampler.jl:27
         if (!d->slice_widths) return KLARA_ERR_INVALID_ARG;
         for (int i = 0; i < d->ndims; ++i) if (!(d->slice_widths[i] > 0.0)) return KLARA_ERR_INVALID_ARG;
@@ -73,6 +85,8 @@ static klara_status validate_fields(const klara_desc* d)
     if (d->smmala_softabs > 0.0 && d->sampler != KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
     if (d->smmala_softabs > 0.0 && d->target != KLARA_TARGET_CUSTOM) return KLARA_ERR_UNSUPPORTED;
     if (d->sampler != KLARA_SAMPLER_RAM && (d->ram_S0 != nullptr || d->ram_targetrate != 0.0 || d->ram_gamma != 0.0)) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler != KLARA_SAMPLER_AM && (d->am_C0 != nullptr || d->am_corescale != 0.0 || d->am_minorscale != 0.0 || d->am_c != 0.0 || d->am_t0 != 0))
+        return KLARA_ERR_INVALID_ARG;
     // pooled marginal histograms: 0 = off and no pointers; 1 .. KLARA_MARG_MAX_BINS with finite lo[d] < hi[d]
     if (d->marg_nbins < 0 || d->marg_nbins > KLARA_MARG_MAX_BINS) return KLARA_ERR_INVALID_ARG;
     if (d->marg_nbins == 0 ? (d->marg_lo != nullptr || d->marg_hi != nullptr) : (!d->marg_lo || !d->marg_hi)) return KLARA_ERR_INVALID_ARG;
@@ -352,6 +366,12 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
         KCHK(upload(mem, &h->ram_S0, tri.data(), tri.size()));
         HIPCHK(mem.alloc(&h->ram_S, tri.size() * N)); HIPCHK(mem.alloc(&h->ram_skipped, 1));
     }
+    if (desc->sampler == KLARA_SAMPLER_AM) {                     // the packed upper triangle of C0 (C_ij, i <= j, at ktri(i, j, D)); the means' 2 D planes
+        std::vector<double> tri(D * (D + 1) / 2);
+        for (size_t i = 0; i < D; ++i) for (size_t j = i; j < D; ++j) tri[(size_t)ktri((int)i, (int)j, (int)D)] = desc->am_C0[i * D + j];
+        KCHK(upload(mem, &h->am_C0, tri.data(), tri.size()));
+        HIPCHK(mem.alloc(&h->am_C, tri.size() * N)); HIPCHK(mem.alloc(&h->am_mean, 2 * D * N)); HIPCHK(mem.alloc(&h->am_fallbacks, 1));
+    }
     if (desc->target == KLARA_TARGET_GAUSS_DIAG) {
         if (desc->gauss_w) KCHK(upload(mem, &h->gw, desc->gauss_w, D));
         if (desc->gauss_mu) KCHK(upload(mem, &h->gmu, desc->gauss_mu, D));
@@ -388,7 +408,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     // the descriptor's host pointers are not retained
     h->d.mh_sigma = nullptr; h->d.slice_widths = nullptr; h->d.gauss_w = nullptr; h->d.gauss_mu = nullptr;
     h->d.gauss_prec = nullptr; h->d.logit_X = nullptr; h->d.logit_y = nullptr; h->d.hier_Y = nullptr; h->d.hier_xc = nullptr; h->d.stream = nullptr;
-    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
+    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.am_C0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
     {   // static kernel parameters live in device memory (read with scalar loads at the point of use)
         const KParams hp = make_params(h);
         HIPCHK(mem.alloc(&h->d_params, 1));
@@ -482,6 +502,8 @@ KParams make_params(klara_handle* h)
     p.clock_probe = (decltype(p.clock_probe))h->clock_probe;
     p.smmala_softabs = d.smmala_softabs;
     p.ram_S = (decltype(p.ram_S))h->ram_S; p.ram_skipped = (decltype(p.ram_skipped))h->ram_skipped; p.ram_targetrate = d.ram_targetrate; p.ram_gamma = d.ram_gamma;
+    p.am_C = (decltype(p.am_C))h->am_C; p.am_mean = (decltype(p.am_mean))h->am_mean; p.am_fallbacks = (decltype(p.am_fallbacks))h->am_fallbacks;
+    p.am_corescale = d.am_corescale; p.am_sqrtminor = std::sqrt(d.am_minorscale); p.am_w1 = 1.0 - d.am_c; p.am_t0 = d.am_t0;     // AM.jl:235-236: sqrtminorscale, w = [1 - c, c]
     return p;
 }
 

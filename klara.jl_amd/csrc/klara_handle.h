@@ -81,6 +81,9 @@ struct klara_handle {
     double* cdata = nullptr; KlaraJit* jit = nullptr;   // user-defined target: data block, run-time compiled kernels
     // RAM: the chains' factors (D (D + 1) / 2 planes of nchains doubles, KParams::ram_S), the packed lower triangle of klara_desc.ram_S0 they restart from, the skipped-update counter
     double *ram_S = nullptr, *ram_S0 = nullptr; unsigned long long* ram_skipped = nullptr;
+    // AM: the chains' covariances (D (D + 1) / 2 planes, KParams::am_C), their running means (2 D planes, KParams::am_mean), the packed upper triangle of
+    // klara_desc.am_C0 they restart from, the counter of transitions that fell back to the minor component
+    double *am_C = nullptr, *am_C0 = nullptr, *am_mean = nullptr; unsigned long long* am_fallbacks = nullptr;
     // streaming batch means (bm_batchlen > 0): running sum at the last batch boundary, Welford mean / M2 of the batch means
     double *bm_prev = nullptr, *bm_mean = nullptr, *bm_m2 = nullptr; long long bm_count = 0;
     KParams* d_params = nullptr;    // device copy of the handle's static kernel parameters

@@ -235,7 +235,8 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
             }
         }
     }
-    // (MH, the slice sampler and RAM evaluate no gradient: k_transitions<KLARA_SAMPLER_RAM, ...> and k_init are instantiated by the names below like MH's)
+    // (MH, the slice sampler, RAM and AM evaluate no gradient: k_transitions<KLARA_SAMPLER_RAM, ...>, k_transitions<KLARA_SAMPLER_AM, ...> and k_init are instantiated
+    //  by the names below like MH's)
     const bool needgrad = sampler_needs_gradient(sampler);
     // SMMALA: the metric is the user's klara_user_tensorlogtarget (klara_custom.h); a source without it cannot run the sampler
     // forward-mode autodiff (klara_autodiff.h): the marker's value; the generic function it promises has to be there

@@ -88,6 +88,12 @@ __host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { re
 #define KLARA_SLICE_MAX_ATT ((1 << KLARA_SLICE_ATT_BITS) - 1)
 #define KLARA_INIT_TRANSITION ((((uint64_t)1) << 40) - 1)
 
+// AM kernels, wavefronts per SIMD asked of the compiler (the covariance's triangle is live through the target's row loop, as RAM's factor is; the second
+// triangle — the factor of corescale C — only until the proposal is formed; the compiler's resource table is in DESIGN.md section 2)
+#ifndef KLARA_AM_WAVES
+#define KLARA_AM_WAVES(E, MODE) ((E) == 8 ? 1 : 2)
+#endif
+
 // Device pointers inside KParams are typed as address space 1 (global) in device compilation: the struct is read
 // from memory, and without the qualifier hipcc treats the loaded pointers as generic and emits flat_load/flat_store
 // (vmcnt + lgkmcnt, 64-bit VGPR addresses) instead of global_load v, v_off32, s[base:base+1].  Host code sees plain
@@ -153,6 +159,10 @@ struct KParams {
     // RAM: the chains' factors, D (D + 1) / 2 planes of nchains doubles (entry S_ij, i >= j, of chain c at [ktri(j, i, D) * nchains + c]: a wavefront's
     // loads and stores of one entry are contiguous); the handle's counter of skipped updates; RAM.targetrate, RAM.γ
     gdouble* ram_S; gulong* ram_skipped; double ram_targetrate; double ram_gamma;
+    // AM: the chains' covariances, D (D + 1) / 2 planes of nchains doubles (entry C_ij, i <= j, of chain c at [ktri(i, j, D) * nchains + c]); their running
+    // means, 2 D planes (lastmean_i at plane i, secondlastmean_i at plane D + i); the handle's counter of transitions that fell back to the minor component;
+    // AM.corescale, sqrt(AM.minorscale), the core component's weight 1 - AM.c, AM.t0
+    gdouble* am_C; gdouble* am_mean; gulong* am_fallbacks; double am_corescale; double am_sqrtminor; double am_w1; long long am_t0;
 };
 
 // Per-launch values, passed by value.  Everything else (KParams) is static for a handle and lives in device memory:
@@ -1148,8 +1158,34 @@ KLARA_PRAGMA_UNROLL_E
     }
     if (r.skipped != 0) atomicAdd((unsigned long long*)p.ram_skipped, r.skipped);
 }
+// The in-place factorisation RAM and AM share (smmala_factor's loop nest without log-determinant and diag term): the packed lower triangle A (A_ij, i >= j,
+// at ktri(j, i, E)) becomes its Cholesky factor, column by column, one sqrt and one reciprocal per pivot; false where a pivot is not a finite positive number
+template <int E>
+__device__ __forceinline__ bool tri_factor(double (&A)[E * (E + 1) / 2])
+{
+    bool ok = true;
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {
+        double sj = A[ktri(j, j, E)];
+KLARA_PRAGMA_UNROLL_E
+        for (int k = 0; k < j; ++k) sj = sj - A[ktri(k, j, E)] * A[ktri(k, j, E)];
+        const bool okj = sj > 0.0 && kfinite(sj);
+        ok = ok && okj;
+        const double ljj = __builtin_sqrt(okj ? sj : 1.0);
+        const double rj = 1.0 / ljj;
+        A[ktri(j, j, E)] = ljj;
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j + 1; i < E; ++i) {
+            double a = A[ktri(j, i, E)];
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 0; k < j; ++k) a = a - A[ktri(k, i, E)] * A[ktri(k, j, E)];
+            A[ktri(j, i, E)] = a * rj;
+        }
+    }
+    return ok;
+}
 // iterate/RAM.jl:123-129: S <- chol(S (I + c z z') S')' with c = eta (min(1, exp(ratio)) - targetrate) / (z . z), formed as S S' + c w w' with w = S z
-// (R2) and factored by smmala_factor's loop nest (R4); false — and S as it was — where z . z or a pivot is not a finite positive number
+// (R2) and factored by tri_factor (R4); false — and S as it was — where z . z or a pivot is not a finite positive number
 template <int E>
 __device__ __forceinline__ bool ram_update(const KParams& p, unsigned long long t, double ratio, double zz, const double (&w)[E], double (&S)[RamRegs<E>::NT])
 {
@@ -1169,24 +1205,7 @@ KLARA_PRAGMA_UNROLL_E
             A[ktri(j, i, E)] = a + (c * w[i]) * w[j];                                       // :128
         }
     }
-KLARA_PRAGMA_UNROLL_E
-    for (int j = 0; j < E; ++j) {                                                           // :129, in place: A becomes the new factor
-        double sj = A[ktri(j, j, E)];
-KLARA_PRAGMA_UNROLL_E
-        for (int k = 0; k < j; ++k) sj = sj - A[ktri(k, j, E)] * A[ktri(k, j, E)];
-        const bool okj = sj > 0.0 && kfinite(sj);
-        ok = ok && okj;
-        const double ljj = __builtin_sqrt(okj ? sj : 1.0);
-        const double rj = 1.0 / ljj;
-        A[ktri(j, j, E)] = ljj;
-KLARA_PRAGMA_UNROLL_E
-        for (int i = j + 1; i < E; ++i) {
-            double a = A[ktri(j, i, E)];
-KLARA_PRAGMA_UNROLL_E
-            for (int k = 0; k < j; ++k) a = a - A[ktri(k, i, E)] * A[ktri(k, j, E)];
-            A[ktri(j, i, E)] = a * rj;
-        }
-    }
+    ok = tri_factor<E>(A) && ok;                                                            // :129, in place: A becomes the new factor
 KLARA_PRAGMA_UNROLL_E
     for (int k = 0; k < RamRegs<E>::NT; ++k) S[k] = ok ? A[k] : S[k];
     return ok;
@@ -1227,6 +1246,142 @@ KLARA_PRAGMA_UNROLL_E
         lt = ltp;
     }
     if (!ram_update<E>(p, t, ratio, zz, w, rs.S)) rs.skipped += 1;                           // :123-129
+    return acc;
+}
+
+// ---- AM (src/samplers/AM.jl, iterate/AM.jl:77-152, after Haario, Saksman and Tamminen 2001 with the mixture proposal of Roberts and Rosenthal 2009) ----
+// C is the chain's E x E covariance in the lane's registers, its upper triangle packed (C_ij, i <= j, at ktri(i, j, E): Hermitian(C), iterate/AM.jl:91,
+// keeps that triangle); m and m2 are lastmean and secondlastmean.  The padding i >= D of C holds the identity block, the update is masked to the D x D
+// block, and x, z, m, m2 are zero there, so no bit depends on E (tests/am_ref.c runs the plain D loops).  The three travel between
+// launches in KParams::am_C / am_mean.
+template <int E>
+struct AmRegs {
+    static constexpr int NT = E * (E + 1) / 2;
+    double C[NT], m[E], m2[E];
+    unsigned long long fallbacks;    // transitions of this launch at which corescale C did not factor
+};
+// (the planes of a chain are walked with running offsets: entry (i, j), i <= j < D, in this order is plane ktri(i, j, D), the next one; 52 plane
+//  offsets formed at once at E = 8 would not fit the scalar registers)
+template <int E>
+__device__ __forceinline__ void am_load(const KParams& p, const LaneCtx<E>& cx, AmRegs<E>& r)
+{
+    const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's state and store nothing)
+    const gdouble* pc = p.am_C + c0;
+    const gdouble* pm = p.am_mean + c0;
+    const long long m2off = (long long)p.D * p.nchains;
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {
+KLARA_PRAGMA_UNROLL_E
+        for (int j = i; j < E; ++j) {
+            double v = i == j ? 1.0 : 0.0;
+            if (j < p.D) { v = *pc; pc += p.nchains; }
+            r.C[ktri(i, j, E)] = v;
+        }
+        double a = 0.0, b = 0.0;
+        if (i < p.D) { a = pm[0]; b = pm[m2off]; pm += p.nchains; }
+        r.m[i] = a; r.m2[i] = b;
+    }
+    r.fallbacks = 0;
+}
+template <int E>
+__device__ __forceinline__ void am_store(const KParams& p, const LaneCtx<E>& cx, const AmRegs<E>& r)
+{
+    gdouble* pc = p.am_C + cx.chain;
+    gdouble* pm = p.am_mean + cx.chain;
+    const long long m2off = (long long)p.D * p.nchains;
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {
+KLARA_PRAGMA_UNROLL_E
+        for (int j = i; j < E; ++j)
+            if (j < p.D) { *pc = r.C[ktri(i, j, E)]; pc += p.nchains; }
+        if (i < p.D) { pm[0] = r.m[i]; pm[m2off] = r.m2[i]; pm += p.nchains; }
+    }
+    if (r.fallbacks != 0) atomicAdd((unsigned long long*)p.am_fallbacks, r.fallbacks);
+}
+// covariance!(C, C, k, x, lastmean, secondlastmean), stats/covariance.jl:6-19, on the triangle Hermitian(C) keeps (iterate/AM.jl:87-91): entry (i, j), i <= j,
+// with i as the row of the three rank-one updates; plain products and sums in the reference's order
+template <int E>
+__device__ __forceinline__ void am_covariance(const KParams& p, long long k, const double (&x)[E], AmRegs<E>& r)
+{
+    const double kf = (double)k, km1 = (double)(k - 1), nk1 = (double)(-(k + 1));
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {
+        const double a = nk1 * r.m[i], b = kf * r.m2[i];                                    // :16 -(k+1)*lastmean, :17 k*secondlastmean
+KLARA_PRAGMA_UNROLL_E
+        for (int j = i; j < E; ++j) {
+            double c = km1 * r.C[ktri(i, j, E)];                                            // :14
+            c = c + x[i] * x[j];                                                            // :15
+            c = c + a * r.m[j];                                                             // :16
+            c = c + b * r.m2[j];                                                            // :17
+            c = c / kf;                                                                     // :18
+            r.C[ktri(i, j, E)] = j < p.D ? c : r.C[ktri(i, j, E)];                          // (A4: the padding stays the identity)
+        }
+    }
+}
+// L = chol(corescale C), lower, packed as RamRegs::S (L_ji, j >= i, at ktri(i, j, E) — where C_ij sits): ram_update's factorisation (tri_factor) and its pivot test;
+// false where a pivot is not a finite positive number (the reference's MvNormal constructor throws there: A2)
+template <int E>
+__device__ __forceinline__ bool am_factor(const KParams& p, const double (&C)[AmRegs<E>::NT], double (&A)[AmRegs<E>::NT])
+{
+KLARA_PRAGMA_UNROLL_E
+    for (int j = 0; j < E; ++j) {
+KLARA_PRAGMA_UNROLL_E
+        for (int i = j; i < E; ++i) A[ktri(j, i, E)] = i < p.D ? p.am_corescale * C[ktri(j, i, E)] : C[ktri(j, i, E)];
+    }
+    return tri_factor<E>(A);
+}
+// iterate!(job, AM, Multivariate) — iterate/AM.jl:77-152: MH's step with the proposal of the phase (count <= t0: N(x, minorscale I); beyond: C brought up to
+// date, then the mixture), then the running means from the state the accept test leaves.  The proposal log-densities of :102-106 cancel (A1).
+template <class T, int E, bool COMMIT = true>
+__device__ __forceinline__ bool step_am(const KParams& p, const T& tg, const LaneCtx<E>& cx,
+                                        unsigned long long gchain, unsigned long long t,
+                                        const double (&z)[E], const AccDraw& ad, AmRegs<E>& as,
+                                        double (&x)[E], double& lt, Proposal<E>& prop)
+{
+    double xp[E], gd[E], red[1];
+    const long long count = (long long)t + 1;                                               // :78
+    bool core = false;
+    if (count > p.am_t0) {                                                                  // :84-94 (uniform over the launch's chains: no divergence)
+        am_covariance<E>(p, count - 2, x, as);                                              // :87-91
+        double L[AmRegs<E>::NT];
+        const bool ok = am_factor<E>(p, as.C, L);                                           // set_gmm!, AM.jl:215-216
+        if (!ok) as.fallbacks += 1;                                                         // A2
+        // the component: a uniform from words (z, w) of the accept block, which nothing else reads
+        const double usel = kd_uniform_zw(kd_stream_block(p.seed, gchain, t, (uint32_t)((p.D + 1) >> 1)));
+        core = ok && usel < p.am_w1;
+KLARA_PRAGMA_UNROLL_E
+        for (int i = 0; i < E; ++i) {                                                       // x + L z, k ascending (as RAM's R1)
+            double a = L[ktri(0, i, E)] * z[0];
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 1; k <= i; ++k) a = a + L[ktri(k, i, E)] * z[k];
+            xp[i] = x[i] + (core ? a : p.am_sqrtminor * z[i]);                              // :96
+        }
+    } else {
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) xp[e] = x[e] + p.am_sqrtminor * z[e];                   // :85, :96 (set_normal!)
+    }
+    tg.template eval<true, false>(cx, xp, red[0], gd);                                      // :98
+    group_allreduce<1>(red, cx.G, cx.lane);
+    const double ltp = tg.finalize(red[0]);
+    const double ratio = ltp - lt;                                                          // :100
+    bool acc = ratio > 0.0;                                                                 // :108
+    acc = accept_log_test<E>(p, cx, gchain, t, ad, acc, ratio);
+    const double cm1 = (double)(count - 1), cf = (double)count;
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) {                                                           // :134-135, recursive_mean! (stats/mean.jl:5) with the new state
+        const double xn = acc ? xp[e] : x[e];
+        as.m2[e] = as.m[e];
+        as.m[e] = (cm1 * as.m[e] + xn) / cf;
+    }
+    if (!COMMIT) {
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) prop.x[e] = xp[e];
+        prop.lt = ltp;
+    } else if (acc) {                                                                       // :109-110
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) x[e] = xp[e];
+        lt = ltp;
+    }
     return acc;
 }
 
@@ -1561,9 +1716,10 @@ template <int SAMPLER, int TARGET, int E, int GT, int MODE>
 // (RAM: the factor S, E (E + 1) / 2 doubles, is live through the whole transition — the target's row loop included — and a second triangle while
 //  S S' + c w w' is formed and factored in place: 2 E (E + 1) registers before x, x', z and w — 144 at E = 8.  From the compiler's resource report on the
 //  logistic target: E = 2 takes 168-215 registers and E = 4 205-253 — two wavefronts per SIMD without scratch (asked for three they spill 32-160 B and
-//  116-304 B); E = 8 takes 256 + 52-80 accumulation registers at one wavefront per SIMD without scratch, and spills 136-304 B at two.  So 2, 2, 1: no RAM
+//  116-304 B); E = 8 takes 256 + 40-80 accumulation registers at one wavefront per SIMD without scratch, and spills 136-304 B at two.  So 2, 2, 1: no RAM
 //  kernel uses scratch; DESIGN.md section 2 and profiles/ram.txt have the table)
 __global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_RAM ? KLARA_RAM_WAVES(E, MODE) :
+                                   SAMPLER == KLARA_SAMPLER_AM ? KLARA_AM_WAVES(E, MODE) :
                                    SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
                                                                                                   metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2; with the
                                                                                                   softabs transform's eigenvectors: 20-120 B in every mode) */ :
@@ -1623,7 +1779,9 @@ void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
         // of the launch).  Fused launches amortise that latency over their transitions and load the next group when they get to it —
         // the prefetched copy would hold 2 E + 8 registers through every transition (logistic MALA at 4 wavefronts per SIMD: the
         // difference between fitting 128 registers and spilling).
-        constexpr bool PREFETCH = ONESTEP;
+        // (AM at E = 8 does not prefetch either: with the second lane context the kernel's scalar registers spill into vector registers it has none left for,
+        //  28 B of scratch in the compiler's report; the order of the loads changes no bit)
+        constexpr bool PREFETCH = ONESTEP && !(SAMPLER == KLARA_SAMPLER_AM && E == 8);
         const long long grp_next = grp + nwaves;
         const bool has_next = grp_next * cpw < p.nchains;
         LaneCtx<E> cxn = cx;
@@ -1675,6 +1833,9 @@ KLARA_PRAGMA_UNROLL_E
         // last one stopped whatever its length
         RamRegs<SAMPLER == KLARA_SAMPLER_RAM ? E : 2> rms;
         if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_load<E>(p, cx, rms);
+        // AM: the group's covariances and running means likewise
+        AmRegs<SAMPLER == KLARA_SAMPLER_AM ? E : 2> ams;
+        if constexpr (SAMPLER == KLARA_SAMPLER_AM) am_load<E>(p, cx, ams);
 
         TuneRegs tn;
         if (per_chain_tune) tn = { cur.step, cur.accepted, cur.proposed, cur.totproposed, 0, 0.0, 0.0 };
@@ -1696,6 +1857,7 @@ KLARA_PRAGMA_UNROLL_E
             if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA)
                 acc = step_smmala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, sms, prop);
             else if constexpr (SAMPLER == KLARA_SAMPLER_RAM) acc = step_ram<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, rms, cur.x, cur.lt, prop);
+            else if constexpr (SAMPLER == KLARA_SAMPLER_AM) acc = step_am<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, ams, cur.x, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_MH) acc = step_mh<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_MALA) acc = step_mala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_HMC) {
@@ -1770,6 +1932,7 @@ KLARA_PRAGMA_UNROLL_E
         }
         if (cx.chain_ok && cx.q == 0 && cx.rq == 0) {
             if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_store<E>(p, cx, rms);
+            if constexpr (SAMPLER == KLARA_SAMPLER_AM) am_store<E>(p, cx, ams);
             if (do_sum) p.held[cx.chain] = held;
             if (nacc != 0) { p.LT[cx.chain] = cur.lt; p.naccept[cx.chain] += nacc; }
             if (da) { p.tune_step[cx.chain] = tn.step; p.da_epsbar[cx.chain] = tn.epsbar; p.da_hbar[cx.chain] = tn.hbar; }

@@ -740,6 +740,37 @@ extern "C" klara_status klara_set_ram_factor(klara_handle* h, const double* S)
     return KLARA_OK;
 }
 
+extern "C" klara_status klara_get_am_state(klara_handle* h, double* Cout, double* lastmean, double* secondlastmean, int64_t* fallbacks)
+{
+    if (!h || h->d.sampler != KLARA_SAMPLER_AM) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims, NP = D * (D + 1) / 2;
+    if (Cout) {
+        std::vector<double> planes(NP * N);
+        HIPCHK(hipMemcpy(planes.data(), h->am_C, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < N; ++c)
+            for (size_t i = 0; i < D; ++i)
+                for (size_t j = 0; j < D; ++j) Cout[(c * D + i) * D + j] = planes[(size_t)ktri((int)(i < j ? i : j), (int)(i < j ? j : i), (int)D) * N + c];
+    }
+    if (lastmean || secondlastmean) {
+        std::vector<double> planes(2 * D * N);
+        HIPCHK(hipMemcpy(planes.data(), h->am_mean, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t c = 0; c < N; ++c)
+            for (size_t i = 0; i < D; ++i) {
+                if (lastmean) lastmean[c * D + i] = planes[i * N + c];
+                if (secondlastmean) secondlastmean[c * D + i] = planes[(D + i) * N + c];
+            }
+    }
+    if (fallbacks) {
+        unsigned long long k = 0;
+        HIPCHK(hipMemcpy(&k, h->am_fallbacks, sizeof(k), hipMemcpyDeviceToHost));
+        *fallbacks = (int64_t)k;
+    }
+    return KLARA_OK;
+}
+
 extern "C" klara_status klara_device_ptrs(klara_handle* h, void** x, void** logtarget, void** gradlogtarget)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;

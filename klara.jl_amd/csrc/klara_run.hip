@@ -35,6 +35,15 @@ __global__ void k_fill_ram(double* S, const double* tri, long long n, int nplane
     if (i < n) for (int k = 0; k < nplanes; ++k) S[(long long)k * n + i] = tri[k];
 }
 
+// AM: every chain's covariance restarts from C0 and both running means from the chain's start value (AM.jl:238-246, 292-304)
+__global__ void k_fill_am(double* Cm, const double* tri, double* mean, const double* X, long long n, int D)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int k = 0; k < D * (D + 1) / 2; ++k) Cm[(long long)k * n + i] = tri[k];
+    for (int k = 0; k < D; ++k) { const double v = X[i * D + k]; mean[(long long)k * n + i] = v; mean[(long long)(D + k) * n + i] = v; }
+}
+
 __global__ void k_fill2(double* a, double* b, long long n, double va, double vb)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -143,6 +152,11 @@ static klara_status init_common(klara_handle* h)
         hipLaunchKernelGGL(k_fill_ram, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->ram_S, h->ram_S0, (long long)N, (int)(D * (D + 1) / 2));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(h->ram_skipped, 0, sizeof(unsigned long long), st));
+    }
+    if (h->am_C) {
+        hipLaunchKernelGGL(k_fill_am, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->am_C, h->am_C0, h->am_mean, h->X, (long long)N, (int)D);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(h->am_fallbacks, 0, sizeof(unsigned long long), st));
     }
     const int needgrad = sampler_needs_gradient(d.sampler);
     KParams p = make_params(h);
@@ -429,6 +443,7 @@ hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
     case KLARA_SAMPLER_HMC: return klara_launch_hmc(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     case KLARA_SAMPLER_RAM: return klara_launch_ram(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    case KLARA_SAMPLER_AM: return klara_launch_am(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     default: return klara_launch_slice(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     }
 }

@@ -293,7 +293,8 @@ class Engine:
                  seed: int = 20260927, chain_offset: int = 0, device: int = 0, monitor: int = 0,
                  steps_per_launch: int = 0, stream: int = 0, nstreams: int = 0, bm_batchlen: int = 0, hist_ring_cols: int = 0,
                  acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0,
-                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None):
+                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None,
+                 am_C0=None, am_corescale: float = 0.0, am_minorscale: float = 0.0, am_c: float = 0.0, am_t0: int = 0):
         self._lib = L.load()
         self.target = target
         self.ndims = int(target.ndims)
@@ -359,6 +360,14 @@ class Engine:
                 raise ValueError(f"ram_S0 must be {self.ndims} x {self.ndims} (or its diagonal), not {a.shape}")
             keep.append(a); d.ram_S0 = _ptr(a)
         d.ram_targetrate, d.ram_gamma = float(ram_targetrate), float(ram_gamma)
+        # AM(C0; corescale, minorscale, c, t0): the initial covariance (D x D symmetric, its upper triangle is read; a vector is its diagonal), AM.jl:131-154
+        if am_C0 is not None:
+            a = _f64(am_C0)
+            a = _f64(np.diag(a.ravel())) if a.ndim < 2 else a
+            if a.shape != (self.ndims, self.ndims):
+                raise ValueError(f"am_C0 must be {self.ndims} x {self.ndims} (or its diagonal), not {a.shape}")
+            keep.append(a); d.am_C0 = _ptr(a)
+        d.am_corescale, d.am_minorscale, d.am_c, d.am_t0 = float(am_corescale), float(am_minorscale), float(am_c), int(am_t0)
         # pooled marginal histograms (klara_desc.marg_lo / marg_hi / marg_nbins): a Marginals, or (nbins, lo, hi)
         self.marginals = None
         if marginals is not None:
@@ -623,6 +632,15 @@ class Engine:
         S = _f64(S)
         S = _f64(np.broadcast_to(S, (self.nchains, self.ndims, self.ndims)))
         L.check(self._lib.klara_set_ram_factor(self._h, S.ctypes.data), "klara_set_ram_factor")
+
+    def am_state(self):
+        """(C (nchains, ndims, ndims) symmetric, lastmean (nchains, ndims), secondlastmean (nchains, ndims), fallbacks): the AM sampler's current
+        covariance and running means of every chain, and the number of transitions since set_state / reset at which corescale C did not factor
+        and the chain proposed from the minor component (klara_get_am_state)."""
+        Cm = np.empty((self.nchains, self.ndims, self.ndims)); m = np.empty((self.nchains, self.ndims)); m2 = np.empty((self.nchains, self.ndims))
+        k = C.c_int64(0)
+        L.check(self._lib.klara_get_am_state(self._h, Cm.ctypes.data, m.ctypes.data, m2.ctypes.data, C.byref(k)), "klara_get_am_state")
+        return Cm, m, m2, int(k.value)
 
     def dual_averaging(self):
         eb = np.empty(self.nchains); hb = np.empty(self.nchains)
