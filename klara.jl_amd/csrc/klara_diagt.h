@@ -36,7 +36,14 @@
 #define KLARA_DT_W1 4
 #endif
 #ifndef KLARA_Q4_MALA_WF
-#define KLARA_Q4_MALA_WF 3   // wavefronts per SIMD requested for the 4-lane MALA kernels with more than 8 pairs per lane
+#define KLARA_Q4_MALA_WF 3   // wavefronts per SIMD requested for the 4-lane MALA kernels with more than 8 pairs per lane (the arithmetic ones: they run at three; the table kernel: KLARA_Q4_SCTAB_WF)
+#endif
+// Wavefronts per SIMD the 4-lane table kernel's registers are budgeted for.  It RUNS at two — the table's 72 KB per workgroup leave room for two
+// workgroups of four wavefronts per compute unit, whatever the registers allow — so 3 caps it at 168 registers for an occupancy it cannot reach, and 2
+// would give it 256.  The budget stays 3: klara_get_kernel_attributes reports this kernel's registers and tests/test_gpu_parity.py holds them to the 168
+// of three wavefronts.  What 2 buys is measured (kept drift means, below): -3.5 % on the headline job.
+#ifndef KLARA_Q4_SCTAB_WF
+#define KLARA_Q4_SCTAB_WF 3
 #endif
 #ifndef KLARA_DT_WF
 #define KLARA_DT_WF 2     // wavefronts per SIMD requested for the fused / monitored / tuned instantiations
@@ -120,6 +127,19 @@ __device__ __forceinline__ PairCtx<NP, Q> make_pctx(int D)
 {
     PairCtx<NP, Q> c;
     c.lane = threadIdx.x & 63;
+    c.q = c.lane & (Q - 1);
+    c.cw = c.lane / Q;
+    c.off0 = (unsigned)((c.cw * D + 2 * c.q) * 8);
+    c.last_ok = 2 * ((NP - 1) * Q + c.q) < D;
+    c.last_full = 2 * ((NP - 1) * Q + c.q) + 1 < D;
+    return c;
+}
+// the same context from a lane number the caller supplies (k_diagt late_ctx)
+template <int NP, int Q>
+__device__ __forceinline__ PairCtx<NP, Q> make_pctx_at(int D, int lane)
+{
+    PairCtx<NP, Q> c;
+    c.lane = lane;
     c.q = c.lane & (Q - 1);
     c.cw = c.lane / Q;
     c.off0 = (unsigned)((c.cw * D + 2 * c.q) * 8);
@@ -394,10 +414,12 @@ __device__ __forceinline__ void diag_elem(double x, double w, double m2w, double
 // pooled per GPU, verbose counting) — the same device functions, per-chain state in registers over the launch.
 // DA (HMC only): DualAveragingMCTuner — per-chain step and trajectory length (iterate/HMC.jl:142-144, 225-249); the
 // wavefront runs to the longest trajectory of its chains, a finished chain's lanes keep their state.
-template <int SAMPLER, int NP, int Q, bool ONESTEP, bool TUNE>
+template <int SAMPLER, int NP, int Q, bool ONESTEP, bool TUNE, bool SCTAB = false>
 __host__ __device__ constexpr int diagt_min_waves()       // wavefronts per SIMD the register allocator is asked to leave room for
 {
-    return NP <= 8 ? (ONESTEP && SAMPLER != KLARA_SAMPLER_HMC ? KLARA_DT_W1 : KLARA_DT_WF)
+    // (SCTAB, 4 lanes: KLARA_Q4_SCTAB_WF below)
+    return SCTAB && Q == 4 && NP > 8 ? KLARA_Q4_SCTAB_WF
+         : NP <= 8 ? (ONESTEP && SAMPLER != KLARA_SAMPLER_HMC ? KLARA_DT_W1 : KLARA_DT_WF)
                    : (Q == 4 && NP <= 13 && !TUNE ? (SAMPLER == KLARA_SAMPLER_MALA ? KLARA_Q4_MALA_WF : 2) : 1);
 }
 
@@ -434,6 +456,37 @@ __host__ __device__ constexpr bool diagt_sctab()
 #endif
 template <int Q, bool SCTAB>
 __host__ __device__ constexpr int diagt_wg_threads() { return SCTAB && Q == 4 ? KLARA_Q4_SCTAB_WG : 256; }
+// Kept drift means.  The headline job rejects 99 % of its proposals, and the mean of the proposal density, m = x + (-h) * x, is a function of the
+// committed state alone: the two table kernels (untuned, unit weights: h = step0 over the whole launch) form it once per chain group after the state
+// is loaded, read it in mala_elem and re-form it from the accepted proposal in the commit — the same multiply and add from the same -h, so no bit
+// moves; nothing is stored, the next launch forms the means from the x it loads.  Two FP64 instructions per element and transition less.
+// The count is the prefix of a lane's elements whose means are kept, the rest are formed per transition as before; it is chosen by what compiles
+// clean (scripts/asm_load_distance.py: no scratch access and no lane spill in the transition body):
+// 4 lanes: none at the 168 registers of KLARA_Q4_SCTAB_WF = 3 — kept means need more registers than the allocator leaves: 4 kept already reload one
+//   value from scratch in every transition, 8 kept eight, 12 kept sixteen.  At KLARA_Q4_SCTAB_WF = 2 all 26 fit: 256 registers, 1,376 -> 1,324 vector
+//   instructions in the body, 28 B of scratch (three constants of the accept draw's log, read only by layouts without a padding pair); that build
+//   is bit for bit the oracle's (the jobs of tests/test_gpu_kept_drift_means.py) and measures -3.5 % on the headline job, 438.6 -> 422.2 us per
+//   launch.  It is a build-time choice (-DKLARA_Q4_SCTAB_WF=2 -DKLARA_Q4_KEPT_MEANS=26), not the default: see KLARA_Q4_SCTAB_WF.
+// 8 lanes: none.  12 of 14 compile clean (253 registers, no scratch, 759 -> 736; with 13 and 14 the body reads 6 and 2 scalar values back from spill
+//   lanes in every transition), but the device picks this kernel while chains move often, and a wavefront of 8 chains then commits in nearly every
+//   transition: the 24 instructions that re-form the means there take back the 23 saved, and the late-formed lane context that makes the room
+//   (late_ctx) has the fold of a moving chain re-form its offsets.  Measured on the launches of a fresh job: 12 kept with the late context
+//   SQ_INSTS_VALU +2.0 %, launch 511 -> 517 us; the late context alone +3.6 %, 512 -> 522 us.  So the 8-lane kernel gets neither and compiles to
+//   what it was but for the narrower launch constants (219 registers, no scratch); the count stays a build-time switch.
+// What made the room stays in the 4-lane kernel at either budget: the launch constants below are kept narrow and a lane's place is re-formed late
+// (late_ctx).  At 168 registers that takes the kernel from 60 B of scratch (25 scratch accesses per stored history column) to none, at 166 registers.
+// profiles/ab_kept_drift_means.txt.
+#ifndef KLARA_Q4_KEPT_MEANS
+#define KLARA_Q4_KEPT_MEANS 0
+#endif
+#ifndef KLARA_Q8_KEPT_MEANS
+#define KLARA_Q8_KEPT_MEANS 0
+#endif
+template <int SAMPLER, int NP, int Q, bool UNITW, bool TUNE, bool SCTAB>
+__host__ __device__ constexpr int diagt_kept_means()
+{
+    return SCTAB && SAMPLER == KLARA_SAMPLER_MALA && UNITW && !TUNE ? (Q == 4 ? KLARA_Q4_KEPT_MEANS : Q == 8 ? KLARA_Q8_KEPT_MEANS : 0) : 0;
+}
 
 // USERPAIR (run-time compiled instantiations only, klara_custom_pair.h): the target is the user's pair closure
 //     lt(x) = sum over element pairs P of klara_user_pair(x[2P], x[2P+1], P, ...)      (it also returns the pair's two partial derivatives)
@@ -447,7 +500,7 @@ __host__ __device__ constexpr int diagt_wg_threads() { return SCTAB && Q == 4 ? 
 #define KLARA_PAIR_CALL(a, b, P, g0, g1) 0.0
 #endif
 template <int SAMPLER, int NP, int Q, bool ONESTEP, bool UNITW, bool MON, bool TUNE = false, bool DA = false, bool USERPAIR = false, bool SCTAB = false>
-__global__ __launch_bounds__((diagt_wg_threads<Q, SCTAB>()), (SAMPLER == KLARA_SAMPLER_SLICE && NP <= 8 && !MON && !TUNE ? KLARA_DT_SLICE_WF : diagt_min_waves<SAMPLER, NP, Q, ONESTEP, TUNE>()))
+__global__ __launch_bounds__((diagt_wg_threads<Q, SCTAB>()), (SAMPLER == KLARA_SAMPLER_SLICE && NP <= 8 && !MON && !TUNE ? KLARA_DT_SLICE_WF : diagt_min_waves<SAMPLER, NP, Q, ONESTEP, TUNE, SCTAB>()))
 void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 {
 #ifndef KLARA_USER_PAIR_TARGET
@@ -462,6 +515,8 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
     constexpr int E = 2 * NP, CPW = 64 / Q;
     constexpr bool NEEDG = SAMPLER == KLARA_SAMPLER_MALA || SAMPLER == KLARA_SAMPLER_HMC;
     constexpr bool SLICE = SAMPLER == KLARA_SAMPLER_SLICE;
+    constexpr int KM = diagt_kept_means<SAMPLER, NP, Q, UNITW, TUNE, SCTAB>();
+    static_assert(KM >= 0 && KM <= E, "kept drift means: a prefix of the lane's elements");
     static_assert(!(SLICE && ONESTEP), "the slice sampler moves every chain: it runs the committing kernel");
     // running sums folded into memory instead of being held in registers (diagt_fold_rmw): untuned MH / MALA on the
     // 4-lanes-per-chain form of the layout
@@ -524,6 +579,16 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
 
         double x[E];
         load_pairs<NP, Q>(cx, wx, x);
+        // 4-lane table kernel: what the rarely taken branches of the step loop and the code behind it need of a lane's place — the chain, the pairs' offsets —
+        // is re-formed there from the lane's number (two mbcnt) through a register the compiler cannot see through.  Kept from here, those are values
+        // it spills before the loop and reads back in those branches: scratch bytes the kernel's first dispatch on a queue pays ~120 us to set up.
+        const auto late_ctx = [&]() -> PairCtx<NP, Q> {
+            if constexpr (SCTAB && Q == 4) {
+                int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                KLARA_PIN(l);
+                return make_pctx_at<NP, Q>(D, l & 63);
+            } else return cx;
+        };
         // The gradient of this target family is a function of the value alone and GR always holds gradlogtarget(X) (set by
         // initialize! and by every accepted transition).  It is therefore neither loaded nor kept: wherever iterate! reads
         // the current gradient it is re-formed from x — the same operations that produced the stored bits — and the
@@ -586,14 +651,32 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
         // registers opaque (nothing to rematerialise); the Philox key schedule then hangs off registers, not off a load.
         // (held_inc: a saved step's held += 1 as a scalar operand — the compiler's own form is a select in two vector registers.)  The other
         // instantiations keep reading at the point of use: KLARA_LC picks at compile time, and their code is what it was.
-        struct { unsigned long long seed; long long burnin, nsteps_total, hist_cols, held_inc; int thinning; double sqrt_step0, inv_step0; } lc = {};
+        struct { unsigned long long seed; long long hist_cols, held_inc; int thinning, acc_free, save_lo, save_hi; double sqrt_step0, half_inv_step0; } lc = {};
         if constexpr (SCTAB) {
-            lc.seed = p.seed; lc.burnin = p.burnin; lc.nsteps_total = p.nsteps_total; lc.hist_cols = p.hist_cols; lc.thinning = (int)p.thinning;
-            lc.held_inc = __builtin_amdgcn_readfirstlane(do_sum ? 1 : 0); lc.sqrt_step0 = p.sqrt_step0; lc.inv_step0 = p.inv_step0;
-            KLARA_PIN_S(lc.seed); KLARA_PIN_S(lc.burnin); KLARA_PIN_S(lc.nsteps_total); KLARA_PIN_S(lc.hist_cols); KLARA_PIN_S(lc.thinning);
-            KLARA_PIN_S(lc.held_inc); KLARA_PIN_S(lc.sqrt_step0); KLARA_PIN_S(lc.inv_step0);
+            lc.seed = p.seed; lc.hist_cols = p.hist_cols; lc.thinning = (int)p.thinning;
+            lc.held_inc = __builtin_amdgcn_readfirstlane(do_sum ? 1 : 0); lc.sqrt_step0 = p.sqrt_step0;
+            KLARA_PIN_S(lc.seed); KLARA_PIN_S(lc.hist_cols); KLARA_PIN_S(lc.thinning);
+            KLARA_PIN_S(lc.held_inc); KLARA_PIN_S(lc.sqrt_step0);
+            // (MALA's 0.5 / h: a product, so the compiler holds it in a vector register pair over the loop; handed to scalar registers it frees the pair)
+            const kd_uint2 hih = __builtin_bit_cast(kd_uint2, 0.5 * p.inv_step0);
+            lc.half_inv_step0 = __builtin_bit_cast(double, kd_uint2{ (uint32_t)__builtin_amdgcn_readfirstlane((int)hih.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)hih.y) });
+            KLARA_PIN_S(lc.half_inv_step0);
+            // (the wave-uniform "the accept draw is the last pair's" as one scalar register: as a condition the compiler keeps it as a 64-bit lane mask)
+            lc.acc_free = __builtin_amdgcn_readfirstlane(acc_free ? 1 : 0);
+            KLARA_PIN_S(lc.acc_free);
+            // (the save range burnin < t0 + s + 1 <= nsteps_total as the launch's own steps save_lo <= s < save_hi: two registers for four)
+            const long long lo = (long long)p.burnin - (long long)kl.t0, hi = (long long)p.nsteps_total - (long long)kl.t0;
+            lc.save_lo = (int)(lo < 0 ? 0 : lo > nsteps ? nsteps : lo); lc.save_hi = (int)(hi < 0 ? 0 : hi > nsteps ? nsteps : hi);
+            KLARA_PIN_S(lc.save_lo); KLARA_PIN_S(lc.save_hi);
         }
 #define KLARA_LC(f) (SCTAB ? lc.f : p.f)
+        // kept drift means (diagt_kept_means above): x + (-h) * x of the committed state, the multiply and the add mala_elem would form
+        double dm[KM > 0 ? KM : 1];
+        const double neg_h_kept = KM > 0 ? -tn.step : 0.0;
+        if constexpr (KM > 0) {
+#pragma unroll
+            for (int e = 0; e < KM; ++e) dm[e] = x[e] + neg_h_kept * x[e];
+        }
         for (int s = 0; s < nsteps; ++s) {
             const unsigned long long t = kl.t0 + (unsigned long long)s;
             if (KCNT) tune_count_proposal(p, tn);
@@ -769,7 +852,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot)));
             } else if (SAMPLER == KLARA_SAMPLER_MALA) {                            // iterate/MALA.jl:78-128
                 const double h_ = tn.step, halfh = 0.5 * h_, sq = KCNT ? __builtin_sqrt(h_) : KLARA_LC(sqrt_step0);
-                const double half_inv_h = 0.5 * (KCNT ? 1.0 / h_ : KLARA_LC(inv_step0));
+                const double half_inv_h = SCTAB ? lc.half_inv_step0 : 0.5 * (KCNT ? 1.0 / h_ : p.inv_step0);
                 // UNITW: the gradient -2.0 * x is an exact scaling, so halfh * (-2.0 * x) and (-h) * x are one real number, rounded once
                 // either way: the same bits and one instruction less per mean (still a multiply and an add, never an fma).  It needs h to
                 // be a normal number (0.5 * h is exact) and -2 x not to overflow (|x| <= DBL_MAX / 2; lt is -inf from |x| ~ 1e154 on).
@@ -781,7 +864,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 const auto mala_elem = [&](int e, double ze, int r, bool first) -> double {
                     double term, ge = 0.0, gpe;
                     if constexpr (!UNITW) diag_elem<UNITW>(x[e], wv(e), m2wv(e), mv(e), term, ge);   // (the current gradient, re-formed)
-                    const double m_ = UNITW ? x[e] + neg_h * x[e] : x[e] + halfh * ge;         // :83
+                    const double m_ = UNITW ? (e < KM ? dm[e < KM ? e : 0] : x[e] + neg_h * x[e]) : x[e] + halfh * ge;   // :83
                     const double xe = m_ + sq * ze;                                            // :84
                     diag_elem<UNITW>(xe, wv(e), m2wv(e), mv(e), term, gpe);         // :86
                     red[r] = first ? term : red[r] + term;
@@ -831,9 +914,13 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 ratio += red[1];                                                               // :90
                 ratio -= red[2];                                                               // :92
                 acc = ratio > 0.0;                                                             // :94
-                if (acc_free) acc = acc || ratio > lane_bcast(lg_last, acc_lane);
-                else if (!acc && ratio > KD_LOG_UMIN_GUARD)
-                    acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot)));
+                if (SCTAB ? lc.acc_free != 0 : acc_free) acc = acc || ratio > lane_bcast(lg_last, acc_lane);
+                else {
+                    double guard = KD_LOG_UMIN_GUARD;
+                    if constexpr (SCTAB) KLARA_PIN_S(guard);     // (formed here, on the rare side: hoisted, the constant is spilled to a lane and read back in every transition)
+                    if (!acc && ratio > guard)
+                        acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot)));
+                }
             } else {                                                               // iterate/HMC.jl:124-201
                 const double eps = tn.step, halfe = 0.5 * eps;
                 double mom[E], gp[E];
@@ -937,7 +1024,12 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 acc = u < a;                                                                   // :165
             }
 
-            if (accept_out != nullptr && chain_ok && cx.q == 0) accept_out[(long long)s * p.nchains + chain] = acc ? 1 : 0;
+            if constexpr (SCTAB) {
+                if (accept_out != nullptr) {
+                    const PairCtx<NP, Q> cxa = late_ctx();
+                    if (cxa.cw < here && cxa.q == 0) accept_out[(long long)s * p.nchains + (first_chain + cxa.cw)] = acc ? 1 : 0;
+                }
+            } else if (accept_out != nullptr && chain_ok && cx.q == 0) accept_out[(long long)s * p.nchains + chain] = acc ? 1 : 0;
             if (KCNT && acc && !SLICE) tn.accepted += 1;                // (the slice sampler never counts accepts)
             if (DA) da_update(p, tn, (long long)t + 1, a_da);           // iterate/HMC.jl:225-249
             if (per_chain_tune && !DA) tuning_block(p, tn);             // iterate/MALA.jl:130-152, HMC.jl:203-224
@@ -967,44 +1059,54 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                 if (acc) {
 #pragma unroll
                     for (int e = 0; e < E; ++e) x[e] = xp[e];
+                    if constexpr (KM > 0) {              // the new state's drift means (exec-masked per chain, like the copy above)
+#pragma unroll
+                        for (int e = 0; e < KM; ++e) dm[e] = xp[e] + neg_h_kept * xp[e];
+                    }
                     lt = ltp;
                 }
             }
             // save rule: BasicMCJob.jl:226-231 with postrange = (burnin+1):thinning:nsteps (BasicMCRange.jl:36); the
             // phase / column bookkeeping comes from the host (klara_run_async), as in the group-layout kernel
             const long long i1 = (long long)t + 1;
-            if (MON && i1 > KLARA_LC(burnin) && i1 <= KLARA_LC(nsteps_total)) {
+            if (MON && (SCTAB ? s >= lc.save_lo && s < lc.save_hi : i1 > p.burnin && i1 <= p.nsteps_total)) {
                 if (sphase == 0) {
                     if constexpr (SCTAB) held += lc.held_inc;
                     else if (do_sum) held += 1;
                     if (scol < KLARA_LC(hist_cols)) {
                         const long long col0 = scol * p.nchains + first_chain;
-                        if (p.hist != nullptr) store_pairs<NP, Q>(cx, group_window(p.hist, col0, here, D), x);
-                        if (NEEDG && p.hist_g != nullptr) { double gq[E]; grad_of(x, gq); store_pairs<NP, Q>(cx, group_window(p.hist_g, col0, here, D), gq); }
-                        if (p.hist_lt != nullptr && chain_ok && cx.q == 0) p.hist_lt[scol * p.nchains + chain] = lt;
+                        const PairCtx<NP, Q> cxh = late_ctx();      // (4-lane table kernel: the pairs' offsets are formed here, not kept over the step loop)
+                        if (p.hist != nullptr) store_pairs<NP, Q>(cxh, group_window(p.hist, col0, here, D), x);
+                        if (NEEDG && p.hist_g != nullptr) { double gq[E]; grad_of(x, gq); store_pairs<NP, Q>(cxh, group_window(p.hist_g, col0, here, D), gq); }
+                        if constexpr (SCTAB) {
+                            if (p.hist_lt != nullptr && cxh.cw < here && cxh.q == 0) p.hist_lt[scol * p.nchains + (first_chain + cxh.cw)] = lt;
+                        } else if (p.hist_lt != nullptr && chain_ok && cx.q == 0) p.hist_lt[scol * p.nchains + chain] = lt;
                     }
                     ++scol;
                 }
                 sphase = (sphase + 1 == (SCTAB ? lc.thinning : (int)p.thinning)) ? 0 : sphase + 1;
             }
         }
+        const PairCtx<NP, Q> cxe = late_ctx();             // (the 4-lane table kernel keeps nothing of the lane's place over the step loop)
+        const bool chain_ok_e = SCTAB ? cxe.cw < here : chain_ok;
+        const long long chain_e = SCTAB ? first_chain + cxe.cw : chain;
         if (do_sum) {
             if constexpr (!MEMSUM) {
                 if (__any(sums_loaded)) {                  // only the chains that left a state during the launch write their sums back
-                    store_pairs_if<NP, Q>(cx, wsum, sums_loaded, sm);
-                    store_pairs_if<NP, Q>(cx, wsq, sums_loaded, sq);
+                    store_pairs_if<NP, Q>(cxe, wsum, sums_loaded, sm);
+                    store_pairs_if<NP, Q>(cxe, wsq, sums_loaded, sq);
                 }
             }
-            if (chain_ok && cx.q == 0) p.held[chain] = held;
+            if (chain_ok_e && cxe.q == 0) p.held[chain_e] = held;
         }
         // (a per-lane flag: the lane whose coordinate ran out of attempts stops, the chain's other lanes finish the transition — the oracle returns at the
         // first stuck coordinate, so after KLARA_ERR_SLICE_STUCK the device state is NOT the oracle's: unspecified, include/klara_hip.h)
         if (SLICE && stuck && chain_ok) klara_raise(p.error_flag, KLARA_ERR_SLICE_STUCK);
-        if (!ONESTEP) wave_acc += (chain_ok && cx.q == 0) ? (unsigned)nacc : 0u;     // (per-lane partial; summed in auto_finish)
+        if (!ONESTEP) wave_acc += (chain_ok_e && cxe.q == 0) ? (unsigned)nacc : 0u;     // (per-lane partial; summed in auto_finish)
         if (!ONESTEP && nacc != 0) {
-            store_pairs<NP, Q>(cx, wx, x);
-            if (NEEDG) { double gq[E]; grad_of(x, gq); store_pairs<NP, Q>(cx, wg, gq); }
-            if (chain_ok && cx.q == 0) { p.LT[chain] = lt; p.naccept[chain] += nacc; }
+            store_pairs<NP, Q>(cxe, wx, x);
+            if (NEEDG) { double gq[E]; grad_of(x, gq); store_pairs<NP, Q>(cxe, wg, gq); }
+            if (chain_ok_e && cxe.q == 0) { p.LT[chain_e] = lt; p.naccept[chain_e] += nacc; }
         }
         if (TUNE && chain_ok && cx.q == 0) {
             if (DA) { p.tune_step[chain] = tn.step; p.da_epsbar[chain] = tn.epsbar; p.da_hbar[chain] = tn.hbar; }
