@@ -15,7 +15,9 @@ EPS = np.finfo(np.float64).eps
 # by A1 / A2 the device computes the same bits, so these are the device's errors too).  The test's cap is 4 x these.
 MEASURED = {"negdot_d2": 0.0, "negdot_d3": 0.0, "negdot_d9": 0.0, "negdot_d32": 0.0, "negdot_d33": 0.0, "negdot_d100": 0.0, "negdot_d520": 0.0,
             "banana": 1.394, "logit_swiss": 2.313, "logit_d9": 0.726, "quartic_d33": 1.055, "quartic_d100": 1.058, "nn_d5": 0.850, "erf_d3": 2.575,
-            "gauss_d3": 0.787}
+            "gauss_d3": 0.787,
+            # tests/test_closure_sweep_host.py: the coupled likelihood + prior closure of tests/closure_sweep.py at D = 105, hand-written gll + glp and its autodiff form
+            "quartic_parts_hand_d105": 1.102, "quartic_parts_d105": 1.079}
 MEASURED_ORDER2 = {"logit_swiss": 5.333, "gauss_d3": 0.0}
 
 AD_NEGDOT = r"""

@@ -130,6 +130,25 @@ def split_dense_layout(d: int):
     return (6, w, new)
 
 
+def staged_plan(ndims: int, custom_rows: int = 2):
+    """(G, E, wpb, padded, stride) of a whole-vector closure staged through LDS (klara_plan.h custom_layout / custom_stage_bytes, D > 32): G lanes x
+    E = 2 ceil(D / 2G) <= 16 elements, `wpb` wavefronts per workgroup whose rows (wpb x 64 / G chains, `custom_rows` vectors each) stay within 56 KB;
+    `stride` is a chain's row length in doubles, `padded` whether it carries the 2-double bank pad.  KLARA_CUSTOM_LANES / KLARA_CUSTOM_WPB are honoured
+    as the library honours them.  default_layout's staged branch and tests/closure_sweep.py both call this: the arithmetic is written once on this side."""
+    d = int(ndims)
+    g = int(os.environ.get("KLARA_CUSTOM_LANES", "0")) or 4
+    rows = custom_rows
+    stride = rows * ((d + 1) & ~1) + 2
+    padded = (2 * stride) % 64 == 0
+    stride += 2 if padded else 0
+    while g < 64 and (d + 2 * g - 1) // (2 * g) > 8:          # at most 16 elements per lane (round 6: up to 64 lanes, D <= 1024)
+        g *= 2
+    wpb = int(os.environ.get("KLARA_CUSTOM_WPB", "0")) or (2 if (g >= 8 and 4 * (64 // g) * stride * 8 > 57344) else 4)   # wavefronts per workgroup
+    while g < 64 and wpb * (64 // g) * stride * 8 > 57344:
+        g *= 2
+    return g, 2 * ((d + 2 * g - 1) // (2 * g)), wpb, padded, stride
+
+
 def default_layout(target_kind: int, ndims: int, ndata: int = 0, sampler=None, tuner=0, tuner_mode=0, verbose=False,
                    hier_nunits: int = 0, hier_ntimes: int = 0, summaries: bool = True, sparse_moves: bool = False, pair_form: bool = False, custom_rows: int = 2):
     """Mirror of the product's layout choice (klara_get_layout reports the real one on the GPU box).  `sampler`, `tuner`,
@@ -151,16 +170,8 @@ def default_layout(target_kind: int, ndims: int, ndata: int = 0, sampler=None, t
     if target_kind == L.TARGET_CUSTOM and d > 32 and os.environ.get("KLARA_CUSTOM_LANES", "0") != "1":
         # whole-vector closure staged through LDS (klara_plan.h custom_layout): G lanes x E = 2 ceil(D / 2G) <= 16 elements, a workgroup's
         # rows (4 wavefronts x 64 / G chains, `custom_rows` vectors each) within 56 KB
-        g = int(os.environ.get("KLARA_CUSTOM_LANES", "0")) or 4
-        rows = custom_rows
-        stride = rows * ((d + 1) & ~1) + 2
-        stride += 2 if (2 * stride) % 64 == 0 else 0
-        while g < 64 and (d + 2 * g - 1) // (2 * g) > 8:          # at most 16 elements per lane (round 6: up to 64 lanes, D <= 1024)
-            g *= 2
-        wpb = int(os.environ.get("KLARA_CUSTOM_WPB", "0")) or (2 if (g >= 8 and 4 * (64 // g) * stride * 8 > 57344) else 4)   # wavefronts per workgroup
-        while g < 64 and wpb * (64 // g) * stride * 8 > 57344:
-            g *= 2
-        return (0, g, 2 * ((d + 2 * g - 1) // (2 * g)))
+        g, e = staged_plan(d, custom_rows)[:2]
+        return (0, g, e)
     if target_kind == L.TARGET_CUSTOM:        # one chain per lane, pow2ceil(D) elements in registers (klara_custom.h)
         e = 2
         while e < d:
