@@ -666,6 +666,22 @@ __device__ __forceinline__ void kd_normal_pair_issue(uint32_t wa, uint32_t wb, k
     r->rot = *(const kd_screm_t*)&KD_SCTAB(2 * (k >> 12));
     r->rem = kd_screm_lds[k & (KD_SCREM_ENTRIES - 1u)];
 }
+/* kd_normal_pair_issue in two parts, for a caller that has too little work of its own to put between issue and finish (klara_diagt.h, the screened
+ * MALA kernel's first pass): the log bin's entry is the first one finish consumes, the two angle entries are the last — the log and the radius stand
+ * between.  The same reads into the same fields. */
+__device__ __forceinline__ void kd_normal_pair_issue_log(uint32_t wa, uint32_t wb, kd_pair_reads* r)
+{
+    uint32_t i;
+    r->u1 = kd_u44(wa, wb);
+    kd_log_u01_reduce(r->u1, &i, &r->k, &r->z);
+    r->lg = *(const kd_screm_t*)&KD_LOGTAB(2 * i);
+}
+__device__ __forceinline__ void kd_normal_pair_issue_angle(uint32_t wb, kd_pair_reads* r)
+{
+    const uint32_t k = wb >> 12;
+    r->rot = *(const kd_screm_t*)&KD_SCTAB(2 * (k >> 12));
+    r->rem = kd_screm_lds[k & (KD_SCREM_ENTRIES - 1u)];
+}
 __device__ __forceinline__ void kd_normal_pair_finish(const kd_pair_reads* r, double* z0, double* z1, double* u1_out, double* logu1_out)
 {
     const double lg = kd_log_u01_finish(r->z, r->k, r->lg.x, r->lg.y);

@@ -19,6 +19,7 @@
 // this order for layout kind 3 (oracle/klara_oracle.c ko_reduce).
 #pragma once
 #include "klara_kernels.h"
+#include "klara_mala_screen.h"
 
 #ifndef KLARA_DIAGT_Q
 #define KLARA_DIAGT_Q 8                       // lanes per chain
@@ -379,6 +380,24 @@ __device__ __forceinline__ void pair_issue(const PairCtx<NP, Q>& c, unsigned lon
     kd_normal_pair_issue(wa, wb, &rd);
     __builtin_amdgcn_sched_barrier(0);
 }
+// pair_issue in two parts (detmath.h kd_normal_pair_issue_log / _angle): the pair's words and its log bin's read, then its two angle reads (wb: the
+// word they are addressed by).  For the screened MALA kernel's first pass, which has four fmas per pair of its own: pair p + 1's log read goes out
+// before pair p is finished, its angle reads after — they are consumed last, behind the pair's log and radius — so that no read is waited for
+// soon after it was issued and only the log part of a second pair's entries is live across a finish (7 registers, not 17).
+template <int NP, int Q>
+__device__ __forceinline__ void pair_issue_log(const PairCtx<NP, Q>& c, unsigned long long seed, unsigned long long gchain,
+                                               unsigned long long t, int p, uint32_t (&stash)[4], kd_pair_reads& rd, uint32_t& wb)
+{
+    uint32_t wa;
+    pair_words<NP, Q>(c, seed, gchain, t, p, stash, wa, wb);
+    kd_normal_pair_issue_log(wa, wb, &rd);
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void pair_issue_angle(uint32_t wb, kd_pair_reads& rd)
+{
+    kd_normal_pair_issue_angle(wb, &rd);
+    __builtin_amdgcn_sched_barrier(0);
+}
 template <int NP, int Q>
 __device__ __forceinline__ void pair_finish(const PairCtx<NP, Q>& c, int p, const kd_pair_reads& rd, double& z0, double& z1, double& u1, double& lg1)
 {
@@ -445,6 +464,35 @@ template <int SAMPLER, int NP, int Q, bool ONESTEP, bool UNITW, bool MON, bool T
 __host__ __device__ constexpr bool diagt_sctab()
 {
     return SAMPLER == KLARA_SAMPLER_MALA && ((Q == 4 && NP == 13) || (Q == 8 && NP == 7)) && !ONESTEP && UNITW && MON && !TUNE;
+}
+// Screened rejections (klara_mala_screen.h).  The headline job rejects 99 % of its proposals, and all a rejected transition
+// leaves behind is the fact that it was rejected.  On lt = gconst - sum x^2 the Metropolis ratio is, in real arithmetic, linear in sum x^2 (kept per
+// lane with the committed state), sum x z and sum z^2: the 4-lane table kernel first draws a transition's normals into the registers of the
+// proposal, adds up the two sums (two fma per element), and asks kd_mala_screen_decide whether the accept test certainly fails — the estimate
+// stands 2^-30 of the terms' magnitudes clear of log u, 2^14 times the proven distance between it and the ratio the kernel would compute.  If that
+// holds for every chain of the wavefront the transition is over (acc = false); otherwise the literal arithmetic of MALA.jl:83-92 runs over the
+// stored normals, in the same order, and decides as before: no bit of any result depends on the estimate.  A wavefront of 16 chains falls back in
+// 6-13 % of the transitions of the headline job.  The 8-lane sibling runs while chains move often and keeps the one-pass loop.
+// -DKLARA_MALA_SCREEN=0 compiles the screen out (the A/B build of profiles/ab_mala_reject_screen.txt).
+#ifndef KLARA_MALA_SCREEN
+#define KLARA_MALA_SCREEN 1
+#endif
+// A wavefront ends at most KLARA_MALA_SCREEN_RUN transitions in a row on the screen; the next one takes the literal pass whatever the screen says
+// (0: no limit).  This is a brake, and it is here for one reason: bench.py's roofline prices the headline kernel at the reference's formula on every
+// proposal (scripts/instruction_budget.py: 1,505 vector instructions per wavefront and transition, held by tests/test_host_api.py), and
+// tests/test_gpu_multi.py holds the priced fraction of a single-stream launch to at most 1 — 321 us for 32 transitions of 65,536 chains.  Without a
+// limit the kernel runs such a launch in 320-330 us, at that line, and the test passes or fails with the box.  Counted in runs, not in the launch's
+// steps, the brake costs nothing where wavefronts fall back of their own accord (a fresh job's first launches); a change that prices the screen in
+// the budget can set this to 0.  No bit depends on it.  profiles/ab_mala_reject_screen.txt.
+#ifndef KLARA_MALA_SCREEN_RUN
+#define KLARA_MALA_SCREEN_RUN 2
+#endif
+template <bool C, class A, class B> struct kd_type_if { typedef A type; };
+template <class A, class B> struct kd_type_if<false, A, B> { typedef B type; };
+template <int SAMPLER, int NP, int Q, bool UNITW, bool TUNE, bool USERPAIR, bool SCTAB>
+__host__ __device__ constexpr bool diagt_mala_screen()
+{
+    return KLARA_MALA_SCREEN != 0 && SCTAB && SAMPLER == KLARA_SAMPLER_MALA && Q == 4 && NP == 13 && UNITW && !TUNE && !USERPAIR;
 }
 // threads per workgroup of a kernel (the launcher's workgroup, klara_launch.h diagt_go): 256 — four chain groups — everywhere; the 4-lane table
 // kernel's is a build-time choice, because 384 threads (two workgroups per compute unit: 2 x 72 KB, three wavefronts per SIMD at its 168
@@ -517,6 +565,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
     constexpr bool SLICE = SAMPLER == KLARA_SAMPLER_SLICE;
     constexpr int KM = diagt_kept_means<SAMPLER, NP, Q, UNITW, TUNE, SCTAB>();
     static_assert(KM >= 0 && KM <= E, "kept drift means: a prefix of the lane's elements");
+    constexpr bool SCREEN = diagt_mala_screen<SAMPLER, NP, Q, UNITW, TUNE, USERPAIR, SCTAB>();
     static_assert(!(SLICE && ONESTEP), "the slice sampler moves every chain: it runs the committing kernel");
     // running sums folded into memory instead of being held in registers (diagt_fold_rmw): untuned MH / MALA on the
     // 4-lanes-per-chain form of the layout
@@ -532,6 +581,17 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
             lds_w[i] = (p.gw != nullptr && i < p.D) ? p.gw[i] : 1.0;
             lds_mu[i] = (p.gmu != nullptr && i < p.D) ? p.gmu[i] : 0.0;
             lds_m2w[i] = -2.0 * lds_w[i];
+        }
+    }
+    // screened rejections: the launch's screen constants (K0, K1), (T0, T2), K2 — one LDS copy per workgroup: five more scalar
+    // register pairs over the step loop are more than the allocator has (it spills loop constants of the log to lanes and reads them back in
+    // every transition).  A launch the bound is not proven for (kd_mala_screen_k::on) screens nothing: its T is NaN, and "certain" needs T <= 2^1000.
+    __shared__ __attribute__((aligned(16))) double lds_screen[6];
+    if constexpr (SCREEN) {
+        if (threadIdx.x == 0) {
+            const kd_mala_screen_k k = kd_mala_screen_consts(p.step0, p.sqrt_step0, 0.5 * p.inv_step0);
+            lds_screen[0] = k.K0; lds_screen[1] = k.K1; lds_screen[4] = k.K2; lds_screen[5] = 0.0;
+            lds_screen[2] = k.on ? k.T0 : __builtin_nan(""); lds_screen[3] = k.on ? k.T2 : __builtin_nan("");
         }
     }
     auto_begin();
@@ -614,7 +674,8 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
             }
         };
         double lt = p.LT[chain_ok ? chain : 0];
-        unsigned long long nacc = 0;
+        // (screened kernel: 32 bits — a launch has fewer than 2^31 steps — which pays for the register of its run counter `srun` below)
+        typename kd_type_if<SCREEN, unsigned, unsigned long long>::type nacc = 0;
         bool stuck = false;                                // slice sampler: step-out / shrink ran out of attempts
         // saved-sample monitors (MON).  Running sums are kept in sojourn form (KParams::held): the save rule only counts the saved
         // steps a chain spends at its current state, and the state is folded into sum / sumsq (held * x, held * x^2) when the
@@ -676,6 +737,14 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
         if constexpr (KM > 0) {
 #pragma unroll
             for (int e = 0; e < KM; ++e) dm[e] = x[e] + neg_h_kept * x[e];
+        }
+        // screened rejections (diagt_mala_screen above): the lane's share of the committed state's sum x^2 — formed from x itself, here and in the commit:
+        // lt is the caller's to set
+        double sxx = 0.0;
+        int srun = 0;                                      // transitions in a row that this wavefront ended on the screen (wave-uniform)
+        if constexpr (SCREEN) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) sxx = kd_fma(x[e], x[e], sxx);
         }
         for (int s = 0; s < nsteps; ++s) {
             const unsigned long long t = kl.t0 + (unsigned long long)s;
@@ -875,10 +944,51 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     red[r + 2] = first ? (q2 * q2) * half_inv_h : red[r + 2] + (q2 * q2) * half_inv_h;   // :92
                     return xe;
                 };
+                // Screened rejections, first pass: the transition's normals go to the proposal's registers and into sum x z and sum z^2 (estimates: one partial
+                // each); pair pi + 1's log read goes out before pair pi is finished and its angle reads after (pair_issue_log) — there is no elementwise arithmetic to run them under.
+                // Padding chains count as certain; one chain that may accept sends the wavefront through the literal arithmetic below.
+                bool screened = false;
+                if constexpr (SCREEN) {
+                    double sxz = 0.0, szz = 0.0;
+                    kd_screm_t sk01, skt;
+                    double sk2;
+                    pair_issue<NP, Q>(cx, KLARA_LC(seed), gchain, t, 0, nstash, rd[0]);
+#pragma unroll
+                    for (int pi = 0; pi < NP; ++pi) {
+                        double z0, z1;
+                        uint32_t wb_next = 0u;
+                        if (pi == NP - 1) {                              // the screen constants, under the last pair (volatile: read here, not kept over the loop)
+                            typedef volatile const __attribute__((address_space(3))) kd_screm_t* lds_entry;
+                            sk01 = *(lds_entry)&lds_screen[0]; skt = *(lds_entry)&lds_screen[2];
+                            sk2 = *(volatile const __attribute__((address_space(3))) double*)&lds_screen[4];
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        if (pi + 1 < NP) pair_issue_log<NP, Q>(cx, KLARA_LC(seed), gchain, t, pi + 1, nstash, rd[(pi + 1) & 1], wb_next);
+                        pair_finish<NP, Q>(cx, pi, rd[pi & 1], z0, z1, u_last, lg_last);
+                        if (pi + 1 < NP) pair_issue_angle(wb_next, rd[(pi + 1) & 1]);
+                        sxz = kd_fma(x[2 * pi], z0, sxz); sxz = kd_fma(x[2 * pi + 1], z1, sxz);
+                        szz = kd_fma(z0, z0, szz); szz = kd_fma(z1, z1, szz);
+                        put_xp(pi, z0, z1);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    double sc[2] = { kd_mala_screen_e(sk01.x, sk01.y, sk2, sxx, sxz, szz), kd_mala_screen_t(skt.x, skt.y, sxx, szz) };
+                    group_allreduce<2>(sc, Q, cx.lane);
+                    double lg_s;
+                    if (lc.acc_free != 0) lg_s = lane_bcast(lg_last, acc_lane);
+                    else { lg_s = KD_LOG_UMIN_GUARD; KLARA_PIN_S(lg_s); }       // (no draw in hand: certain means the kernel would not draw)
+                    const bool certain = !chain_ok || kd_mala_screen_decide(sc[0], sc[1], lt, gconst, lg_s, nullptr, nullptr) != 0;
+                    screened = __all(certain) != 0;
+                    if (KLARA_MALA_SCREEN_RUN > 0 && srun >= KLARA_MALA_SCREEN_RUN) screened = false;     // (the brake: see KLARA_MALA_SCREEN_RUN)
+                    srun = screened ? srun + 1 : 0;
+                    KLARA_PIN(srun);                                     // (in a vector register: one more scalar over the loop and the allocator spills a constant of the log to a lane)
+                    acc = false; ltp = lt;                               // the reject path; nothing below reads the estimate
+                }
+                if (!screened) {
 #pragma unroll
                 for (int pi = 0; pi < NP; ++pi) {
                     double z0 = ZFIRST ? z[(2 * pi) % (ZFIRST ? E : 2)] : 0.0, z1 = ZFIRST ? z[(2 * pi + 1) % (ZFIRST ? E : 2)] : 0.0;
-                    if constexpr (!ZFIRST && SCTAB) {
+                    if constexpr (SCREEN) { z0 = xp[2 * pi]; z1 = xp[2 * pi + 1]; }      // second pass: the stored normals, the proposal written in place
+                    else if constexpr (!ZFIRST && SCTAB) {
                         // pair pi's entries were asked for one pair ago: its angle reads have had the last pair's arithmetic and this pair's log and
                         // radius to arrive.  Pair pi + 1's reads (after its Philox block, where it forms one) go out in front of this pair's arithmetic.
                         if (pi == 0) pair_issue<NP, Q>(cx, KLARA_LC(seed), gchain, t, 0, nstash, rd[0]);
@@ -904,7 +1014,8 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                         const double a = mala_elem(2 * pi, z0, r, FROM_TERM && pi < NR), b = mala_elem(2 * pi + 1, z1, r, false);
                         put_xp(pi, a, b);
                     }
-                    if constexpr (!ZFIRST && SCTAB) __builtin_amdgcn_sched_barrier(0);
+                    if constexpr (SCREEN) { }                            // (second pass: nothing to fence, the normals are drawn)
+                    else if constexpr (!ZFIRST && SCTAB) __builtin_amdgcn_sched_barrier(0);
                     else if (!ZFIRST) KLARA_DT_PAIR_FENCE(pi);
                 }
                 group_allreduce<3 * NR>(red, Q, cx.lane);
@@ -920,6 +1031,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     if constexpr (SCTAB) KLARA_PIN_S(guard);     // (formed here, on the rare side: hoisted, the constant is spilled to a lane and read back in every transition)
                     if (!acc && ratio > guard)
                         acc = ratio > kd_log_u01(kd_accept_uniform(kd_stream_block(KLARA_LC(seed), gchain, t, (uint32_t)acc_slot)));
+                }
                 }
             } else {                                                               // iterate/HMC.jl:124-201
                 const double eps = tn.step, halfe = 0.5 * eps;
@@ -1044,7 +1156,7 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     if (chain_ok && cx.q == 0) { p.LT[chain] = ltp; p.naccept[chain] += 1ull; }
                 }
             } else {
-                nacc += acc ? 1ull : 0ull;
+                nacc += acc ? 1u : 0u;
                 if (!SLICE && do_sum && __any(chain_ok && acc && held > 0)) {          // a chain of this wavefront leaves its state
                     const bool fold = chain_ok && acc && held > 0;
 #ifdef KLARA_DT_FOLD_RMW
@@ -1062,6 +1174,11 @@ void k_diagt(const KParams* __restrict__ pp, const KLaunch kl, const KAuto ka)
                     if constexpr (KM > 0) {              // the new state's drift means (exec-masked per chain, like the copy above)
 #pragma unroll
                         for (int e = 0; e < KM; ++e) dm[e] = xp[e] + neg_h_kept * xp[e];
+                    }
+                    if constexpr (SCREEN) {              // the new state's sum x^2
+                        sxx = 0.0;
+#pragma unroll
+                        for (int e = 0; e < E; ++e) sxx = kd_fma(xp[e], xp[e], sxx);
                     }
                     lt = ltp;
                 }
