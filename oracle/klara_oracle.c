@@ -34,6 +34,12 @@
  *   slice sampler, coordinate i: slot (i << 14): words (x,y) -> log-uniform, (z,w) -> runiform;
  *     shrink attempt a >= 1: slot (i << 14) | ((a + 1) >> 1), words (x,y) for odd a, (z,w) for even a (two attempts per block).
  *   initial state x0 ~ N(0,I): transition index 2^40 - 1 ("-1"), same element -> slot mapping.
+ *   SMMALA, RAM, AM: the D normals and the accept uniform of MH / MALA; AM's component selector: words (z,w) of the accept block.
+ *
+ * SMMALA (with or without the softabs transform of its metric, klara_softabs.h), RAM and AM restate the kernels of klara_kernels.h
+ * (step_smmala, step_ram / ram_update, step_am / am_covariance / am_factor) loop for loop — DESIGN.md section 2, deviations S1-S5, T1-T5,
+ * R1-R4, A1-A5 — for E <= 8 padded elements per chain and a logistic or user-defined target.  They run in ko_run's two loops like every
+ * other sampler; what a chain carries beyond x, g and lt (RAM's factor, AM's covariance and means) comes in through ko_sampler_state.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -42,8 +48,11 @@
 
 #include "../include/klara_hip.h"
 #include "../klara.jl_amd/csrc/detmath.h"
+#include "../klara.jl_amd/csrc/klara_softabs.h"      /* the very header the device compiles (ko_smmala) */
 
 #define KO_MAXD 1024
+#define KO_MAXE 8                                    /* SMMALA, RAM, AM: elements per lane the kernels hold a chain's matrix in */
+#define KO_MAXNT (KO_MAXE * (KO_MAXE + 1) / 2)
 
 /* LITERAL MODE (VERDICT r3 item 5 / ADVICE r3): ko_set_literal(1) — or KO_LITERAL=1 in the environment when the library is loaded —
  * takes back the deliberate deviations from the literal Julia arithmetic that the shipped oracle shares with the kernels (DESIGN.md
@@ -377,6 +386,10 @@ typedef void (*ko_user_grad_fn)(const double* x, int D, const double* data, long
 static ko_user_lt_fn ko_user_lt = NULL;
 static ko_user_grad_fn ko_user_grad = NULL;
 void ko_set_custom_target(ko_user_lt_fn lt, ko_user_grad_fn grad) { ko_user_lt = lt; ko_user_grad = grad; }
+/* SMMALA: the user's klara_user_tensorlogtarget (the metric G(x), D x D row-major, upper triangle read) */
+typedef void (*ko_user_tensor_fn)(const double* x, int D, const double* data, long long ndata, double* G);
+static ko_user_tensor_fn ko_user_tensor = NULL;
+void ko_set_custom_tensor(ko_user_tensor_fn tensor) { ko_user_tensor = tensor; }
 
 /* The same closures given one element pair at a time (`#define KLARA_USER_PAIR_TARGET 1`, include/klara_hip.h):
  *     lt(x) = sum over pairs P of klara_user_pair(x[2P], x[2P+1], P, ...),   which also returns the pair's two partial derivatives.
@@ -497,7 +510,8 @@ static void ko_tuning_block(const klara_desc* d, ko_tune* tn, int cnt, int64_t p
  * MALA.jl(iterate):79 / HMC.jl(iterate):129-133 `(Vanilla && verbose) || AcceptanceRate`. */
 static int ko_cnt(const klara_desc* d)
 {
-    if (d->sampler == KLARA_SAMPLER_MH || d->sampler == KLARA_SAMPLER_SLICE) return d->verbose != 0;
+    if (d->sampler == KLARA_SAMPLER_MH || d->sampler == KLARA_SAMPLER_SLICE || d->sampler == KLARA_SAMPLER_RAM || d->sampler == KLARA_SAMPLER_AM)
+        return d->verbose != 0;                                          /* iterate/RAM.jl:68, iterate/AM.jl:80: tuner.verbose */
     return (d->tuner == KLARA_TUNER_VANILLA && d->verbose) || d->tuner == KLARA_TUNER_ACCEPT_RATE ||
            (d->tuner == KLARA_TUNER_DUAL_AVERAGING && d->verbose);      /* HMC.jl(iterate):129-133 */
 }
@@ -758,6 +772,362 @@ static int ko_slice_pair_delta(const ko_target_ctx* c, uint64_t chain, uint64_t 
     return 1;
 }
 
+/* ------------------------------------------------------------------ SMMALA, RAM, AM: the samplers that carry a matrix per chain */
+/* What such a chain carries beyond x, g and lt, as the caller of ko_init / ko_run holds it (NULL for the other samplers; SMMALA's factor
+ * state is not here: it is formed from x and its gradient at the start of every ko_run call, as the kernels do at a launch start). */
+typedef struct ko_sampler_state {
+    double* ram_S;            /* RAM: nchains packed E x E lower factors, S_ij (i >= j) at ko_tri(j, i, E), the identity in the padding */
+    int64_t* ram_skipped;     /* RAM: += the factor updates skipped (z . z or a pivot not a finite positive number), over all chains */
+    double* am_C;             /* AM: nchains packed D x D upper triangles, C_ij (i <= j) at ko_tri(i, j, D) */
+    double* am_mean;          /* AM: nchains x D, lastmean */
+    double* am_mean2;         /* AM: nchains x D, secondlastmean */
+    int64_t* am_fallbacks;    /* AM: += the transitions whose covariance did not factor (A2), over all chains */
+    int64_t* softabs_sweeps;  /* SMMALA with the transform, may be NULL: [0] += metrics transformed, [1] += their sweeps, [2] = max(., most sweeps) */
+} ko_sampler_state;
+
+static int ko_matrix_sampler(int s) { return s == KLARA_SAMPLER_SMMALA || s == KLARA_SAMPLER_RAM || s == KLARA_SAMPLER_AM; }
+static int ko_tri(int a, int b, int E) { return a * E - (a * (a - 1)) / 2 + (b - a); }
+
+/* smmala_factor's loop nest (klara_kernels.h tri_factor), which ram_update and am_factor share (R4, A2): the packed n x n matrix A (upper
+ * triangle, A_ji (j <= i) at ko_tri(j, i, n)) becomes its lower Cholesky factor in place, column by column.  1 when every pivot is a finite
+ * positive number; a pivot that is not counts as 1. */
+static int ko_tri_factor(int n, double* A)
+{
+    int ok = 1;
+    for (int j = 0; j < n; ++j) {
+        double sj = A[ko_tri(j, j, n)];
+        for (int k = 0; k < j; ++k) sj = sj - A[ko_tri(k, j, n)] * A[ko_tri(k, j, n)];
+        const int okj = sj > 0.0 && ko_isfinite(sj);
+        ok = ok && okj;
+        const double ljj = sqrt(okj ? sj : 1.0);
+        const double rj = 1.0 / ljj;
+        A[ko_tri(j, j, n)] = ljj;
+        for (int i = j + 1; i < n; ++i) {
+            double a = A[ko_tri(j, i, n)];
+            for (int k = 0; k < j; ++k) a = a - A[ko_tri(k, i, n)] * A[ko_tri(k, j, n)];
+            A[ko_tri(j, i, n)] = a * rj;
+        }
+    }
+    return ok;
+}
+
+/* a chain of one of the three samplers during a ko_run call */
+typedef struct ko_smmala_state { double L[KO_MAXNT], r[KO_MAXE], f[KO_MAXE], ld; } ko_smmala_state;
+typedef struct ko_chain {
+    ko_smmala_state sm;       /* SMMALA: factor of the metric at x, its reciprocal diagonal, the drift G^-1 g, log det L */
+    double* S;                /* RAM: this chain's factor */
+    double *C, *m, *m2;       /* AM: this chain's covariance and means */
+    int64_t cn[4];            /* counted during the call: RAM updates skipped, AM fallbacks, metrics transformed, their sweeps ... */
+    int64_t maxsweeps;        /* ... and the most sweeps of one metric */
+} ko_chain;
+
+/* ---- SMMALA (klara_kernels.h step_smmala; iterate/SMMALA.jl) */
+/* the butterflied upper triangle of X' diag(r (1 - r)) X over E padded columns (LogisticTarget::eval, NTRI > 0), or the upper triangle of a
+ * user's tensor (CustomTarget::eval); no other target runs the softabs transform: NaNs */
+void ko_smmala_metric(const klara_desc* d, const ko_layout* L, const double* x, double* gm)
+{
+    const int E = L->E, D = d->ndims, NT = E * (E + 1) / 2, n = d->logit_ndata;
+    if (d->target == KLARA_TARGET_CUSTOM) {
+        double gt[KO_MAXE * KO_MAXE];
+        ko_user_tensor(x, D, d->custom_data, (long long)d->custom_ndata, gt);
+        for (int a = 0; a < E; ++a) for (int b = a; b < E; ++b) gm[ko_tri(a, b, E)] = b < D ? gt[a * D + b] : 0.0;
+        return;
+    }
+    if (d->smmala_softabs > 0.0) {
+        for (int k = 0; k < NT; ++k) gm[k] = kd_u2d(0x7ff8000000000000ull);          /* (no other target runs the transform) */
+        return;
+    }
+    const int RS = L->kind == 2 ? L->G : 1;
+    double part[16][KO_MAXNT], nw[16][KO_MAXNT];
+    for (int l = 0; l < RS; ++l) for (int k = 0; k < NT; ++k) part[l][k] = 0.0;
+    for (int r = 0; r < n; ++r) {
+        double row[KO_MAXE], xp = 0.0, sp, lg;
+        for (int e = 0; e < E; ++e) row[e] = e < D ? d->logit_X[(size_t)r * D + e] : 0.0;
+        for (int e = 0; e < E; ++e) xp = kd_fma(row[e], e < D ? x[e] : 0.0, xp);
+        kd_softplus_logistic_rows(xp, &sp, &lg);
+        const double wr = lg * (1.0 - lg);
+        double* pl = part[r % RS];
+        for (int a = 0; a < E; ++a) {
+            const double ta = row[a] * wr;
+            for (int b = a; b < E; ++b) pl[ko_tri(a, b, E)] = kd_fma(ta, row[b], pl[ko_tri(a, b, E)]);
+        }
+    }
+    for (int m = 1; m < RS; m <<= 1) {
+        for (int l = 0; l < RS; ++l) for (int k = 0; k < NT; ++k) nw[l][k] = part[l][k] + part[l ^ m][k];
+        memcpy(part, nw, sizeof(part));
+    }
+    for (int k = 0; k < NT; ++k) gm[k] = part[0][k];
+}
+
+/* the metric's diagonal term beyond gm (T::metric_diag): I / lambda of the logistic target, nothing for a user's tensor */
+static double ko_smmala_diag(const klara_desc* d) { return d->target == KLARA_TARGET_LOGISTIC ? 1.0 / d->logit_lambda : 0.0; }
+
+/* klara_desc.smmala_softabs > 0: the metric with T::metric_diag added, transformed (klara_kernels.h smmala_softabs_metric); the
+ * factorisation then adds nothing.  Returns the diagonal term that is left for the factorisation to add. */
+static double ko_smmala_transform(const klara_desc* d, int E, double* gm, ko_chain* ch)
+{
+    const int D = d->ndims;
+    const double diag = ko_smmala_diag(d);
+    if (!(d->smmala_softabs > 0.0)) return diag;
+    for (int j = 0; j < D; ++j) gm[ko_tri(j, j, E)] = gm[ko_tri(j, j, E)] + diag;
+    double Q[KO_MAXE * KO_MAXE];
+    const int sweeps = ksa_softabs_tri(gm, D, E, d->smmala_softabs, Q, 1);
+    if (sweeps > ch->maxsweeps) ch->maxsweeps = sweeps;
+    if (sweeps >= 0) { ch->cn[3] += sweeps; ch->cn[2] += 1; }
+    return 0.0;
+}
+
+/* smmala_factor: G = L L' column by column; 1 when every pivot is a finite positive number */
+static int ko_smmala_factor(const double* gm, int D, int E, double inv_lambda, ko_smmala_state* s)
+{
+    for (int j = 0; j < E; ++j) {
+        s->L[ko_tri(j, j, E)] = j < D ? gm[ko_tri(j, j, E)] + inv_lambda : 1.0;
+        for (int i = j + 1; i < E; ++i) s->L[ko_tri(j, i, E)] = (i < D && j < D) ? gm[ko_tri(j, i, E)] : 0.0;
+    }
+    const int pd = ko_tri_factor(E, s->L);
+    double ld = 0.0;
+    for (int j = 0; j < E; ++j) {
+        const double ljj = s->L[ko_tri(j, j, E)];
+        s->r[j] = 1.0 / ljj;
+        ld = ld + kd_log(ljj);
+    }
+    s->ld = ld;
+    return pd;
+}
+static void ko_smmala_solve_lt(const ko_smmala_state* s, int E, const double* z, double* v)
+{
+    for (int i = E - 1; i >= 0; --i) {
+        double t = z[i];
+        for (int k = i + 1; k < E; ++k) t = t - s->L[ko_tri(i, k, E)] * v[k];
+        v[i] = t * s->r[i];
+    }
+}
+static void ko_smmala_drift(ko_smmala_state* s, int E, const double* g)
+{
+    double y[KO_MAXE];
+    for (int i = 0; i < E; ++i) {
+        double t = g[i];
+        for (int k = 0; k < i; ++k) t = t - s->L[ko_tri(k, i, E)] * y[k];
+        y[i] = t * s->r[i];
+    }
+    ko_smmala_solve_lt(s, E, y, s->f);
+}
+static double ko_smmala_quad(const ko_smmala_state* s, int E, const double* d)
+{
+    double q = 0.0;
+    for (int i = 0; i < E; ++i) {
+        double w = s->L[ko_tri(i, i, E)] * d[i];
+        for (int k = i + 1; k < E; ++k) w = w + s->L[ko_tri(i, k, E)] * d[k];
+        q = q + w * w;
+    }
+    return q;
+}
+
+/* the factor state at x (padded to E) with gradient g: what the kernels form at a launch start and check at a start state (S5) */
+static int ko_smmala_state_at(const ko_target_ctx* c, const double* x, const double* g, ko_chain* ch)
+{
+    const klara_desc* d = c->d;
+    const int E = c->L->E, D = d->ndims;
+    double gm[KO_MAXNT], gp[KO_MAXE];
+    ko_smmala_metric(d, c->L, x, gm);
+    for (int e = 0; e < E; ++e) gp[e] = e < D ? g[e] : 0.0;
+    const double diag = ko_smmala_transform(d, E, gm, ch);
+    const int pd = ko_smmala_factor(gm, D, E, diag, &ch->sm);
+    ko_smmala_drift(&ch->sm, E, gp);
+    return pd;
+}
+
+/* step_smmala for one chain: x, g (D), lt and the factor state are updated on acceptance */
+static int ko_smmala(const ko_target_ctx* c, uint64_t chain, uint64_t t, double h, double* x, double* g, double* lt, ko_chain* ch)
+{
+    const klara_desc* d = c->d;
+    const int E = c->L->E, D = d->ndims;
+    ko_smmala_state* s = &ch->sm;
+    double z[KO_MAXE], xe[KO_MAXE], mu[KO_MAXE], v[KO_MAXE], xp[KO_MAXE], dd[KO_MAXE], gp[KO_MAXE], gm[KO_MAXNT], scratch[KO_MAXD];
+    for (int e = 0; e < KO_MAXE; ++e) { z[e] = 0.0; gp[e] = 0.0; }
+    ko_normals(d->seed, chain, t, D, z);
+    for (int e = 0; e < E; ++e) xe[e] = e < D ? x[e] : 0.0;
+    const double halfh = 0.5 * h, sq = sqrt(h), inv_h = 1.0 / h, dlogh = (double)D * kd_log(h);
+    for (int e = 0; e < E; ++e) mu[e] = xe[e] + halfh * s->f[e];
+    ko_smmala_solve_lt(s, E, z, v);
+    for (int e = 0; e < E; ++e) xp[e] = mu[e] + sq * v[e];
+    for (int e = 0; e < E; ++e) dd[e] = xp[e] - mu[e];
+    const double fwd = 0.5 * ((dlogh - 2.0 * s->ld) + ko_smmala_quad(s, E, dd) * inv_h);
+    const double ltp = ko_uptograd(c, xp, gp, scratch);
+    ko_smmala_metric(d, c->L, xp, gm);
+    ko_smmala_state sn;
+    const double diag = ko_smmala_transform(d, E, gm, ch);
+    const int pd = ko_smmala_factor(gm, D, E, diag, &sn);
+    ko_smmala_drift(&sn, E, gp);
+    for (int e = 0; e < E; ++e) dd[e] = xe[e] - (xp[e] + halfh * sn.f[e]);
+    const double rev = 0.5 * ((dlogh - 2.0 * sn.ld) + ko_smmala_quad(&sn, E, dd) * inv_h);
+    double ratio = ltp - *lt;
+    ratio += fwd;
+    ratio -= rev;
+    int acc = ratio > 0.0;
+    if (!acc) acc = ratio > kd_log_u01(ko_accept_uniform(d->seed, chain, t, D));
+    acc = acc && pd;
+    if (acc) {
+        memcpy(x, xp, sizeof(double) * (size_t)D);
+        memcpy(g, gp, sizeof(double) * (size_t)D);
+        *lt = ltp;
+        *s = sn;
+    }
+    return acc;
+}
+
+/* ---- RAM (klara_kernels.h step_ram / ram_update; iterate/RAM.jl) */
+/* iterate/RAM.jl:123-127: c = eta (min(1, exp(ratio)) - targetrate) / (z . z), eta = min(1, D count^-gamma), count = t + 1 (R3) */
+double ko_ram_coef(int D, uint64_t t, double gamma, double targetrate, double ratio, double zz)
+{
+    double eta = (double)D * kd_exp(-gamma * kd_log((double)(t + 1ull)));
+    eta = eta < 1.0 ? eta : 1.0;
+    const double ap = ratio >= 0.0 ? 1.0 : (ko_isfinite(ratio) ? kd_exp(ratio) : 0.0);
+    return eta * (ap - targetrate) / zz;
+}
+
+/* ram_update from c on: A = S S' + c w w' (R2), factored in place (R4).  S: the packed E x E lower factor, S_ij (i >= j) at ko_tri(j, i, E).
+ * Returns 1 and the new factor, or 0 — S as it was — where z . z or a pivot is not a finite positive number. */
+int ko_ram_update_c(int E, double c, double zz, const double* w, double* S)
+{
+    const int NT = E * (E + 1) / 2;
+    double A[KO_MAXNT];
+    for (int j = 0; j < E; ++j)
+        for (int i = j; i < E; ++i) {
+            double a = S[ko_tri(0, i, E)] * S[ko_tri(0, j, E)];
+            for (int k = 1; k <= j; ++k) a = a + S[ko_tri(k, i, E)] * S[ko_tri(k, j, E)];
+            A[ko_tri(j, i, E)] = a + (c * w[i]) * w[j];
+        }
+    const int ok = ko_tri_factor(E, A) && zz > 0.0 && ko_isfinite(zz);
+    if (ok) memcpy(S, A, sizeof(double) * (size_t)NT);
+    return ok;
+}
+
+/* step_ram for one chain: x (D) and lt are updated on acceptance, the factor S (packed, E padded) after every transition; z_out (E) and
+ * c_out, where given, take what the transition drew and formed */
+static int ko_ram(const ko_target_ctx* c, uint64_t chain, uint64_t t, double* x, double* lt, ko_chain* ch, double* z_out, double* c_out)
+{
+    const klara_desc* d = c->d;
+    const int E = c->L->E, D = d->ndims;
+    double* S = ch->S;
+    double z[KO_MAXE], w[KO_MAXE], xp[KO_MAXE], zz = 0.0, scratch[KO_MAXD];
+    for (int e = 0; e < KO_MAXE; ++e) z[e] = 0.0;
+    ko_normals(d->seed, chain, t, D, z);
+    for (int e = 0; e < E; ++e) zz = zz + z[e] * z[e];
+    for (int i = 0; i < E; ++i) {                                   /* R1 */
+        double a = S[ko_tri(0, i, E)] * z[0];
+        for (int k = 1; k <= i; ++k) a = a + S[ko_tri(k, i, E)] * z[k];
+        w[i] = a;
+    }
+    for (int e = 0; e < E; ++e) xp[e] = (e < D ? x[e] : 0.0) + w[e];
+    const double ltp = ko_logtarget(c, xp, scratch);
+    const double ratio = ltp - *lt;
+    int acc = ratio > 0.0;
+    if (!acc) acc = ratio > kd_log_u01(ko_accept_uniform(d->seed, chain, t, D));
+    if (acc) { memcpy(x, xp, sizeof(double) * (size_t)D); *lt = ltp; }
+    const double cf = ko_ram_coef(D, t, d->ram_gamma, d->ram_targetrate, ratio, zz);
+    if (z_out) { memcpy(z_out, z, sizeof(double) * (size_t)E); *c_out = cf; }
+    if (!ko_ram_update_c(E, cf, zz, w, S)) ch->cn[0] += 1;
+    return acc;
+}
+
+/* ---- AM (klara_kernels.h step_am / am_covariance / am_factor; iterate/AM.jl): plain loops over the D elements — the kernel's padding to
+ * E elements may change no bit (A5) */
+/* the component selector of transition t: words (z, w) of the accept block, slot ceil(D / 2) */
+double ko_am_selector(uint64_t seed, uint64_t chain, uint64_t t, int D)
+{
+    return kd_uniform_zw(kd_stream_block(seed, chain, t, (uint32_t)((D + 1) >> 1)));
+}
+
+/* covariance!(C, C, k, x, lastmean, secondlastmean), stats/covariance.jl:6-19, on the packed upper triangle (C_ij, i <= j, at ko_tri(i, j, D)) */
+void ko_am_covariance(int D, int64_t k, const double* x, const double* m, const double* m2, double* C)
+{
+    const double kf = (double)k, km1 = (double)(k - 1), nk1 = (double)(-(k + 1));
+    for (int i = 0; i < D; ++i) {
+        const double a = nk1 * m[i], b = kf * m2[i];
+        for (int j = i; j < D; ++j) {
+            double c = km1 * C[ko_tri(i, j, D)];
+            c = c + x[i] * x[j];
+            c = c + a * m[j];
+            c = c + b * m2[j];
+            C[ko_tri(i, j, D)] = c / kf;
+        }
+    }
+}
+
+/* L = chol(corescale C), lower, L_ji (j >= i) at ko_tri(i, j, D); 1, or 0 where a pivot is not a finite positive number (A2) */
+int ko_am_factor(int D, double corescale, const double* C, double* A)
+{
+    for (int k = 0; k < D * (D + 1) / 2; ++k) A[k] = corescale * C[k];
+    return ko_tri_factor(D, A);
+}
+
+/* step_am for one chain: x (D) and lt are updated on acceptance; C (packed), m, m2 as the kernel keeps them */
+static int ko_am(const ko_target_ctx* c, uint64_t chain, uint64_t t, double* x, double* lt, ko_chain* ch)
+{
+    const klara_desc* d = c->d;
+    const int D = d->ndims;
+    double *C = ch->C, *m = ch->m, *m2 = ch->m2;
+    const int64_t count = (int64_t)t + 1;
+    const double sqrtminor = sqrt(d->am_minorscale), w1 = 1.0 - d->am_c;
+    double z[KO_MAXE], xp[KO_MAXE], scratch[KO_MAXD];
+    for (int e = 0; e < KO_MAXE; ++e) { z[e] = 0.0; xp[e] = 0.0; }
+    ko_normals(d->seed, chain, t, D, z);
+    if (count > d->am_t0) {
+        double Lf[KO_MAXNT];
+        ko_am_covariance(D, count - 2, x, m, m2, C);
+        const int ok = ko_am_factor(D, d->am_corescale, C, Lf);
+        if (!ok) ch->cn[1] += 1;
+        const int core = ok && ko_am_selector(d->seed, chain, t, D) < w1;
+        for (int i = 0; i < D; ++i) {
+            double a = Lf[ko_tri(0, i, D)] * z[0];
+            for (int k = 1; k <= i; ++k) a = a + Lf[ko_tri(k, i, D)] * z[k];
+            xp[i] = x[i] + (core ? a : sqrtminor * z[i]);
+        }
+    } else {
+        for (int e = 0; e < D; ++e) xp[e] = x[e] + sqrtminor * z[e];
+    }
+    const double ltp = ko_logtarget(c, xp, scratch);
+    const double ratio = ltp - *lt;
+    int acc = ratio > 0.0;
+    if (!acc) acc = ratio > kd_log_u01(ko_accept_uniform(d->seed, chain, t, D));
+    if (acc) { memcpy(x, xp, sizeof(double) * (size_t)D); *lt = ltp; }
+    const double cm1 = (double)(count - 1), cf = (double)count;
+    for (int e = 0; e < D; ++e) { m2[e] = m[e]; m[e] = (cm1 * m[e] + x[e]) / cf; }
+    return acc;
+}
+
+/* ---- the three samplers inside ko_init / ko_run */
+/* what the kernels serve (klara_plan.h smmala_eligible / ram_eligible / am_eligible): E <= 8 padded elements, and the state that RAM and AM need */
+static int ko_matrix_check(const klara_desc* d, const ko_layout* L, const ko_sampler_state* ss)
+{
+    if (L->E > KO_MAXE || d->ndims > L->E || d->ndims < 1) return KLARA_ERR_UNSUPPORTED;
+    if (d->sampler == KLARA_SAMPLER_RAM && !(ss && ss->ram_S)) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler == KLARA_SAMPLER_AM && !(ss && ss->am_C && ss->am_mean && ss->am_mean2)) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler == KLARA_SAMPLER_SMMALA && d->target == KLARA_TARGET_CUSTOM && !ko_user_tensor) return KLARA_ERR_INVALID_ARG;
+    return KLARA_OK;
+}
+/* chain n at the start of a ko_run call */
+static void ko_chain_begin(const ko_target_ctx* c, const ko_sampler_state* ss, int64_t n, const double* x, const double* g, ko_chain* ch)
+{
+    const int D = c->d->ndims, E = c->L->E;
+    memset(ch->cn, 0, sizeof ch->cn); ch->maxsweeps = 0;
+    if (c->d->sampler == KLARA_SAMPLER_SMMALA) (void)ko_smmala_state_at(c, x, g, ch);
+    else if (c->d->sampler == KLARA_SAMPLER_RAM) ch->S = ss->ram_S + n * (E * (E + 1) / 2);
+    else { ch->C = ss->am_C + n * (D * (D + 1) / 2); ch->m = ss->am_mean + n * D; ch->m2 = ss->am_mean2 + n * D; }
+}
+/* the counts of a call, summed over its chains, go out once */
+static void ko_counts_out(const ko_sampler_state* ss, const int64_t cn[4], int64_t maxsweeps)
+{
+    if (!ss) return;
+    if (ss->ram_skipped) *ss->ram_skipped += cn[0];
+    if (ss->am_fallbacks) *ss->am_fallbacks += cn[1];
+    if (ss->softabs_sweeps) {
+        ss->softabs_sweeps[0] += cn[2]; ss->softabs_sweeps[1] += cn[3];
+        if (maxsweeps > ss->softabs_sweeps[2]) ss->softabs_sweeps[2] = maxsweeps;
+    }
+}
+
 /* Streaming batch means (klara_desc.bm_batchlen): mcvar(v, Val{:bm}) of src/stats/variance/mcvar.jl:35-41 takes
  * var(batch means); the history-free form closes a batch from the running sums at its two boundaries and updates the mean
  * and the sum of squared deviations of the batch means in place (Welford).  n = nchains * D series, count = batches closed
@@ -785,15 +1155,18 @@ static void ko_ctx_init(ko_target_ctx* c, const klara_desc* d, const ko_layout* 
 }
 
 /* initialize!(pstate, parameter, sampler) — MH.jl:72-85, MALA.jl:76-90, HMC.jl:106-120,
- * SliceSampler.jl:40-48; tuner_state — samplers.jl:29-45 (totproposed starts at tuner.period). */
+ * SliceSampler.jl:40-48; tuner_state — samplers.jl:29-45 (totproposed starts at tuner.period).  SMMALA, RAM, AM: klara_plan.h
+ * sampler_needs_gradient / sampler_step0; the caller sets RAM's factor and AM's covariance and means (ss) to their start values; SMMALA's
+ * metric must be positive definite at every start state (S5). */
 int ko_init(const klara_desc* d, const ko_layout* L, const double* X, double* G, double* LT,
             double* step, int64_t* accepted, int64_t* proposed, int64_t* totproposed,
-            double* da_epsbar, double* da_hbar)
+            double* da_epsbar, double* da_hbar, const ko_sampler_state* ss)
 {
     ko_target_ctx c; ko_ctx_init(&c, d, L);
     const int D = d->ndims;
     if (D > KO_MAXD) return KLARA_ERR_UNSUPPORTED;
-    const int needgrad = d->sampler == KLARA_SAMPLER_MALA || d->sampler == KLARA_SAMPLER_HMC;
+    if (ko_matrix_sampler(d->sampler)) { const int st = ko_matrix_check(d, L, ss); if (st != KLARA_OK) return st; }
+    const int needgrad = d->sampler == KLARA_SAMPLER_MALA || d->sampler == KLARA_SAMPLER_HMC || d->sampler == KLARA_SAMPLER_SMMALA;
     int bad = 0;
     for (int64_t n = 0; n < d->nchains; ++n) {
         double scratch[KO_MAXD];
@@ -808,13 +1181,18 @@ int ko_init(const klara_desc* d, const ko_layout* L, const double* X, double* G,
         const int pooled = d->tuner_mode == KLARA_TUNE_POOLED;
         if (!pooled || n == 0) {
             const int64_t k = pooled ? 0 : n;
-            step[k] = d->sampler == KLARA_SAMPLER_MH ? 1.0
-                    : d->sampler == KLARA_SAMPLER_MALA ? d->driftstep
+            step[k] = (d->sampler == KLARA_SAMPLER_MH || d->sampler == KLARA_SAMPLER_RAM || d->sampler == KLARA_SAMPLER_AM) ? 1.0
+                    : (d->sampler == KLARA_SAMPLER_MALA || d->sampler == KLARA_SAMPLER_SMMALA) ? d->driftstep
                     : d->sampler == KLARA_SAMPLER_HMC ? d->leapstep : NAN;
             accepted[k] = 0; proposed[k] = 0; totproposed[k] = d->period;
             /* tuner_state(parameter, sampler::HMC, tuner::DualAveragingMCTuner) — HMC.jl:124-133 */
             if (d->tuner == KLARA_TUNER_DUAL_AVERAGING && da_epsbar) { da_epsbar[k] = d->da_eps0bar; da_hbar[k] = d->da_h0bar; }
         }
+    }
+    if (!bad && d->sampler == KLARA_SAMPLER_SMMALA) {
+        ko_chain ch = { .cn = { 0, 0, 0, 0 }, .maxsweeps = 0 };
+        for (int64_t n = 0; n < d->nchains; ++n) if (!ko_smmala_state_at(&c, X + n * D, G + n * D, &ch)) bad = 1;
+        ko_counts_out(ss, ch.cn, ch.maxsweeps);
     }
     return bad ? KLARA_ERR_NONFINITE_INIT : KLARA_OK;
 }
@@ -837,15 +1215,35 @@ static void ko_fold(double* sum, double* sumsq, const double* xold, int D, int64
     *held = 0;
 }
 
-/* one transition of one chain; returns accept flag */
+/* the save rule of run(), BasicMCJob.jl:226-231: the 1-based step i = t + 1 is saved as column (i - burnin - 1) / thinning (see ko_run) */
+static void ko_save(const klara_desc* d, int64_t n, int64_t t, const double* x, const double* g, double lt, int64_t* held,
+                    double* hist, int64_t hist_cols, double* hist_lt, double* hist_g)
+{
+    const int D = d->ndims;
+    const int64_t i1 = t + 1;                       /* 1-based step index i of run() */
+    if (i1 > d->burnin && (i1 - d->burnin - 1) % d->thinning == 0 && i1 <= d->nsteps) {
+        const int64_t col = (i1 - d->burnin - 1) / d->thinning;
+        if (held) held[n] += 1;
+        if (hist && col < hist_cols)
+            memcpy(hist + ((size_t)col * (size_t)d->nchains + (size_t)n) * (size_t)D, x, sizeof(double) * (size_t)D);
+        if (hist_lt && col < hist_cols) hist_lt[(size_t)col * (size_t)d->nchains + (size_t)n] = lt;
+        if (hist_g && col < hist_cols)
+            memcpy(hist_g + ((size_t)col * (size_t)d->nchains + (size_t)n) * (size_t)D, g, sizeof(double) * (size_t)D);
+    }
+}
+
+/* one transition of one chain; returns accept flag (ch: the chain's state of SMMALA, RAM and AM, unused by the others) */
 static int ko_transition(const ko_target_ctx* c, uint64_t gchain, uint64_t t, double step, int64_t nleaps,
-                         double* x, double* g, double* lt, int* stuck, double* a_out)
+                         double* x, double* g, double* lt, int* stuck, double* a_out, ko_chain* ch)
 {
     const klara_desc* d = c->d;
     switch (d->sampler) {
     case KLARA_SAMPLER_MH: return ko_mh(c, gchain, t, x, lt);
     case KLARA_SAMPLER_MALA: return ko_mala(c, gchain, t, step, x, g, lt);
     case KLARA_SAMPLER_HMC: return ko_hmc(c, gchain, t, step, nleaps, x, g, lt, a_out);
+    case KLARA_SAMPLER_SMMALA: return ko_smmala(c, gchain, t, step, x, g, lt, ch);
+    case KLARA_SAMPLER_RAM: return ko_ram(c, gchain, t, x, lt, ch, NULL, NULL);
+    case KLARA_SAMPLER_AM: return ko_am(c, gchain, t, x, lt, ch);
     default:
         if (c->L->kind == 3 && d->target == KLARA_TARGET_GAUSS_DIAG && !ko_is_literal()) return ko_slice_diag_delta(c, gchain, t, x, lt, stuck);
         if (c->L->kind == 3 && d->target == KLARA_TARGET_CUSTOM && ko_user_pair && !ko_is_literal()) return ko_slice_pair_delta(c, gchain, t, x, lt, stuck);
@@ -866,16 +1264,21 @@ static int ko_transition(const ko_target_ctx* c, uint64_t gchain, uint64_t t, do
  *                                    running-sum traffic of chains that did not move.)
  *   naccept[n]                       accepted transitions
  *   hist[(col * nchains + n) * D + i] value saved as column `col` (save rule BasicMCJob.jl:226-231)
- * Tuner arrays have nchains entries (per-chain mode) or 1 entry (pooled mode). */
+ * Tuner arrays have nchains entries (per-chain mode) or 1 entry (pooled mode).
+ * ss: what the chains of SMMALA, RAM and AM carry beyond that (ko_sampler_state), NULL for the other samplers; `matrix` below is the one
+ * test, uniform over the call, behind which all of its handling sits. */
 int ko_run(const klara_desc* d, const ko_layout* L, double* X, double* G, double* LT,
            double* step, int64_t* accepted, int64_t* proposed, int64_t* totproposed,
            int64_t t0, int64_t nsteps, uint8_t* accept_out, double* sum, double* sumsq,
            uint64_t* naccept, double* hist, int64_t hist_cols, double* hist_lt, double* hist_g,
-           double* da_epsbar, double* da_hbar, int64_t* held)
+           double* da_epsbar, double* da_hbar, int64_t* held, const ko_sampler_state* ss)
 {
     ko_target_ctx c; ko_ctx_init(&c, d, L);
     const int D = d->ndims;
     if (D > KO_MAXD) return KLARA_ERR_UNSUPPORTED;
+    const int matrix = ko_matrix_sampler(d->sampler);
+    if (matrix) { const int st = ko_matrix_check(d, L, ss); if (st != KLARA_OK) return st; }
+    int64_t cn[4] = { 0, 0, 0, 0 }, maxsweeps = 0;      /* (matrix) counted over the chains of this call: ko_chain.cn */
     const int cnt = ko_cnt(d);
     const int pooled = d->tuner_mode == KLARA_TUNE_POOLED;
     const int da = d->tuner == KLARA_TUNER_DUAL_AVERAGING && d->sampler == KLARA_SAMPLER_HMC;
@@ -887,11 +1290,13 @@ int ko_run(const klara_desc* d, const ko_layout* L, double* X, double* G, double
     int stuck_any = 0;
 
     if (!pooled) {
-#pragma omp parallel for schedule(static) reduction(| : stuck_any)
+#pragma omp parallel for schedule(static) reduction(| : stuck_any) reduction(+ : cn[:4]) reduction(max : maxsweeps)
         for (int64_t n = 0; n < d->nchains; ++n) {
             double* x = X + n * D; double* g = G + n * D;
             ko_tune tn = { step[n], accepted[n], proposed[n], totproposed[n], NAN };
             int stuck = 0;
+            ko_chain ch;
+            if (matrix) ko_chain_begin(&c, ss, n, x, g, &ch);
             for (int64_t s = 0; s < nsteps && !stuck; ++s) {
                 const int64_t t = t0 + s;
                 if (cnt) tn.proposed += 1;
@@ -906,7 +1311,7 @@ int ko_run(const klara_desc* d, const ko_layout* L, double* X, double* G, double
                 const int want_fold = sum && held[n] > 0;
                 if (want_fold) memcpy(xold, x, sizeof(double) * (size_t)D);
                 const int acc = ko_transition(&c, (uint64_t)(d->chain_offset + n), (uint64_t)t,
-                                              tn.step, nl, x, g, &LT[n], &stuck, &a_prob);
+                                              tn.step, nl, x, g, &LT[n], &stuck, &a_prob, &ch);
                 if (stuck) break;
                 if (want_fold && acc) ko_fold(sum + n * D, sumsq + n * D, xold, D, &held[n]);
                 if (da) {                                       /* iterate/HMC.jl:225-249 */
@@ -928,25 +1333,24 @@ int ko_run(const klara_desc* d, const ko_layout* L, double* X, double* G, double
                 else if (cnt && (tn.proposed % d->period) == 0 && t + 1 <= d->da_nadapt) {   /* verbose report block :229-243 */
                     tn.totproposed += tn.proposed; tn.accepted = 0; tn.proposed = 0;
                 }
-                const int64_t i1 = t + 1;                       /* 1-based step index i of run() */
-                if (i1 > d->burnin && (i1 - d->burnin - 1) % d->thinning == 0 && i1 <= d->nsteps) {
-                    const int64_t col = (i1 - d->burnin - 1) / d->thinning;
-                    if (sum) held[n] += 1;
-                    if (hist && col < hist_cols)
-                        memcpy(hist + ((size_t)col * (size_t)d->nchains + (size_t)n) * (size_t)D, x,
-                               sizeof(double) * (size_t)D);
-                    if (hist_lt && col < hist_cols) hist_lt[(size_t)col * (size_t)d->nchains + (size_t)n] = LT[n];
-                    if (hist_g && col < hist_cols)
-                        memcpy(hist_g + ((size_t)col * (size_t)d->nchains + (size_t)n) * (size_t)D, g,
-                               sizeof(double) * (size_t)D);
-                }
+                ko_save(d, n, t, x, g, LT[n], sum ? held : NULL, hist, hist_cols, hist_lt, hist_g);
             }
             step[n] = tn.step; accepted[n] = tn.accepted; proposed[n] = tn.proposed;
             totproposed[n] = tn.totproposed;
             stuck_any |= stuck;
+            if (matrix) {
+                for (int k = 0; k < 4; ++k) cn[k] += ch.cn[k];
+                if (ch.maxsweeps > maxsweeps) maxsweeps = ch.maxsweeps;
+            }
         }
     } else {
         ko_tune tn = { step[0], accepted[0], proposed[0], totproposed[0], NAN };
+        ko_chain* chs = NULL;                                   /* (matrix) every chain's state, for the length of this call */
+        if (matrix) {
+            chs = (ko_chain*)malloc(sizeof(ko_chain) * (size_t)d->nchains);
+            if (!chs) return KLARA_ERR_NOMEM;
+            for (int64_t n = 0; n < d->nchains; ++n) ko_chain_begin(&c, ss, n, X + n * D, G + n * D, &chs[n]);
+        }
         for (int64_t s = 0; s < nsteps && !stuck_any; ++s) {
             const int64_t t = t0 + s;
             if (cnt) tn.proposed += 1;
@@ -959,31 +1363,28 @@ int ko_run(const klara_desc* d, const ko_layout* L, double* X, double* G, double
                 const int want_fold = sum && held[n] > 0;
                 if (want_fold) memcpy(xold, x, sizeof(double) * (size_t)D);
                 const int acc = ko_transition(&c, (uint64_t)(d->chain_offset + n), (uint64_t)t,
-                                              tn.step, d->nleaps, x, g, &LT[n], &stuck, NULL);
+                                              tn.step, d->nleaps, x, g, &LT[n], &stuck, NULL, matrix ? &chs[n] : NULL);
                 stuck_any |= stuck;
                 if (want_fold && acc && !stuck) ko_fold(sum + n * D, sumsq + n * D, xold, D, &held[n]);
                 nacc += acc;
                 if (accept_out) accept_out[s * d->nchains + n] = (uint8_t)acc;
                 if (naccept) naccept[n] += (uint64_t)acc;
-                const int64_t i1 = t + 1;
-                if (i1 > d->burnin && (i1 - d->burnin - 1) % d->thinning == 0 && i1 <= d->nsteps) {
-                    const int64_t col = (i1 - d->burnin - 1) / d->thinning;
-                    if (sum) held[n] += 1;
-                    if (hist && col < hist_cols)
-                        memcpy(hist + ((size_t)col * (size_t)d->nchains + (size_t)n) * (size_t)D, x,
-                               sizeof(double) * (size_t)D);
-                    if (hist_lt && col < hist_cols) hist_lt[(size_t)col * (size_t)d->nchains + (size_t)n] = LT[n];
-                    if (hist_g && col < hist_cols)
-                        memcpy(hist_g + ((size_t)col * (size_t)d->nchains + (size_t)n) * (size_t)D, g,
-                               sizeof(double) * (size_t)D);
-                }
+                ko_save(d, n, t, x, g, LT[n], sum ? held : NULL, hist, hist_cols, hist_lt, hist_g);
             }
             if (cnt) tn.accepted += nacc;
             ko_tuning_block(d, &tn, cnt, d->nchains);
         }
         step[0] = tn.step; accepted[0] = tn.accepted; proposed[0] = tn.proposed;
         totproposed[0] = tn.totproposed;
+        if (matrix) {
+            for (int64_t n = 0; n < d->nchains; ++n) {
+                for (int k = 0; k < 4; ++k) cn[k] += chs[n].cn[k];
+                if (chs[n].maxsweeps > maxsweeps) maxsweeps = chs[n].maxsweeps;
+            }
+            free(chs);
+        }
     }
+    if (matrix) ko_counts_out(ss, cn, maxsweeps);
     return stuck_any ? KLARA_ERR_SLICE_STUCK : KLARA_OK;
 }
 
@@ -1086,3 +1487,46 @@ int ko_eval_target(const klara_desc* d, const ko_layout* L, const double* x, dou
     *lt = ko_uptograd(&c, x, g, scratch);
     return KLARA_OK;
 }
+
+/* ---- pieces of SMMALA, RAM and AM for the host tests (ko_smmala_metric, ko_ram_coef, ko_ram_update_c, ko_am_selector, ko_am_covariance
+ * and ko_am_factor above are exported as they stand) */
+/* one RAM transition of one chain (x, lt, its packed factor S), which also returns what it drew and formed: z (E) and c */
+int ko_ram_step(const klara_desc* d, const ko_layout* L, uint64_t chain, uint64_t t, double* x, double* lt, double* S, double* z, double* c_out)
+{
+    ko_target_ctx c; ko_ctx_init(&c, d, L);
+    if (L->E > KO_MAXE || d->ndims > L->E || d->ndims < 1) return -1;
+    ko_chain ch = { .S = S };
+    return ko_ram(&c, chain, t, x, lt, &ch, z, c_out);
+}
+/* C = L^-T of a D x D row-major SPD matrix G (tests: C C' = inv(G)); returns 0 when G does not factor */
+int ko_smmala_inv_chol_t(const double* G, int D, double* Cout)
+{
+    const int E = D;
+    double gm[KO_MAXNT];
+    ko_smmala_state s;
+    if (D > KO_MAXE) return 0;
+    for (int a = 0; a < D; ++a) for (int b = a; b < D; ++b) gm[ko_tri(a, b, E)] = G[a * D + b];
+    /* ko_smmala_factor adds inv_lambda on the diagonal: 0 here */
+    const int pd = ko_smmala_factor(gm, D, E, 0.0, &s);
+    for (int j = 0; j < D; ++j) {
+        double e[KO_MAXE], col[KO_MAXE];
+        for (int i = 0; i < D; ++i) e[i] = i == j ? 1.0 : 0.0;
+        ko_smmala_solve_lt(&s, E, e, col);
+        for (int i = 0; i < D; ++i) Cout[i * D + j] = col[i];
+    }
+    return pd;
+}
+/* klara_softabs.h's pieces */
+double ko_softabs_f(double lam, double a) { return ksa_f(lam, a); }
+/* softabs of a D x D row-major symmetric matrix H (upper triangle read), padded to E as the kernels hold it; T out (D x D, mirrored); returns the sweeps (-1: not transformed) */
+int ko_softabs(const double* H, int D, int E, double a, double* T)
+{
+    double gm[KO_MAXNT];
+    if (D > E || E > KO_MAXE) return -2;
+    for (int i = 0; i < E; ++i) for (int j = i; j < E; ++j) gm[ko_tri(i, j, E)] = (j < D) ? H[i * D + j] : 0.0;
+    double Q[KO_MAXE * KO_MAXE];
+    const int sw = ksa_softabs_tri(gm, D, E, a, Q, 1);
+    for (int i = 0; i < D; ++i) for (int j = i; j < D; ++j) { T[i * D + j] = gm[ko_tri(i, j, E)]; T[j * D + i] = gm[ko_tri(i, j, E)]; }
+    return sw;
+}
+void ko_softabs_limits(double* out) { out[0] = (double)KSA_MAX_SWEEPS; out[1] = KSA_TOL2; out[2] = KSA_SMALL; out[3] = KSA_BIG; }

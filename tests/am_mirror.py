@@ -5,7 +5,7 @@ src/stats/covariance.jl:6-19 and recursive_mean! of src/stats/mean.jl:5, taken l
 `Hermitian(C)`, `MixtureModel([MvNormal(x, corescale * C), MvNormal(x, sqrtminorscale)], [1 - c, c])` with numpy.linalg.cholesky where the
 MvNormal constructor factors its covariance (it raises where that throws), the mixture's logpdf by log-sum-exp at both centres, and the ratio
 `(r - q(x -> x')) + q(x' -> x)` of :100-106.  None of the library's deviations A1-A5 is taken over, and no code is shared
-with tests/am_ref.c or the kernels.  The draws are the job's Philox stream, read through the oracle library: ko_transition_normals (D normals
+with oracle/klara_oracle.c ko_am or the kernels.  The draws are the job's Philox stream, read through the oracle library: ko_transition_normals (D normals
 and the accept uniform of a transition) and ko_stream_block, whose words (z, w) of the accept block choose the mixture component.
 """
 import ctypes as C

@@ -2,8 +2,8 @@
 
 `build(src, ndims, chunk)` compiles, with g++ -O2 -std=c++17 -ffp-contract=off, the same user text between the same prelude and glue
 (klara.jl_amd/csrc/klara_autodiff.h) the run-time compiler puts around it on the device, and exports klara_user_logtarget,
-klara_user_gradlogtarget and (marker value 2) klara_user_tensorlogtarget with C linkage — the closures the CPU oracle and tests/smmala_ref.c
-take as function pointers.  The gradient is swept `chunk` directions at a time (default 1: invariant A2 of the header makes the width
+klara_user_gradlogtarget and (marker value 2) klara_user_tensorlogtarget with C linkage — the closures the CPU oracle takes as function
+pointers.  The gradient is swept `chunk` directions at a time (default 1: invariant A2 of the header makes the width
 immaterial); klara_ref_dual_value is the value a dual carries through the user's function (invariant A1: the double instantiation's bits).
 
 `AdOracleJob` / `AdSmmalaRefJob` are oracle_ffi.OracleJob / smmala_ref.SmmalaRefJob on such a source: their constructors compile a source
@@ -12,9 +12,6 @@ first evaluation."""
 from __future__ import annotations
 
 import ctypes as C
-import hashlib
-import os
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -58,23 +55,14 @@ double klara_ref_dual_value(%(sig)s)
 
 def build(src: str, ndims: int, chunk: int = 1, chunk2: int = 1):
     """ctypes library of the host build; `chunk` directions per gradient sweep, `chunk2` inner directions per Hessian sweep"""
-    hdr = (CSRC / "klara_autodiff.h").read_bytes() + (CSRC / "detmath.h").read_bytes() + (CSRC / "klara_custom_compose.h").read_bytes()
-    key = hashlib.sha1(hdr + f"{ndims} {chunk} {chunk2}\n{src}{_GLUE}".encode()).hexdigest()[:16]
+    key = (int(ndims), int(chunk), int(chunk2), src)
     if key in _libs:
         return _libs[key]
-    out = ROOT / "build" / "autodiff_ref"
-    out.mkdir(parents=True, exist_ok=True)
-    so, cpp = out / f"ad_{key}.so", out / f"ad_{key}.cpp"
-    if not so.exists():
-        cpp.write_text(f'#include "klara_autodiff.h"\n#define KLARA_D {int(ndims)}\n#define KLARA_USER_FN\n#define KLARA_SMMALA 1\n'
-                       f'#line 1 "klara_user_target"\n{src}\n'
-                       f'#undef KLARA_USER_AUTODIFF_CHUNK\n#define KLARA_USER_AUTODIFF_CHUNK {int(chunk)}\n#define KLARA_AD_CHUNK2 {int(chunk2)}\n' + _GLUE)
-        tmp = out / f".ad_{key}.{os.getpid()}.so"
-        r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", str(CSRC), "-o", str(tmp), str(cpp)],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("autodiff source did not compile on the host:\n" + r.stderr)
-        tmp.replace(so)
+    text = (f'#include "klara_autodiff.h"\n#define KLARA_D {int(ndims)}\n#define KLARA_USER_FN\n#define KLARA_SMMALA 1\n'
+            f'#line 1 "klara_user_target"\n{src}\n'
+            f'#undef KLARA_USER_AUTODIFF_CHUNK\n#define KLARA_USER_AUTODIFF_CHUNK {int(chunk)}\n#define KLARA_AD_CHUNK2 {int(chunk2)}\n' + _GLUE)
+    so = O.build_c("autodiff_ref", ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", str(CSRC)], text=text, text_suffix=".cpp",
+                   hashed=[CSRC / "klara_autodiff.h", CSRC / "detmath.h", CSRC / "klara_custom_compose.h"], libs=(), cc="g++")
     lib = C.CDLL(str(so))
     dp = C.POINTER(C.c_double)
     for name in ("klara_user_logtarget", "klara_ref_dual_value"):
@@ -162,7 +150,7 @@ class AdSmmalaRefJob(smmala_ref.SmmalaRefJob):
         self.ad = build(custom_src, self.D, chunk)
         lt, grad = _pointers(self.ad)
         self._user = (self.ad, lt, grad, None)
-        self._tensor = C.cast(self.ad.klara_user_tensorlogtarget, C.c_void_p).value
+        self._tensor = C.cast(self.ad.klara_user_tensorlogtarget, C.c_void_p)
 
 
 def ref_job(case, layout=None, chain_offset=0, nchains=None, want_hist=False):

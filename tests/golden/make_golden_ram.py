@@ -1,4 +1,4 @@
-"""Regenerates the RAM golden vectors under tests/golden/ from the CPU reference (tests/ram_ref.c).
+"""Regenerates the RAM golden vectors under tests/golden/ from the CPU reference (oracle/klara_oracle.c ko_ram).
 
     python tests/golden/make_golden_ram.py
 

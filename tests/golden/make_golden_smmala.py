@@ -1,4 +1,4 @@
-"""Regenerates the SMMALA golden vectors under tests/golden/ from the CPU reference (tests/smmala_ref.c).
+"""Regenerates the SMMALA golden vectors under tests/golden/ from the CPU reference (oracle/klara_oracle.c ko_smmala).
 
     python tests/golden/make_golden_smmala.py
 

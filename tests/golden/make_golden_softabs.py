@@ -1,5 +1,5 @@
 """Regenerates the golden vectors of the SMMALA sampler with the softabs transform under tests/golden/ from the CPU reference
-(tests/softabs_ref.c).
+(oracle/klara_oracle.c ko_smmala).
 
     python tests/golden/make_golden_softabs.py
 

@@ -24,6 +24,39 @@ class KoLayout(C.Structure):
     _fields_ = [("kind", C.c_int32), ("G", C.c_int32), ("E", C.c_int32)]
 
 
+class KoSamplerState(C.Structure):
+    """klara_oracle.c ko_sampler_state: what the chains of RAM and AM carry beyond x, g and lt, and the counters of a call"""
+    _fields_ = [("ram_S", C.c_void_p), ("ram_skipped", C.c_void_p), ("am_C", C.c_void_p), ("am_mean", C.c_void_p), ("am_mean2", C.c_void_p),
+                ("am_fallbacks", C.c_void_p), ("softabs_sweeps", C.c_void_p)]
+
+
+CSRC = ROOT / "klara.jl_amd" / "csrc"
+INC = ["-I", str(CSRC), "-I", str(ROOT / "include")]
+
+
+def build_c(name: str, flags, sources=(), hashed=(), text=None, text_suffix=".c", libs=("-lm",), cc="gcc", shared=True) -> Path:
+    """The one builder of the C helpers of the tests: `cc *flags -o <out> *sources [<text>] *libs` into the git-ignored build/<name>/, once per
+    content of the sources, of `hashed` (paths: the headers a source includes) and of `text` (a generated source, written beside the output),
+    and per command line.  Returns the shared object, or with shared=False the program."""
+    parts = [Path(p).read_bytes() for p in (*sources, *hashed)] + [(text or "").encode(), " ".join([cc, *flags, *libs]).encode()]
+    key = hashlib.sha1(b"\0".join(parts)).hexdigest()[:16]
+    out = ROOT / "build" / name
+    out.mkdir(parents=True, exist_ok=True)
+    target = out / (f"{name}_{key}.so" if shared else f"{name}_{key}")
+    if not target.exists():
+        srcs = [str(s) for s in sources]
+        if text is not None:
+            gen = out / f"{name}_{key}{text_suffix}"
+            gen.write_text(text)
+            srcs.append(str(gen))
+        tmp = out / f".{target.name}.{os.getpid()}"
+        r = subprocess.run([cc, *flags, "-o", str(tmp), *srcs, *libs], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"{name} did not compile:\n" + r.stderr)
+        tmp.replace(target)
+    return target
+
+
 _lib = None
 
 
@@ -32,19 +65,33 @@ def load() -> C.CDLL:
     if _lib is not None:
         return _lib
     srcs = [ROOT / "oracle" / "klara_oracle.c", ROOT / "include" / "klara_hip.h",
-            ROOT / "klara.jl_amd" / "csrc" / "detmath.h"]
+            ROOT / "klara.jl_amd" / "csrc" / "detmath.h", ROOT / "klara.jl_amd" / "csrc" / "klara_softabs.h"]
     if not SO.exists() or any(s.stat().st_mtime > SO.stat().st_mtime for s in srcs):
         r = subprocess.run(["make", "-C", str(ROOT / "oracle")], capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("oracle build failed:\n" + r.stdout + r.stderr)
     lib = C.CDLL(str(SO))
     vp = C.c_void_p
-    lib.ko_init.argtypes = [C.POINTER(L.KlaraDesc), C.POINTER(KoLayout)] + [vp] * 9
+    desc, lay, ss = C.POINTER(L.KlaraDesc), C.POINTER(KoLayout), C.POINTER(KoSamplerState)
+    lib.ko_init.argtypes = [desc, lay] + [vp] * 9 + [ss]
     lib.ko_init.restype = C.c_int
     lib.ko_init_state_normal.argtypes = [C.POINTER(L.KlaraDesc), vp]
     lib.ko_init_state_normal.restype = None
-    lib.ko_run.argtypes = [C.POINTER(L.KlaraDesc), C.POINTER(KoLayout)] + [vp] * 7 + [C.c_int64, C.c_int64] + [vp] * 5 + [C.c_int64, vp, vp, vp, vp, vp]
+    lib.ko_run.argtypes = [desc, lay] + [vp] * 7 + [C.c_int64, C.c_int64] + [vp] * 5 + [C.c_int64, vp, vp, vp, vp, vp, ss]
     lib.ko_run.restype = C.c_int
+    # pieces of SMMALA (and klara_softabs.h), RAM and AM for the host tests
+    lib.ko_set_custom_tensor.argtypes = [vp]; lib.ko_set_custom_tensor.restype = None
+    lib.ko_smmala_metric.argtypes = [desc, lay, vp, vp]; lib.ko_smmala_metric.restype = None
+    lib.ko_smmala_inv_chol_t.argtypes = [vp, C.c_int, vp]; lib.ko_smmala_inv_chol_t.restype = C.c_int
+    lib.ko_softabs_f.argtypes = [C.c_double, C.c_double]; lib.ko_softabs_f.restype = C.c_double
+    lib.ko_softabs.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp]; lib.ko_softabs.restype = C.c_int
+    lib.ko_softabs_limits.argtypes = [vp]; lib.ko_softabs_limits.restype = None
+    lib.ko_ram_coef.argtypes = [C.c_int, C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double]; lib.ko_ram_coef.restype = C.c_double
+    lib.ko_ram_update_c.argtypes = [C.c_int, C.c_double, C.c_double, vp, vp]; lib.ko_ram_update_c.restype = C.c_int
+    lib.ko_ram_step.argtypes = [desc, lay, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp]; lib.ko_ram_step.restype = C.c_int
+    lib.ko_am_selector.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]; lib.ko_am_selector.restype = C.c_double
+    lib.ko_am_covariance.argtypes = [C.c_int, C.c_int64, vp, vp, vp, vp]; lib.ko_am_covariance.restype = None
+    lib.ko_am_factor.argtypes = [C.c_int, C.c_double, vp, vp]; lib.ko_am_factor.restype = C.c_int
     lib.ko_philox_block.argtypes = [vp, vp, vp]
     lib.ko_stream_block.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, vp]
     lib.ko_math.argtypes = [C.c_int, C.c_int64, vp, vp, vp]
@@ -84,21 +131,15 @@ _user_libs = {}
 def compile_user_target(src: str, ndims: int):
     """Host form of a user-defined target (KLARA_TARGET_CUSTOM): the same C text the product hands to hiprtc, compiled by
     gcc with the same arithmetic contract (-ffp-contract=off, detmath.h for kd_*).  Returns (lib, lt_ptr, grad_ptr|None)."""
-    key = hashlib.sha1(f"v2 {ndims}\n{src}".encode()).hexdigest()[:16]
+    key = (int(ndims), src)
     if key in _user_libs:
         return _user_libs[key]
-    out = ROOT / "oracle" / "_user"
-    out.mkdir(exist_ok=True)
-    so, c = out / f"user_{key}.so", out / f"user_{key}.c"
-    if not so.exists():
-        # (a likelihood + prior source without gradient closures — an MH / slice job — gets no composed gradient, as on the device)
-        nograd = "#define KLARA_CUSTOM_NOGRAD 1\n" if ("KLARA_USER_LIKELIHOOD_PRIOR" in src and "klara_user_gradloglikelihood" not in src) else ""
-        c.write_text(f'#include "detmath.h"\n#define KLARA_D {int(ndims)}\n#define KLARA_USER_FN\n{nograd}#line 1 "klara_user_target"\n{src}\n'
-                     '#line 1 "klara_custom_glue"\n#include "klara_custom_compose.h"\n')      # (likelihood + prior form: same composition as the device)
-        r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared", "-I", str(ROOT / "klara.jl_amd" / "csrc"),
-                            "-o", str(so), str(c), "-lm"], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("user target did not compile on the host:\n" + r.stderr)
+    # (a likelihood + prior source without gradient closures — an MH / slice job — gets no composed gradient, as on the device)
+    nograd = "#define KLARA_CUSTOM_NOGRAD 1\n" if ("KLARA_USER_LIKELIHOOD_PRIOR" in src and "klara_user_gradloglikelihood" not in src) else ""
+    text = (f'#include "detmath.h"\n#define KLARA_D {int(ndims)}\n#define KLARA_USER_FN\n{nograd}#line 1 "klara_user_target"\n{src}\n'
+            '#line 1 "klara_custom_glue"\n#include "klara_custom_compose.h"\n')      # (likelihood + prior form: same composition as the device)
+    so = build_c("user_target", ["-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared", "-I", str(CSRC)], text=text,
+                 hashed=[CSRC / "detmath.h", CSRC / "detmath_tables.h", CSRC / "klara_custom_compose.h"])
     lib = C.CDLL(str(so))
     if "KLARA_USER_PAIR_TARGET" in src and "KLARA_PAIR_AS_WHOLE" not in src:        # pair closure (klara_user_pair): third entry; no whole-vector closures
         _user_libs[key] = (lib, None, None, C.cast(lib.klara_user_pair, C.c_void_p))
@@ -258,12 +299,14 @@ class OracleJob:
         if hier_Y is not None:
             d.hier_nunits, d.hier_ntimes = int(np.shape(hier_Y)[0]), int(np.shape(hier_Y)[1])
         d.hier_prior_prec, d.hier_gamma_a, d.hier_gamma_b = float(hier_prior_prec), float(hier_gamma_a), float(hier_gamma_b)
-        self._user = None
+        self._user = self._tensor = None
         if custom_src is not None:
             # (a pair closure the pair-transposed kernels do not serve runs as a whole-vector closure: klara_plan.h pair_as_whole, klara_custom_compose.h)
             if "KLARA_USER_PAIR_TARGET" in custom_src and (self.D < 17 or (int(sampler) == L.SAMPLER_SLICE and "KLARA_PAIR_SLICE_AS_WHOLE" in os.environ)):
                 custom_src = "#define KLARA_PAIR_AS_WHOLE 1\n" + custom_src
             self._user = compile_user_target(custom_src, self.D)
+            if hasattr(self._user[0], "klara_user_tensorlogtarget"):      # SMMALA's metric
+                self._tensor = C.cast(self._user[0].klara_user_tensorlogtarget, C.c_void_p)
             if custom_data is not None and np.size(custom_data):
                 d.custom_data = ptr(custom_data); d.custom_ndata = int(np.size(custom_data))
         d.seed = int(seed)
@@ -310,6 +353,12 @@ class OracleJob:
         if self._user is not None:             # (process-global in the oracle: bound before every call that evaluates the target)
             self.lib.ko_set_custom_target(self._user[1], self._user[2])
             self.lib.ko_set_custom_pair_target(self._user[3])
+            self.lib.ko_set_custom_tensor(self._tensor)
+
+    def _sampler_state(self):
+        """what ko_init / ko_run take as ko_sampler_state: nothing, but for the samplers that carry a matrix per chain (the subclasses of
+        ram_ref, am_ref, softabs_ref)"""
+        return None
 
     def set_state(self, x) -> int:
         self.X[...] = _f64(x).reshape(self.N, self.D)
@@ -341,7 +390,7 @@ class OracleJob:
         return self.lib.ko_init(C.byref(self.desc), C.byref(self.layout), self._p(self.X), self._p(self.G),
                                 self._p(self.LT), self._p(self.step), self._p(self.accepted),
                                 self._p(self.proposed), self._p(self.totproposed), self._p(self.da_epsbar),
-                                self._p(self.da_hbar))
+                                self._p(self.da_hbar), self._sampler_state())
 
     def run(self, nsteps: int) -> int:
         acc = np.zeros((nsteps, self.N), np.uint8) if self.want_accept else None
@@ -351,7 +400,7 @@ class OracleJob:
                              self._p(self.totproposed), self.t, int(nsteps), self._p(acc), self._p(self._sum),
                              self._p(self._sumsq), self._p(self.naccept), self._p(self.hist), self.hist_cols,
                              self._p(self.hist_lt), self._p(self.hist_g), self._p(self.da_epsbar), self._p(self.da_hbar),
-                             self._p(self.held))
+                             self._p(self.held), self._sampler_state())
         self.t += int(nsteps)
         if acc is not None:
             self.accept = np.concatenate([self.accept, acc], axis=0)

@@ -3,7 +3,7 @@
 iterate!(job, RAM, Multivariate) of src/samplers/iterate/RAM.jl:65-130 and the sampler state of src/samplers/RAM.jl:147-163, 201-211, taken
 literally: `S * (eye + z z' / dot(z, z) * eta * (min(1, exp(ratio)) - targetrate)) * S'` and numpy.linalg.cholesky for
 `ctranspose(chol(Hermitian(SST)))`, `count^(-gamma)` as a power.  None of the library's deviations R1-R4 is taken
-over, and no code is shared with tests/ram_ref.c or the kernels.  The draws are the job's Philox stream, read through the oracle library's
+over, and no code is shared with oracle/klara_oracle.c ko_ram or the kernels.  The draws are the job's Philox stream, read through the oracle library's
 ko_transition_normals (D normals and the accept uniform of a transition).
 """
 import ctypes as C

@@ -2,7 +2,7 @@
 
 iterate!(job, SMMALA, Multivariate) of src/samplers/iterate/SMMALA.jl:107-221 and the initial sampler state of src/samplers/SMMALA.jl:139-181,
 with numpy.linalg for inv / logdet / the factorisation, the metric of doc/examples/swiss/SMMALA/analytical.jl:20-23, and the stream,
-the log-target and the gradient of tests/numpy_mirror.py.  It shares no code with tests/smmala_ref.c or the kernels.  The one
+the log-target and the gradient of tests/numpy_mirror.py.  It shares no code with oracle/klara_oracle.c ko_smmala or the kernels.  The one
 deviation it takes over from the library is the one that changes the draws (SMMALA deviation 1): the proposal
 factor is C = L^-T with G = L L' (numpy.linalg.cholesky) instead of chol(inv(G))'.  Everything else — logdet(step * inv(G)),
 dot(d, G d) / step — is the Julia expression.

@@ -1,4 +1,4 @@
-"""The AM sampler without a GPU: the CPU reference (tests/am_ref.c) against the literal NumPy restatement of the Julia source
+"""The AM sampler without a GPU: the CPU reference (oracle/klara_oracle.c ko_am) against the literal NumPy restatement of the Julia source
 (tests/am_mirror.py), deviation A1 case by case, the fallback of A2 / A3, the descriptor mapping and refusals of the C ABI, the Python API, the
 Julia binding's mapping, a run of the reference under the host sanitizers, and whether the sampler learns its target's covariance."""
 import re
@@ -12,12 +12,13 @@ import am_cases as AC
 import am_ref as AR
 import cases
 import klara_jl_amd as K
+import oracle_ffi as O
 import smmala_cases as SC
 from klara_jl_amd import _lib as L
 
 ROOT = Path(__file__).resolve().parent.parent
 
-# Relative bounds, max |a - a_ref| / max |a_ref| per chain, between tests/am_ref.c and the literal restatement over the cases of AC.ALL, 8 chains each:
+# Relative bounds, max |a - a_ref| / max |a_ref| per chain, between oracle/klara_oracle.c ko_am and the literal restatement over the cases of AC.ALL, 8 chains each:
 # twice the largest difference measured.  The covariance: 3.04e-14 measured (swiss_example: 30 adaptive transitions of a recursion whose every step
 # rounds three rank-one updates in the same order on both sides, but from states that the two sides' factorisations and products L z have moved apart by
 # an ulp or two); RAM's comparable figure is 2.4e-14.  The running means: 1.07e-14 measured (swiss_example).
@@ -67,45 +68,45 @@ def test_selector_is_the_unused_half_of_the_accept_block():
     """the reference's selector (detmath.h: kd_uniform_zw of block slot ceil(D / 2)) is the restatement's (the oracle's ko_stream_block, words z and w),
     strictly inside (0, 1); c = 0 therefore always picks the core component (w1 = 1.0)"""
     import am_mirror as AMM
-    lib = AR.load()
+    lib = O.load()
     us = []
     for d in range(1, 9):
         for chain in (0, 5, 1 << 33):
             for t in (0, 1, 77):
-                u = lib.ar_selector(20260927, chain, t, d)
+                u = lib.ko_am_selector(20260927, chain, t, d)
                 assert u == AMM.selector(20260927, chain, t, d)
                 us.append(u)
     assert 0.0 < min(us) and max(us) < 1.0 and len(set(us)) == 4 * 9         # (D = 2 j - 1 and 2 j share block slot j)
 
 
 def test_covariance_update_is_the_empirical_covariance_recursion():
-    """ar_covariance on exact data: with C = cov(x_1 .. x_k) (k >= 2 samples, normalised by k - 1), lastmean and secondlastmean the means of k + 1 and k
+    """ko_am_covariance on exact data: with C = cov(x_1 .. x_k) (k >= 2 samples, normalised by k - 1), lastmean and secondlastmean the means of k + 1 and k
     values as iterate/AM.jl keeps them, the update gives the reference's formula entry for entry (formed here in NumPy with the full matrix)"""
-    lib = AR.load()
+    lib = O.load()
     rng = np.random.default_rng(5)
     for d in (1, 3, 8):
         for k in (1, 2, 7):
             x, m, m2 = rng.standard_normal(d), rng.standard_normal(d), rng.standard_normal(d)
             A = rng.standard_normal((d, d)); C0 = A @ A.T
             P = AR.pack(C0[None])[0].copy()
-            lib.ar_covariance(d, k, x.ctypes.data, m.ctypes.data, m2.ctypes.data, P.ctypes.data)
+            lib.ko_am_covariance(d, k, x.ctypes.data, m.ctypes.data, m2.ctypes.data, P.ctypes.data)
             want = ((k - 1) * C0 + np.outer(x, x) + np.outer(-(k + 1) * m, m) + np.outer(k * m2, m2)) / k
             got = AR.unpack(P[None], d)[0]
             assert np.array_equal(np.triu(got), np.triu(want)), (d, k)
 
 
 def test_factor_is_the_cholesky_factor_or_refuses():
-    lib = AR.load()
+    lib = O.load()
     rng = np.random.default_rng(6)
     for d in (1, 2, 5, 8):
         A = rng.standard_normal((d, d)); Cm = A @ A.T + 0.1 * np.eye(d)
         out = np.zeros(d * (d + 1) // 2)
-        assert lib.ar_factor(d, 1.7, AR.pack(Cm[None])[0].ctypes.data, out.ctypes.data) == 1
+        assert lib.ko_am_factor(d, 1.7, AR.pack(Cm[None])[0].ctypes.data, out.ctypes.data) == 1
         Lf = np.tril(AR.unpack(out[None], d)[0])
         np.testing.assert_allclose(Lf, np.linalg.cholesky(1.7 * Cm), rtol=1e-12, atol=1e-14)
     for bad in (np.zeros((3, 3)), -np.eye(3), np.full((3, 3), np.nan), np.diag([1.0, np.inf, 1.0]), np.ones((3, 3))):
         out = np.zeros(6)
-        assert lib.ar_factor(3, 1.0, AR.pack(bad[None])[0].ctypes.data, out.ctypes.data) == 0
+        assert lib.ko_am_factor(3, 1.0, AR.pack(bad[None])[0].ctypes.data, out.ctypes.data) == 0
 
 
 def test_t0_2_falls_back_until_the_samples_span_the_space():
@@ -343,7 +344,7 @@ def test_julia_binding_maps_am():
 
 
 def test_reference_runs_clean_under_the_host_sanitizers():
-    """tests/am_ref.c with its own main (one small t0 = 2 job, so that the fallback path runs), built with -fsanitize=address,undefined and run as a
+    """oracle/klara_oracle.c with the main of tests/am_sanitizer_main.c (one small t0 = 2 job, so that the fallback path runs), built with -fsanitize=address,undefined and run as a
     stand-alone program: no report, exit status 0"""
     exe = AR.sanitizer_program()
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)

@@ -1,4 +1,4 @@
-"""The AM kernels on the GPU: bit for bit against the CPU reference (tests/am_ref.c) — the covariances, the running means and the fallback count
+"""The AM kernels on the GPU: bit for bit against the CPU reference (oracle/klara_oracle.c ko_am) — the covariances, the running means and the fallback count
 included —, launch-length and sharding invariance, runs split around t0, klara_reset, the getter's refusals.  Small shapes: 96 - 131 chains (a last
 wavefront with idle lanes), 30 - 40 transitions with t0 in {2, 5, 10}, so that every run has transitions before, at and after t0."""
 import numpy as np

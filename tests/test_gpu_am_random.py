@@ -1,4 +1,4 @@
-"""The AM kernels over the random jobs of am_cases.random_case: bit for bit against the CPU reference (tests/am_ref.c) at every D in 1 .. 8 (E = 2 / 4 / 8
+"""The AM kernels over the random jobs of am_cases.random_case: bit for bit against the CPU reference (oracle/klara_oracle.c ko_am) at every D in 1 .. 8 (E = 2 / 4 / 8
 with and without padding elements), logistic and user-defined targets, both sides of the 64-row edge of the row split, chain counts around one
 wavefront and one workgroup, every kernel MODE, monitor word, launch length, split run and shard offset, t0 from 2 on, c in {0, 0.05, 0.5} and both
 scales; and one job per precompiled (E, MODE) instantiation.  It follows tests/test_gpu_matrix_samplers.py."""

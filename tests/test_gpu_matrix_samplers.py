@@ -1,5 +1,5 @@
 """The samplers that carry a per-chain matrix in registers — SMMALA, SMMALA with the softabs transform, RAM — over the random jobs of
-tests/matrix_sampler_random.py: bit for bit against the CPU references (tests/smmala_ref.c, tests/softabs_ref.c, tests/ram_ref.c) at every D in 1 .. 8
+tests/matrix_sampler_random.py: bit for bit against the CPU oracle (oracle/klara_oracle.c: ko_smmala, ko_ram) at every D in 1 .. 8
 (E = 2 / 4 / 8 with and without padding elements), both sides of the 64-row edge of the row split, chain counts around one wavefront and one workgroup,
 every tuner, monitor word, launch length and shard offset; one job per precompiled (sampler, E, MODE) instantiation; and launch-length, sharding and
 split-run invariance on random jobs.  tests/test_matrix_samplers_host.py holds the references to the NumPy restatements on the same seeds."""

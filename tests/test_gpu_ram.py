@@ -1,4 +1,4 @@
-"""The RAM kernels on the GPU: bit for bit against the CPU reference (tests/ram_ref.c) — the factors included —, launch-length and sharding
+"""The RAM kernels on the GPU: bit for bit against the CPU reference (oracle/klara_oracle.c ko_ram) — the factors included —, launch-length and sharding
 invariance, klara_reset, the factor round trip, refusals, and a check that needs no reference: the factor learns the target's covariance shape
 at the target acceptance rate."""
 from pathlib import Path

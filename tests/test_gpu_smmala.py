@@ -1,4 +1,4 @@
-"""The SMMALA kernels on the GPU: bit for bit against the CPU reference (tests/smmala_ref.c), launch-length and sharding invariance,
+"""The SMMALA kernels on the GPU: bit for bit against the CPU reference (oracle/klara_oracle.c ko_smmala), launch-length and sharding invariance,
 klara_reset, the pooled tuner, and a posterior check against the MALA kernel that needs no reference."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The SMMALA kernels with the softabs transform of the metric on the GPU: bit for bit against the CPU reference (tests/softabs_ref.c),
+"""The SMMALA kernels with the softabs transform of the metric on the GPU: bit for bit against the CPU reference (oracle/klara_oracle.c ko_smmala),
 launch-length, split-run and sharding invariance (a chain does not depend on its wavefront neighbours), non-finite metrics, the two routes to the
 BivariateNormal example, and a posterior check against the MALA kernel that needs no reference."""
 from pathlib import Path

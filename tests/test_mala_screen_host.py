@@ -18,9 +18,12 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import oracle_ffi as O
+
 ROOT = Path(__file__).resolve().parent.parent
 SRC = Path(__file__).resolve().parent / "mala_screen_ref.c"
 INC = ["-I", str(ROOT / "klara.jl_amd" / "csrc"), "-I", str(ROOT / "include")]
+HDRS = [O.CSRC / "klara_mala_screen.h", O.CSRC / "detmath.h", O.CSRC / "detmath_tables.h"]
 GUARD = -31.2                                   # KD_LOG_UMIN_GUARD: layouts without a padding pair (D = 103, 104) have no accept draw in hand
 LG_HI, LG_LO = float(np.log1p(-2.0 ** -45)), float(np.log(2.0 ** -45))
 H_MIN, H_MAX = 2.0 ** -6, 2.0                   # the step range the bound is proven for
@@ -28,11 +31,8 @@ dp = C.POINTER(C.c_double)
 
 
 @pytest.fixture(scope="module")
-def lib(tmp_path_factory):
-    so = tmp_path_factory.mktemp("mala_screen") / "mala_screen_ref.so"
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared", *INC, "-o", str(so), str(SRC), "-lm"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, "tests/mala_screen_ref.c did not compile:\n" + r.stderr
+def lib():
+    so = O.build_c("mala_screen_ref", ["-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared", *INC], sources=[SRC], hashed=HDRS)
     lb = C.CDLL(str(so))
     lb.ms_consts.argtypes = [C.c_double, C.c_double, C.c_double, C.c_void_p]
     lb.ms_consts.restype = C.c_int

@@ -1,5 +1,5 @@
-"""The random jobs of tests/matrix_sampler_random.py without a GPU: every committed seed runs on its C reference (tests/smmala_ref.c,
-tests/softabs_ref.c, tests/ram_ref.c), the references agree with the NumPy restatements (tests/smmala_mirror.py, tests/ram_mirror.py) on the first
+"""The random jobs of tests/matrix_sampler_random.py without a GPU: every committed seed runs on the CPU oracle (oracle/klara_oracle.c:
+ko_smmala, ko_ram), the oracle agrees with the NumPy restatements (tests/smmala_mirror.py, tests/ram_mirror.py) on the first
 4 chains of every seed, the seeds reach every kernel instantiation and every edge they are there for (the ledger), and the jobs both accept and reject.
 profiles/matrix_sampler_sweep.txt records the ledger and the acceptance fractions printed here."""
 import functools

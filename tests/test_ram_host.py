@@ -1,4 +1,4 @@
-"""The RAM sampler without a GPU: the CPU reference (tests/ram_ref.c) against the literal NumPy restatement of the Julia source
+"""The RAM sampler without a GPU: the CPU reference (oracle/klara_oracle.c ko_ram) against the literal NumPy restatement of the Julia source
 (tests/ram_mirror.py), the algebra of the factor update, the descriptor mapping and refusals of the C ABI, the Python API and the Julia
 binding's mapping."""
 import re
@@ -9,6 +9,7 @@ import pytest
 
 import cases
 import klara_jl_amd as K
+import oracle_ffi as O
 import ram_cases as RC
 import ram_ref as RR
 import smmala_cases as SC
@@ -16,7 +17,7 @@ from klara_jl_amd import _lib as L
 
 ROOT = Path(__file__).resolve().parent.parent
 
-# Relative bound on a factor, max |S - S_ref| / max |S_ref| per chain: 100 x the largest difference measured between tests/ram_ref.c (R1-R4) and the
+# Relative bound on a factor, max |S - S_ref| / max |S_ref| per chain: 100 x the largest difference measured between oracle/klara_oracle.c ko_ram (R1-R4) and the
 # literal restatement over the cases below (2.4e-14, swiss_example: 40 transitions of a recursion whose every step rounds a 4 x 4 product and
 # factorisation differently in the two); the margin covers R1 / R2's reordering, not an algorithmic difference
 S_RTOL = 2.4e-12
@@ -94,11 +95,11 @@ def test_update_is_skipped_where_it_cannot_be_factored():
 
 def test_proposal_outside_the_support_counts_as_acceptance_probability_zero():
     """R3: ratio = -inf gives min(1, exp(ratio)) = 0, as exp(-Inf) does in the reference; NaN too (where the reference's chol would throw)"""
-    lib = RR.load()
-    want = lib.rr_coef(2, 4, 0.7, 0.234, -1e300, 1.5)
-    assert lib.rr_coef(2, 4, 0.7, 0.234, -np.inf, 1.5) == want == min(1.0, 2 * 5 ** -0.7) * (0.0 - 0.234) / 1.5
-    assert lib.rr_coef(2, 4, 0.7, 0.234, np.nan, 1.5) == want
-    assert lib.rr_coef(2, 4, 0.7, 0.234, 3.0, 1.5) == lib.rr_coef(2, 4, 0.7, 0.234, np.inf, 1.5) == lib.rr_coef(2, 4, 0.7, 0.234, 0.0, 1.5)
+    lib = O.load()
+    want = lib.ko_ram_coef(2, 4, 0.7, 0.234, -1e300, 1.5)
+    assert lib.ko_ram_coef(2, 4, 0.7, 0.234, -np.inf, 1.5) == want == min(1.0, 2 * 5 ** -0.7) * (0.0 - 0.234) / 1.5
+    assert lib.ko_ram_coef(2, 4, 0.7, 0.234, np.nan, 1.5) == want
+    assert lib.ko_ram_coef(2, 4, 0.7, 0.234, 3.0, 1.5) == lib.ko_ram_coef(2, 4, 0.7, 0.234, np.inf, 1.5) == lib.ko_ram_coef(2, 4, 0.7, 0.234, 0.0, 1.5)
     case = RC.make("halfspace_d2")
     job = RC.ref_job(case)
     assert job.set_state(case["x0"]) == 0

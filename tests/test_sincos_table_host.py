@@ -6,11 +6,12 @@ transitions per launch read (sin y, cos y - 1) from a 4,096-entry table T[m] tha
 is compiled against the header (gcc, -ffp-contract=off) and, for all 2^20 angles, kd_sincos_rotate(j, T[m]) is compared with the arithmetic form
 bit for bit."""
 import ctypes as C
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
+
+import oracle_ffi as O
 
 ROOT = Path(__file__).resolve().parent.parent
 SRC = Path(__file__).resolve().parent / "sincos_table_ref.c"
@@ -18,11 +19,9 @@ N = 1 << 20
 
 
 @pytest.fixture(scope="module")
-def ref(tmp_path_factory):
-    so = tmp_path_factory.mktemp("sincos_table") / "sincos_table_ref.so"
-    r = subprocess.run(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared", "-I", str(ROOT / "klara.jl_amd" / "csrc"),
-                        "-I", str(ROOT / "include"), "-o", str(so), str(SRC), "-lm"], capture_output=True, text=True)
-    assert r.returncode == 0, "tests/sincos_table_ref.c did not compile:\n" + r.stderr
+def ref():
+    so = O.build_c("sincos_table_ref", ["-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared", *O.INC], sources=[SRC],
+                   hashed=[O.CSRC / "detmath.h", O.CSRC / "detmath_tables.h"])
     lib = C.CDLL(str(so))
     lib.st_fill.argtypes = [C.c_void_p]
     lib.st_fill.restype = None

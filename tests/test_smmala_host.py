@@ -1,4 +1,4 @@
-"""The SMMALA sampler without a GPU: the CPU reference (tests/smmala_ref.c) against the NumPy restatement of the Julia source
+"""The SMMALA sampler without a GPU: the CPU reference (oracle/klara_oracle.c ko_smmala) against the NumPy restatement of the Julia source
 (tests/smmala_mirror.py), the factor C = L^-T against the reference's chol(inv(G))', the descriptor mapping and refusals of the C ABI,
 and the Julia binding's mapping."""
 import re

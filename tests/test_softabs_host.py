@@ -1,5 +1,5 @@
 """The softabs transform of the SMMALA metric without a GPU: the host build of klara.jl_amd/csrc/klara_softabs.h against 60-digit arithmetic
-(mpmath), the CPU reference (tests/softabs_ref.c) against the independent NumPy restatement (tests/smmala_mirror.py with
+(mpmath), the CPU reference (oracle/klara_oracle.c ko_smmala) against the independent NumPy restatement (tests/smmala_mirror.py with
 stats.softabs), the descriptor mapping and refusals of the C ABI, the Python and Julia interfaces, the run-time compiled kernels'
 resources, and the committed vectors."""
 import importlib.util
