@@ -436,6 +436,35 @@ klara_status klara_gather_covariance(klara_handle* h, klara_comm* comm, double* 
 klara_status klara_gather_rhat(klara_handle* h, klara_comm* comm, int32_t split, double* rhat, double* mean, double* wsum, double* bsum,
                                uint64_t* nchains, int64_t* nper);
 
+/* The pooled (multi-chain) effective sample size: how many independent draws are all the chains together worth?  The estimator of BDA3 section 11.5 /
+ * Vehtari et al. 2021 on R-hat's decomposition.  Per dimension, over m units (chains, or half-chains cut as klara_gather_rhat's split form cuts them) of n
+ * saved samples each, with unit mean mu_j and c_j(k) = sum_(t >= k) (x_jt - mu_j)(x_j,t-k - mu_j) (n times StatsBase's autocov(v, k), demean = true):
+ *   csum[k] = sum_j c_j(k),  wsum = csum[0],  mean = (1 / m) sum_j mu_j,  bsum = sum_j (mu_j - mean)^2,
+ *   W = wsum / (m (n - 1)),  var+ = (n - 1) / n W + bsum / (m - 1)   (m = 1: the between term is 0),
+ *   rho[0] = 1,  rho[k] = 1 - (W - csum[k] / (m n)) / var+  for k = 1 .. L,  L = min(maxlag, n - 1),
+ *   P_j = rho[2 j] + rho[2 j + 1], j = 0 .. (L - 1) / 2 (integer division): pair 0 is always summed; from j = 1 the sum stops at the first P_j <= 0 (the
+ *   library's convention for Geyer's stop, as klara_get_chain_acov_mcvar); each summed pair enters as min(P_j, P'_(j-1)) (the monotone sequence);
+ *   tau = -1 + 2 sum P'_j,  ess = m n / tau,  pairs = the number of pairs summed.
+ * pairs == (L - 1) / 2 + 1 means the window ended before Geyer's rule did: ess is then an overestimate (widen the window).  Nothing is clamped (no cap on
+ * ess, no floor on tau); plain IEEE division: var+ = 0 gives NaN.  n < 4: NaN for ess, tau and rho[1..].  When the chains disagree, bsum enters var+ and
+ * every rho rises towards 1 - W / var+: the sum of the per-chain ESS values, whose autocovariances are each taken around the chain's own mean, cannot see that.
+ * mode: */
+#define KLARA_ESS_STREAMED 0   /* from the streamed autocovariances: needs klara_desc.acov_maxlag > 0, nothing else; maxlag must be 0 (it is acov_maxlag) */
+#define KLARA_ESS_HISTORY  1   /* from the stored value history (KLARA_MON_HISTORY, no ring); maxlag 1..127, <= 0: min(127, n - 1) */
+#define KLARA_ESS_SPLIT    2   /* as HISTORY over every chain's two halves, cut as klara_gather_rhat's split form cuts them (>= 8 saved steps) */
+/* A wrong mode for the job's monitors (or a split of fewer than 8 saved steps): KLARA_ERR_STATE; an invalid mode or maxlag: KLARA_ERR_INVALID_ARG before any
+ * HIP call.  The history modes build a temporary streamed state — 3 (L' + 1) nchains ndims doubles, L' the window asked for, twice that for the split form,
+ * freed before the call returns — by feeding the stored columns through the kernels that a job with acov_maxlag runs after its launches; the result has
+ * the bits of a job that had streamed them.  Outputs (any may be NULL): ess, tau, mean, wsum, bsum and pairs ndims each; rho ndims x (L + 1) row-major
+ * (capacity ndims x 128 is always enough); *nunits = m, *nper = n, *lags_out = L.  The across-chain sums are two stages of fixed shape without
+ * floating-point atomics: the bits depend on (nchains, ndims, L, n) and the samples only, not on how the steps were cut into launches.  comm = NULL: this
+ * handle's chains only.  Otherwise collective: the ranks first agree on L (an integer maximum over (L, ~L)); then (m_r, mean_r, bsum_r) merge as for
+ * klara_gather_rhat and wsum, csum are summed; every rank enters every reduction whatever happened locally.  Ranks holding different L or different n all
+ * return KLARA_ERR_STATE.  Before the first saved sample: NaN and zeros, KLARA_OK.  The call only reads the job's state. */
+klara_status klara_gather_ess(klara_handle* h, klara_comm* comm, int32_t mode, int32_t maxlag,
+                              double* ess, double* tau, double* rho /* ndims x (L + 1), row-major */, double* mean, double* wsum, double* bsum,
+                              int32_t* pairs, uint64_t* nunits, int64_t* nper, int32_t* lags_out /* L */);
+
 /* The pooled marginal histograms (requires klara_desc.marg_nbins > 0, else KLARA_ERR_STATE): what credible intervals, medians and tail probabilities are
  * read from when the job is too large to keep its values.  With nbins = marg_nbins and, per dimension d, lo = marg_lo[d], hi = marg_hi[d] and
  * inv_w = nbins / (hi - lo) (formed once on the host, in double), a saved sample x of dimension d is counted in one of nbins + 2 slots:
@@ -694,6 +723,22 @@ klara_status klara_selftest_histogram_ranks(int32_t nranks, int32_t ndims, const
 klara_status klara_selftest_rhat(int32_t device, int64_t nchains, int32_t ndims, int64_t nsaved, const double* sum, const double* sumsq,
                                  const double* X, const int64_t* held, int64_t ncols, const double* hist, int32_t nranks, const int64_t* bounds,
                                  double* out, double* ranks_out, double* split_out, double* split_ranks_out, uint64_t* counters);
+
+/* Self-test hook: the pooled effective sample size on a caller's value history hist (ncols >= 2 saved steps of nchains x ndims values, column t at
+ * hist + t * nchains * ndims; ndims 1..1024), window maxlag (1..127), through the launch functions and the host estimator klara_gather_ess uses.  Three
+ * paths: the streamed state fed launch by launch (nsplits launches of splits[i] >= 0 saved steps, summing to ncols, as klara_selftest_chain_stats), the
+ * history mode, and the split mode (skipped when ncols < 8); each (a) over all chains and (b) cut into nranks shards by bounds (as klara_selftest_rhat),
+ * merged with every all-reduce replaced by a host sum in ascending rank order.  Slot s = 2 * path + (b): out + s * 5 * ndims: ess | tau | mean | wsum | bsum;
+ * rho and csum + s * ndims * (maxlag + 1): ndims x (L + 1) row-major; pairs + s * ndims; counters + 3 * s: units, samples per unit, L.  Every output may be
+ * NULL.  KLARA_ERR_INVALID_ARG (before any launch) for a NULL input, nchains <= 0, ndims outside 1..1024, ncols < 2, maxlag outside 1..127, splits that do
+ * not sum to ncols or bad bounds. */
+klara_status klara_selftest_ess(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t maxlag, int32_t nsplits,
+                                const int64_t* splits, int32_t nranks, const int64_t* bounds, double* out, double* rho, double* csum, int32_t* pairs,
+                                uint64_t* counters);
+
+/* Self-test hook, no device needed: the verdict of a collective klara_gather_ess over simulated ranks holding units[r] units of n[r] samples and windows
+ * lags[r] (0..127): KLARA_OK when all ranks hold the same (n, L), KLARA_ERR_STATE otherwise — L by the maximum over (L, ~L), n by the counters' check. */
+klara_status klara_selftest_ess_ranks(int32_t nranks, const int64_t* units, const int64_t* n, const int32_t* lags);
 
 /* Self-test hook, no device needed: the launches a sequence of klara_run calls of the given lengths issues on a fresh job of
  * this descriptor — transitions per launch k[i], the save-rule bookkeeping handed to the kernels (columns already saved,

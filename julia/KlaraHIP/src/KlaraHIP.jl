@@ -38,7 +38,7 @@ import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
        check_custom_target_softabs, SoftAbs, ramfactor, amstate,
-       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat,
+       HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat, pooledess, gather_ess,
        pooledhistogram, pooledquantiles, gather_histogram, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
@@ -666,4 +666,35 @@ function rhat(job::HIPMCJob; split::Bool=false)
                 job.handle, C_NULL, Int32(split), r, m, w, b, nc, np), "klara_gather_rhat")
     (r, m, w, b, nc[], np[])
 end
+# The pooled (multi-chain) effective sample size over all chains (klara_gather_ess; Klara's ess is per chain, its job being one chain): the tuple
+# (ess, tau, rho, mean, wsum, bsum, pairs, window_exhausted, nunits, nper, lags) — rho is ndims x (lags + 1); window_exhausted[d] says that the window
+# ended before Geyer's rule did, so that ess[d] is an overestimate.  Without split and maxlag the autocovariances kept while sampling are used when the
+# job has them (acov_maxlag > 0), the stored history otherwise; maxlag > 0 (<= 127) and split=true (every chain's two halves, as rhat's split form) work
+# from the stored history.
+const ESS_STREAMED = Int32(0); const ESS_HISTORY = Int32(1); const ESS_SPLIT = Int32(2)
+function ess_call(job::HIPMCJob, comm, mode::Int32, maxlag::Integer)
+    D = job.ndims
+    e = newarray(Float64, D); t = similar(e); m = similar(e); w = similar(e); b = similar(e)
+    rho = newarray(Float64, 128 * D); pairs = newarray(Int32, D)
+    nu = Ref{UInt64}(0); np = Ref{Int64}(0); lg = Ref{Int32}(0)
+    st = ccall((:klara_gather_ess, lib), Cint,
+               (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32},
+                Ref{UInt64}, Ref{Int64}, Ref{Int32}),
+               job.handle, comm, mode, Int32(maxlag), e, t, rho, m, w, b, pairs, nu, np, lg)
+    L = Int(lg[])
+    r = permutedims(reshape(rho[1:D * (L + 1)], L + 1, D))             # (row-major ndims x (L + 1) on the C side)
+    (st, (e, t, r, m, w, b, pairs, pairs .== (div(max(L - 1, 0), 2) + 1), nu[], np[], L))
+end
+function ess_modes(job::HIPMCJob, comm, split::Bool, maxlag::Integer)
+    if !split && maxlag <= 0
+        st, out = ess_call(job, comm, ESS_STREAMED, 0)
+        st != 6 && (check(st, "klara_gather_ess"); return out)        # (KLARA_ERR_STATE: the job keeps no streamed autocovariances — every rank alike)
+    end
+    st, out = ess_call(job, comm, split ? ESS_SPLIT : ESS_HISTORY, maxlag)
+    check(st, "klara_gather_ess")
+    out
+end
+gather_ess(job::HIPMCJob, comm::HIPComm; split::Bool=false, maxlag::Integer=0) = ess_modes(job, comm.handle, split, maxlag)
+# ... and of this job's chains alone (no communicator, no RCCL)
+pooledess(job::HIPMCJob; split::Bool=false, maxlag::Integer=0) = ess_modes(job, C_NULL, split, maxlag)
 end # module

@@ -9,9 +9,9 @@ from .engine import CustomTarget, Engine, GaussDenseTarget, GaussDiagTarget, Hie
 from .api import (  # noqa: F401
     AM, HMC, MALA, MH, RAM, SMMALA, SoftAbs, AcceptanceRateMCTuner, DualAveragingMCTuner, DiffOptions, BasicContMuvParameter, BasicMCJob, BasicMCRange, GenericModel,
     MuvChains, SliceSampler, VanillaMCTuner, acceptance, chain_ess, chain_iact, chain_mcvar, erf_rate_score, likelihood_model, logistic, logistic_rate_score,
-    mcvar_iid, mean, output, reset, run, chain_lzv, chain_qzv, lzv, qzv, pooled_cov, pooled_cor, rhat, pooled_hist, pooled_quantiles,
+    mcvar_iid, mean, output, reset, run, chain_lzv, chain_qzv, lzv, qzv, pooled_cov, pooled_cor, rhat, pooled_hist, pooled_quantiles, pooled_ess, pooled_iact,
 )
-from .distributed import (CommBootstrapTimeout, KlaraComm, allreduce_covariance, allreduce_histogram, allreduce_moments, allreduce_rhat, allreduce_summaries, bootstrap_comm, gather_engine_covariance_klara, gather_engine_moments_klara, gather_engine_rhat_klara,  # noqa: F401
+from .distributed import (CommBootstrapTimeout, KlaraComm, allreduce_covariance, allreduce_ess, allreduce_histogram, allreduce_moments, allreduce_rhat, allreduce_summaries, bootstrap_comm, gather_engine_covariance_klara, gather_engine_moments_klara, gather_engine_rhat_klara, gather_engine_ess_klara,  # noqa: F401
                           gather_engine_summaries, shard_chains, torch_broadcast_bytes)  # noqa: F401
 from .build import build_library, build_oracle  # noqa: F401
 from . import stats  # noqa: F401

@@ -35,6 +35,8 @@ COV_MAX_DIMS = 256                # KLARA_COV_MAX_DIMS
 MARG_MAX_BINS = 1024              # KLARA_MARG_MAX_BINS
 
 ZV_LINEAR, ZV_QUADRATIC, ZV_MAX_TERMS = 1, 2, 128      # KLARA_ZV_*
+ESS_STREAMED, ESS_HISTORY, ESS_SPLIT = 0, 1, 2           # KLARA_ESS_*: the modes of klara_gather_ess
+ESS_MAXLAG = 127
 
 _dp = C.POINTER(C.c_double)
 
@@ -90,6 +92,7 @@ EXPORTS = [
     "klara_selftest_rocrand_blocks", "klara_selftest_math", "klara_selftest_normal_tail", "klara_selftest_transition_normals", "klara_selftest_mfma_f64", "klara_selftest_mfma_f64_4x4x4", "klara_selftest_chain_stats", "klara_selftest_pooled", "klara_strerror",
     "klara_comm_unique_id", "klara_comm_init", "klara_comm_info", "klara_comm_destroy", "klara_gather_summaries", "klara_gather_moments", "klara_gather_covariance", "klara_selftest_covariance",
     "klara_gather_rhat", "klara_selftest_rhat",
+    "klara_gather_ess", "klara_selftest_ess", "klara_selftest_ess_ranks",
     "klara_gather_histogram", "klara_histogram_quantiles", "klara_selftest_marginals", "klara_selftest_histogram_ranks",
     "klara_check_custom_target", "klara_check_custom_target_softabs", "klara_compile_log", "klara_selftest_plan", "klara_selftest_canary", "klara_abi_version",
 ]
@@ -165,6 +168,11 @@ def load() -> C.CDLL:
         "klara_gather_rhat": [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
         "klara_selftest_rhat": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "klara_gather_ess": [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                             C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)],
+        "klara_selftest_ess": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "klara_selftest_ess_ranks": [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_gather_histogram": [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
         "klara_histogram_quantiles": [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
         "klara_selftest_marginals": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,

@@ -522,6 +522,27 @@ def rhat(job_or_chains, split: bool = False, comm=None) -> np.ndarray:
     return job.engine.rhat(split=split, comm=comm)["rhat"]
 
 
+def _pooled_ess(job_or_chains, split, maxlag, comm):
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    if job.acov_maxlag > 0 and not split and maxlag is None:
+        return job.engine.pooled_ess("streamed", None, comm)
+    return job.engine.pooled_ess("split" if split else "history", maxlag, comm)
+
+
+def pooled_ess(job_or_chains, split: bool = False, maxlag=None, comm=None) -> dict:
+    """The pooled (multi-chain) effective sample size per dimension over all chains of a job, formed on the device (Engine.pooled_ess): how many
+    independent draws the chains together are worth — the number to report beside rhat.  From the autocovariances kept while sampling when the job was
+    built with acov_maxlag and neither split nor maxlag is given; otherwise from the stored history (window maxlag, None: min(127, n - 1)), with
+    split=True over every chain's two halves.  `comm`: a klara_comm handle, to take every rank's chains.  Returns Engine.pooled_ess's dict: look at
+    window_exhausted before quoting ess.  The reference has no counterpart (its ess is per chain)."""
+    return _pooled_ess(job_or_chains, split, maxlag, comm)
+
+
+def pooled_iact(job_or_chains, split: bool = False, maxlag=None, comm=None) -> np.ndarray:
+    """The integrated autocorrelation time tau of pooled_ess's call: ess = (chains x saved steps) / tau."""
+    return _pooled_ess(job_or_chains, split, maxlag, comm)["tau"]
+
+
 def pooled_cor(job_or_chains, comm=None) -> np.ndarray:
     """The correlations of pooled_cov: cov_ij / sqrt(cov_ii cov_jj) (NaN where a coordinate never moved)."""
     c = pooled_cov(job_or_chains, comm)

@@ -5,6 +5,7 @@
 #include <new>
 #include "klara_handle.h"
 #include "klara_rhat.h"
+#include "klara_ess.h"
 #include "klara_marg_host.h"
 
 struct klara_comm {
@@ -367,4 +368,154 @@ extern "C" klara_status klara_gather_rhat(klara_handle* h, klara_comm* c, int32_
     }
     const klara_status st = rhat_finish((size_t)D, host.data(), c != nullptr, rhat, mean, wsum, bsum, nchains, nper);
     return st != KLARA_OK ? st : too_short ? KLARA_ERR_STATE : KLARA_OK;
+}
+
+// ---- the pooled effective sample size (klara_ess.h): R-hat's merge with the units' lagged sums riding in the X slot — rank r stages the mean of its units'
+// means, Bsum_r and, as plain sums, Wsum_r | csum_r[D][L + 1] — and, after it, the one statement of the estimator on the host
+void ess_agreement_words(int L, uint64_t v[2]) { v[0] = (uint64_t)(uint32_t)L; v[1] = ~v[0]; }
+bool ess_words_agree(const uint64_t v[2]) { return v[0] == ~v[1]; }                 // max(v) = ~max(~v) = min(v): every rank holds the same L
+
+klara_status ess_finish(size_t D, int Lg, const double* host, bool merged, double* ess, double* tau, double* rho, double* mean, double* wsum, double* bsum,
+                        int32_t* pairs, uint64_t* units, int64_t* nper, double* csum)
+{
+    const size_t R = (size_t)Lg + 1;
+    const MergeLayout L{ D, D, D + D * R };
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    memcpy(cnt, host + L.counters(), sizeof(cnt));
+    const unsigned long long m = cnt[MergeLayout::UNITS], sn = cnt[MergeLayout::UNIT_SAMPLES], sn2 = cnt[MergeLayout::UNIT_SAMPLES_SQ];
+    if ((unsigned __int128)sn * sn != (unsigned __int128)m * sn2) return KLARA_ERR_STATE;       // (as rhat_finish: the same verdict on every rank)
+    const unsigned long long n = m ? sn / m : 0;
+    const bool none = n == 0, shortn = n < 4;
+    const double* mu = host + (merged ? L.mean() : L.mean_r());
+    const double dm = (double)m, dn = (double)n;
+    std::vector<double> r(R);
+    for (size_t j = 0; j < D; ++j) {
+        const double ws = host[L.extra() + j], bs = host[L.M() + j];
+        const double* cs = host + L.extra() + D + j * R;
+        const double Wv = ws / (dm * (dn - 1.0));
+        const double varp = ((dn - 1.0) / dn) * Wv + (m > 1 ? bs / (dm - 1.0) : 0.0);
+        r[0] = 1.0;
+        for (size_t k = 1; k < R; ++k) r[k] = shortn ? (double)NAN : 1.0 - (Wv - cs[k] / (dm * dn)) / varp;
+        double sum = 0.0, prev = 0.0, t = (double)NAN;
+        int np = 0;
+        if (!shortn && Lg >= 1) {
+            const int kk = (Lg - 1) / 2;
+            for (int p = 0; p <= kk; ++p) {
+                const double P = r[2 * p] + r[2 * p + 1];
+                if (p >= 1 && P <= 0.0) break;                                      // Geyer's stop, from the second pair on
+                const double Pm = (p >= 1 && P > prev) ? prev : P;                  // the monotone sequence
+                sum = sum + Pm; prev = Pm; ++np;
+            }
+            t = -1.0 + 2.0 * sum;
+        }
+        if (ess) ess[j] = (dm * dn) / t;
+        if (tau) tau[j] = t;
+        if (rho) memcpy(rho + j * R, r.data(), R * sizeof(double));
+        if (csum) memcpy(csum + j * R, cs, R * sizeof(double));
+        if (pairs) pairs[j] = np;
+        if (mean) mean[j] = none ? 0.0 : mu[j];
+        if (wsum) wsum[j] = none ? 0.0 : ws;
+        if (bsum) bsum[j] = none ? 0.0 : bs;
+    }
+    if (units) *units = none ? 0 : m;
+    if (nper) *nper = (int64_t)n;
+    return KLARA_OK;
+}
+
+// the verdict of a klara_gather_ess call over simulated ranks holding (units[r], n[r], L[r]): the maximum all-reduce of the agreement words and the sum of
+// the counters replaced by host loops, then the very checks of the job path
+extern "C" klara_status klara_selftest_ess_ranks(int32_t nranks, const int64_t* units, const int64_t* n, const int32_t* lags)
+{
+    if (!units || !n || !lags || nranks < 1) return KLARA_ERR_INVALID_ARG;
+    for (int32_t r = 0; r < nranks; ++r)
+        if (units[r] < 1 || n[r] < 0 || lags[r] < 0 || lags[r] > KLARA_ESS_MAXLAG) return KLARA_ERR_INVALID_ARG;
+    uint64_t red[2] = { 0, 0 }, mine[2];
+    unsigned long long sum[MergeLayout::NCOUNTERS] = { 0, 0, 0, 0 }, cnt[MergeLayout::NCOUNTERS];
+    for (int32_t r = 0; r < nranks; ++r) {
+        ess_agreement_words(lags[r], mine);
+        for (int i = 0; i < 2; ++i) if (mine[i] > red[i]) red[i] = mine[i];
+        rhat_counters((unsigned long long)units[r], (unsigned long long)n[r], cnt);
+        for (int i = 0; i < MergeLayout::NCOUNTERS; ++i) sum[i] += cnt[i];
+    }
+    if (!ess_words_agree(red)) return KLARA_ERR_STATE;
+    const MergeLayout L{ 1, 1, 1 + ((size_t)lags[0] + 1) };
+    std::vector<double> host(L.size(), 0.0);
+    memcpy(host.data() + L.counters(), sum, sizeof(sum));
+    return ess_finish(1, lags[0], host.data(), true, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" klara_status klara_gather_ess(klara_handle* h, klara_comm* c, int32_t mode, int32_t maxlag, double* ess, double* tau, double* rho, double* mean,
+                                         double* wsum, double* bsum, int32_t* pairs, uint64_t* nunits, int64_t* nper, int32_t* lags_out)
+{
+    if (!h) return KLARA_ERR_INVALID_ARG;
+    if (mode != KLARA_ESS_STREAMED && mode != KLARA_ESS_HISTORY && mode != KLARA_ESS_SPLIT) return KLARA_ERR_INVALID_ARG;
+    if (mode == KLARA_ESS_STREAMED ? maxlag != 0 : maxlag > KLARA_ESS_MAXLAG) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    const bool streamed = mode == KLARA_ESS_STREAMED, split = mode == KLARA_ESS_SPLIT;
+    if (streamed ? !h->acov_S : (!h->hist || h->ring || !(h->d.monitor & KLARA_MON_HISTORY))) return KLARA_ERR_STATE;   // (history: needs every saved step)
+    HIPCHK(hipSetDevice(h->d.device));
+    const int D = h->d.ndims, per = split ? 2 : 1;
+    const long long N = h->d.nchains, nd = N * D, E = per * nd;
+    // units and samples per unit.  A split of 1 to 7 saved steps is refused, but only after the reductions: no rank leaves the others waiting in theirs
+    const long long nsaved = streamed ? h->acov_n : h->nsaved, n = split ? nsaved / 2 : nsaved;
+    const bool too_short = split && nsaved > 0 && nsaved < 8, run = n >= 1 && !too_short;
+    const long long autolag = n - 1 < 0 ? 0 : n - 1 < KLARA_ESS_MAXLAG ? n - 1 : KLARA_ESS_MAXLAG;
+    const int W = streamed ? h->acov_W : (int)(maxlag > 0 ? maxlag : autolag) + 1;
+    const int Lg = n >= 1 ? (int)((long long)(W - 1) < n - 1 ? (long long)(W - 1) : n - 1) : 0;
+    const MergeLayout L{ (size_t)D, (size_t)D, (size_t)D + (size_t)D * ((size_t)Lg + 1) };
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    rhat_counters((unsigned long long)(per * N), (unsigned long long)n, cnt);
+    if (c) HIPCHK(comm_reserve(c, L.size()));
+    // the streamed state: the job's own, or a temporary one fed from the stored history (3 W N D doubles, twice that for the split form; freed below)
+    DeviceArrays tmp;
+    EssState st[2] = { { h->acov_S, h->acov_head, h->acov_tail, h->acov_total, nullptr }, { nullptr, nullptr, nullptr, nullptr, nullptr } };
+    double* ws = nullptr;
+    hipError_t le = hipSuccess;                                             // local failures: remembered, every reduction is still entered
+    const size_t wse = klara_ess_ws_elems(E, D, W);
+    if (run && streamed) {
+        if (!h->ess_ws) le = h->mem.alloc(&h->ess_ws, wse + L.extra() + (size_t)D + (size_t)D * (size_t)W);
+        ws = h->ess_ws;
+    } else if (run) {
+        le = ess_alloc_states(tmp, per, W, nd, st);
+        if (le == hipSuccess) le = tmp.alloc(&ws, wse + L.size());
+        if (le == hipSuccess) le = ess_feed_history_async(h->stream, h->hist, nsaved, nd, W, per, st);
+    }
+    const auto stage = [&](double* buf) -> hipError_t {                     // zeros | this rank's mean_r, Bsum_r, Wsum_r | csum_r | its counters
+        hipError_t e = hipMemsetAsync(buf, 0, L.size() * sizeof(double), h->stream);
+        if (e == hipSuccess && run && le == hipSuccess) e = ess_reduce_async(h->stream, st, per, n, W, nd, D, ws, buf + L.mean_r(), buf + L.extra());
+        if (e == hipSuccess) e = hipMemcpyAsync(buf + L.counters(), cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream);
+        return e;
+    };
+    const auto leave = [&](klara_status s) { (void)hipStreamSynchronize(h->stream); (void)tmp.release(); return s; };
+    std::vector<double> host(L.size(), 0.0);
+    if (!c) {
+        if (!run) memcpy(host.data() + L.counters(), cnt, sizeof(cnt));
+        else {
+            hipError_t e = le;
+            if (e == hipSuccess) e = stage(ws + wse);
+            if (e == hipSuccess) e = hipMemcpyAsync(host.data(), ws + wse, L.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+            if (e != hipSuccess) return leave(KLARA_ERR_HIP);
+        }
+    } else {
+        // (1) the ranks' L, by an integer maximum over (L, ~L) as klara_gather_histogram's parameters: either all go on or all return KLARA_ERR_STATE
+        // here, before the merge whose X slot has a length that depends on L
+        uint64_t v[2];
+        ess_agreement_words(Lg, v);
+        CommSeq q1{ c, h->stream };
+        q1.H(hipMemcpyAsync(c->buf, v, sizeof(v), hipMemcpyHostToDevice, h->stream));
+        q1.reduce(0, 2, true, ncclMax);
+        if (!q1.finish(v, sizeof(v))) return leave(KLARA_ERR_HIP);
+        if (!ess_words_agree(v)) return leave(KLARA_ERR_STATE);
+        // (2) R-hat's merge; the equal-n check is ess_finish's, on the summed counters
+        CommSeq q{ c, h->stream };
+        q.H(le);
+        q.H(stage(c->buf));
+        if (!comm_merge(q, L, cnt, host)) return leave(KLARA_ERR_HIP);
+    }
+    const bool synced = hipStreamSynchronize(h->stream) == hipSuccess, clean = tmp.release();
+    if (!synced || !clean) return KLARA_ERR_HIP;
+    const klara_status s = ess_finish((size_t)D, Lg, host.data(), c != nullptr, ess, tau, rho, mean, wsum, bsum, pairs, nunits, nper, nullptr);
+    if (lags_out) *lags_out = Lg;
+    return s != KLARA_OK ? s : too_short ? KLARA_ERR_STATE : KLARA_OK;
 }

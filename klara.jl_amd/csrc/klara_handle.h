@@ -78,7 +78,8 @@ struct klara_handle {
     double* pooled_out = nullptr;   // 2*D doubles + 1 u64 scratch for pooled summaries
     double* pool_partial = nullptr; // KLARA_POOL_BLOCKS x (2 D doubles + 1 u64): stage-1 partials of the pooled summaries
     double *rhat_ws = nullptr, *rhat_half = nullptr;   // klara_gather_rhat's workspace, allocated at its first call: stage-1 partials and the staging buffer; the halves' (mean, M2) of the split form
-    double* cdata = nullptr; KlaraJit* jit = nullptr;   // user-defined target: data block, run-time compiled kernels
+    double* ess_ws = nullptr;       // klara_gather_ess in streamed mode: its workspace and staging buffer, allocated at its first call (klara_ess.h)
+    double* cdata = nullptr; KlaraJit* jit = nullptr;  // user-defined target: data block, run-time compiled kernels
     // RAM: the chains' factors (D (D + 1) / 2 planes of nchains doubles, KParams::ram_S), the packed lower triangle of klara_desc.ram_S0 they restart from, the skipped-update counter
     double *ram_S = nullptr, *ram_S0 = nullptr; unsigned long long* ram_skipped = nullptr;
     // AM: the chains' covariances (D (D + 1) / 2 planes, KParams::am_C), their running means (2 D planes, KParams::am_mean), the packed upper triangle of

@@ -52,6 +52,9 @@ hipError_t rhat_sums_async(hipStream_t stream, const double* sum, const double* 
 // become (mean, M2) in half[0, 2 N D) | half[2 N D, 4 N D), unit 2 c + half; then the same reduction over the 2 N units: out, wout as above
 hipError_t rhat_split_async(hipStream_t stream, const double* hist, long long ncols, long long N, int D, double* half, double* partial, double* out,
                             double* wout);
+// The reduction alone, over M units whose (mean, M2) are given (mu, m2: M x D, unit-major — the layout of `half` above): what the pooled effective
+// sample size (klara_ess.hip) hands its units to, so that its mean, Bsum and Wsum come out of R-hat's own code
+hipError_t rhat_units_async(hipStream_t stream, const double* mu, const double* m2, long long M, int D, double* partial, double* out, double* wout);
 // R-hat of one dimension from (Wsum, Bsum) over m units of n samples: NaN for m < 2 or n < 2, plain IEEE division otherwise
 double rhat_value(double wsum, double bsum, double m, double n);
 #ifdef KLARA_HIP_H

@@ -115,6 +115,11 @@ hipError_t rhat_split_async(hipStream_t stream, const double* hist, long long nc
     return rhat_reduce_async(stream, RhatFromHalves{ hm, hq, D }, 2 * N, D, partial, out, wout);
 }
 
+hipError_t rhat_units_async(hipStream_t stream, const double* mu, const double* m2, long long M, int D, double* partial, double* out, double* wout)
+{
+    return rhat_reduce_async(stream, RhatFromHalves{ mu, m2, D }, M, D, partial, out, wout);
+}
+
 double rhat_value(double wsum, double bsum, double m, double n)
 {
     if (m < 2.0 || n < 2.0) return NAN;

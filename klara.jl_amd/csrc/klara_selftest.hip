@@ -3,6 +3,7 @@
 #include <rocrand/rocrand_kernel.h>
 #include "klara_handle.h"
 #include "klara_rhat.h"
+#include "klara_ess.h"
 
 __global__ void k_rocrand_blocks(unsigned long long seed, unsigned long long subseq,
                                  unsigned long long first_block, int nblocks, unsigned int* out)
@@ -582,6 +583,97 @@ extern "C" klara_status klara_selftest_rhat(int32_t device, int64_t nchains, int
         if (cdst) { cdst[2] = units; cdst[3] = (uint64_t)nper; }
     }
     const bool clean = mem.release();
+    if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
+    return status;
+}
+
+// The pooled effective sample size on a caller's value history, through the launch functions and the ess_finish of klara_gather_ess.  One shard's chains
+// [c0, c0 + Nr) through one path into a staging buffer: path 0 the streamed state fed launch by launch over `splits` (as klara_run feeds the job's), path 1
+// the history mode's feed of the stored columns, path 2 the split form's two halves; then the across-chain reduction.  false in *clean: a canary was damaged.
+static hipError_t selftest_ess_one(const MergeLayout& L, int path, const double* hist, long long ncols, long long N, long long c0, long long Nr, int D, int W,
+                                   int nsplits, const int64_t* splits, double* buf, hipStream_t st, bool* clean)
+{
+    const int per = path == 2 ? 2 : 1;
+    const long long nd = Nr * D, n = per == 2 ? ncols / 2 : ncols;
+    DeviceArrays loc;
+    double *dh = nullptr, *ws = nullptr;
+    EssState s[2];
+    hipError_t e = hipMemsetAsync(buf, 0, L.size() * sizeof(double), st);
+    if (e == hipSuccess) e = loc.alloc(&dh, (size_t)ncols * (size_t)nd);
+    if (e == hipSuccess) e = ess_alloc_states(loc, per, W, nd, s);
+    if (e == hipSuccess) e = loc.alloc(&ws, klara_ess_ws_elems((long long)per * nd, D, W));
+    // the shard's chains as a history of their own: column t at dh + t Nr D
+    if (e == hipSuccess) e = hipMemcpy2D(dh, (size_t)nd * sizeof(double), hist + (size_t)c0 * D, (size_t)N * D * sizeof(double), (size_t)nd * sizeof(double),
+                                         (size_t)ncols, hipMemcpyHostToDevice);
+    if (e == hipSuccess && path == 0) {
+        const size_t wb = (size_t)W * (size_t)nd * sizeof(double);
+        e = hipMemsetAsync(s[0].S, 0, wb, st);                               // (what klara_set_state / klara_reset leave)
+        if (e == hipSuccess) e = hipMemsetAsync(s[0].head, 0, wb, st);
+        if (e == hipSuccess) e = hipMemsetAsync(s[0].tail, 0, wb, st);
+        if (e == hipSuccess) e = hipMemsetAsync(s[0].total, 0, (size_t)nd * sizeof(double), st);
+        long long col0 = 0;
+        for (int j = 0; j < nsplits && e == hipSuccess; ++j) {
+            if (splits[j] > 0) e = launch_acov_update(st, dh, s[0].S, s[0].head, s[0].tail, s[0].near, s[0].total, col0, W, nd, col0, (long long)splits[j]);
+            col0 += splits[j];
+        }
+    } else if (e == hipSuccess) e = ess_feed_history_async(st, dh, ncols, nd, W, per, s);
+    if (e == hipSuccess) e = ess_reduce_async(st, s, per, n, W, nd, D, ws, buf + L.mean_r(), buf + L.extra());
+    const hipError_t es = hipStreamSynchronize(st);
+    if (!loc.release()) *clean = false;
+    return e != hipSuccess ? e : es;
+}
+
+extern "C" klara_status klara_selftest_ess(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t maxlag, int32_t nsplits,
+                                           const int64_t* splits, int32_t nranks, const int64_t* bounds, double* out, double* rho, double* csum,
+                                           int32_t* pairs, uint64_t* counters)
+{
+    if (!hist || !splits || !bounds || nchains <= 0 || ndims < 1 || ndims > 1024 || ncols < 2 || maxlag < 1 || maxlag > KLARA_ESS_MAXLAG || nsplits <= 0 ||
+        nranks < 1)
+        return KLARA_ERR_INVALID_ARG;
+    long long sum = 0;
+    for (int j = 0; j < nsplits; ++j) {
+        if (splits[j] < 0 || splits[j] > 0x7fffffffll) return KLARA_ERR_INVALID_ARG;
+        sum += splits[j];
+    }
+    if (sum != ncols) return KLARA_ERR_INVALID_ARG;
+    if (bounds[0] != 0 || bounds[nranks] != nchains) return KLARA_ERR_INVALID_ARG;
+    for (int r = 0; r < nranks; ++r) if (bounds[r + 1] <= bounds[r]) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(device));
+    const size_t D = (size_t)ndims, R = (size_t)maxlag + 1;
+    const long long N = nchains;
+    const int W = maxlag + 1;
+    const hipStream_t st = 0;
+    klara_status status = KLARA_OK;
+    hipError_t e = hipSuccess;
+    bool clean = true;
+    for (int path = 0; path < 3 && e == hipSuccess && status == KLARA_OK; ++path) {
+        if (path == 2 && ncols < 8) continue;                               // (the split form needs 4 samples per half)
+        const unsigned long long per = path == 2 ? 2 : 1, n = (unsigned long long)(path == 2 ? ncols / 2 : ncols);
+        const int Lg = (int)((long long)maxlag < (long long)n - 1 ? (long long)maxlag : (long long)n - 1);
+        const MergeLayout L{ D, D, D + D * ((size_t)Lg + 1) };
+        for (int ranks = 0; ranks < 2 && e == hipSuccess && status == KLARA_OK; ++ranks) {
+            const int slot = 2 * path + ranks, nr = ranks ? nranks : 1;
+            DeviceArrays mem;
+            SimRanks sim{ L, st };
+            e = sim.alloc(mem, nr);
+            for (int r = 0; r < nr && e == hipSuccess; ++r) {
+                const long long c0 = ranks ? bounds[r] : 0, Nr = ranks ? bounds[r + 1] - bounds[r] : N;
+                e = selftest_ess_one(L, path, hist, (long long)ncols, N, c0, Nr, ndims, W, nsplits, splits, sim.buf[r], st, &clean);
+                if (e == hipSuccess) e = sim.set_rhat_counters(r, per * (unsigned long long)Nr, n);
+            }
+            std::vector<double> host(L.size());
+            if (e == hipSuccess && ranks) e = sim.merge(host);              // (b) the between-rank merge; (a) one staging buffer, no merge
+            else if (e == hipSuccess) e = hipMemcpy(host.data(), sim.buf[0], L.size() * sizeof(double), hipMemcpyDeviceToHost);
+            if (!mem.release()) clean = false;
+            if (e != hipSuccess) break;
+            uint64_t units = 0; int64_t nper = 0;
+            double* o = out ? out + (size_t)slot * 5 * D : nullptr;
+            status = ess_finish(D, Lg, host.data(), ranks != 0, o, o ? o + D : nullptr, rho ? rho + (size_t)slot * D * R : nullptr, o ? o + 2 * D : nullptr,
+                                o ? o + 3 * D : nullptr, o ? o + 4 * D : nullptr, pairs ? pairs + (size_t)slot * D : nullptr, &units, &nper,
+                                csum ? csum + (size_t)slot * D * R : nullptr);
+            if (counters) { counters[3 * slot] = units; counters[3 * slot + 1] = (uint64_t)nper; counters[3 * slot + 2] = (uint64_t)Lg; }
+        }
+    }
     if (e != hipSuccess || !clean) return KLARA_ERR_HIP;
     return status;
 }

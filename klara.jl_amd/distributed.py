@@ -320,6 +320,66 @@ def allreduce_rhat(local: Dict[str, np.ndarray], group=None, device=None) -> Dic
     return {"rhat": rhat_from_sums(wsum, bsum, m, n), "mean": mean, "wsum": wsum, "bsum": bsum, "nchains": m, "nper": n}
 
 
+def gather_engine_ess_klara(engine, comm: KlaraComm, mode: str = "streamed", maxlag=None) -> Dict[str, np.ndarray]:
+    """The pooled effective sample size over every rank's chains through the C ABI alone: klara_gather_ess(h, comm, ...) — the ranks agree on the window,
+    then R-hat's merge with the lagged sums summed beside wsum, on the job's stream.  Keys as Engine.pooled_ess."""
+    return engine.pooled_ess(mode=mode, maxlag=maxlag, comm=comm.handle)
+
+
+def allreduce_ess(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
+    """klara_gather_ess's between-rank merge through torch.distributed, for a host that brings its own transport: `local` holds this rank's mean[D],
+    wsum[D], bsum[D], nunits, nper and csum[D, L + 1] — stats.pooled_ess returns all of them; Engine.pooled_ess does not return csum, and without it
+    csum is rebuilt from rho (m n (W - (1 - rho) var+), rounded).  The library's order: a MAX all-reduce of (L, -L) — the ranks must hold the same
+    window —, then R-hat's four SUM all-reduces with wsum | csum in the last; every rank enters all of them.  Raises ValueError, on every rank, when
+    the ranks hold different windows or different numbers of samples per unit.  Works without torch.distributed initialised (single process)."""
+    import torch
+    import torch.distributed as dist
+    from .stats import ess_from_sums
+
+    mean_l = np.asarray(local["mean"], dtype=np.float64).ravel(); b_l = np.asarray(local["bsum"], dtype=np.float64).ravel()
+    w_l = np.asarray(local["wsum"], dtype=np.float64).ravel()
+    m_l, n_l = int(local["nunits"]), int(local["nper"])
+    D = mean_l.size
+    if "csum" in local:
+        c_l = np.asarray(local["csum"], dtype=np.float64).reshape(D, -1)
+    else:
+        rho = np.asarray(local["rho"], dtype=np.float64).reshape(D, -1)
+        with np.errstate(all="ignore"):
+            W = w_l / (float(m_l) * (n_l - 1.0)); varp = ((n_l - 1.0) / n_l) * W + (b_l / (m_l - 1.0) if m_l > 1 else 0.0)
+            c_l = float(m_l) * n_l * (W[:, None] - (1.0 - rho) * varp[:, None])
+        c_l[:, 0] = w_l
+    lags = c_l.shape[1] - 1
+    live = dist.is_available() and dist.is_initialized()
+    if live and device is None:
+        device = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+
+    def reduce(buf: np.ndarray, op) -> np.ndarray:
+        if not live:
+            return buf
+        t = torch.from_numpy(np.ascontiguousarray(buf)).to(device)
+        dist.all_reduce(t, op=op, group=group)
+        return t.cpu().numpy()
+
+    agree = reduce(np.array([lags, -lags], dtype=np.int64), dist.ReduceOp.MAX)
+    if int(agree[0]) != -int(agree[1]):                      # max L = min L: before anything whose length depends on L is exchanged
+        raise ValueError("allreduce_ess: the ranks hold different windows")
+    cnt = reduce(np.array([m_l * n_l, m_l * n_l * n_l, m_l], dtype=np.int64), dist.ReduceOp.SUM)
+    sn, sn2, m = (int(v) for v in cnt)
+    with np.errstate(all="ignore"):
+        wmean = reduce(float(m_l) * mean_l, dist.ReduceOp.SUM)
+        mean = wmean / float(m) if m > 0 else np.zeros_like(wmean)
+        d = mean_l - mean
+        bsum = reduce(b_l + float(m_l) * (d * d), dist.ReduceOp.SUM)
+        x = reduce(np.concatenate([w_l, c_l.ravel()]), dist.ReduceOp.SUM)
+    if sn * sn != m * sn2:
+        raise ValueError("allreduce_ess: the ranks hold different numbers of saved steps")
+    n = sn // m if m else 0
+    wsum, csum = x[:D], x[D:].reshape(D, lags + 1)
+    ess, tau, rho, pairs = ess_from_sums(csum, wsum, bsum, m, n)
+    return {"ess": ess, "tau": tau, "rho": rho, "mean": mean, "wsum": wsum, "bsum": bsum, "csum": csum, "pairs": pairs,
+            "window_exhausted": pairs == (max(lags - 1, 0) // 2 + 1), "nunits": m, "nper": n, "lags": lags}
+
+
 def allreduce_summaries(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
     """The same exchange for a caller that holds pooled RAW sums: `local` = sum[D], sumsq[D], naccept, ntransitions, nsamples of this
     rank's chains.  Returns the global sums plus the posterior moments (mean, var) and the acceptance rate; the variance comes from

@@ -507,6 +507,31 @@ class Engine:
         out["nchains"], out["nper"] = int(nc.value), int(npu.value)
         return out
 
+    def pooled_ess(self, mode: str = "streamed", maxlag=None, comm=None):
+        """The pooled (multi-chain) effective sample size over this handle's chains — or, with a klara_comm handle, over every rank's (klara_gather_ess):
+        ess = m n / tau from R-hat's within / between variances and the across-chain sums of the chains' lagged cross-products, Geyer's monotone pair sum.
+        mode "streamed": from the autocovariances kept while sampling (acov_maxlag > 0; maxlag must be None); "history": from the stored history
+        (MON_HISTORY, no ring) with window maxlag (1..127; None: min(127, n - 1)); "split": the same over every chain's two halves (at least 8 saved
+        steps).  Dict of ess[D], tau[D], rho[D, L + 1], mean[D], wsum[D], bsum[D], pairs[D], window_exhausted[D] (the window ended before Geyer's rule
+        did: ess is an overestimate there), nunits, nper, lags (= L)."""
+        modes = {"streamed": L.ESS_STREAMED, "history": L.ESS_HISTORY, "split": L.ESS_SPLIT}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}")
+        if mode == "streamed" and maxlag is not None:
+            raise ValueError("the streamed mode's window is the job's acov_maxlag: maxlag must be None")
+        out = {k: np.empty(self.ndims) for k in ("ess", "tau", "mean", "wsum", "bsum")}
+        rho = np.empty((self.ndims, L.ESS_MAXLAG + 1)); pairs = np.zeros(self.ndims, dtype=np.int32)
+        nu, npu, lg = C.c_uint64(0), C.c_int64(0), C.c_int32(0)
+        L.check(self._lib.klara_gather_ess(self._h, comm, modes[mode], 0 if maxlag is None else int(maxlag), out["ess"].ctypes.data, out["tau"].ctypes.data,
+                                           rho.ctypes.data, out["mean"].ctypes.data, out["wsum"].ctypes.data, out["bsum"].ctypes.data, pairs.ctypes.data,
+                                           C.byref(nu), C.byref(npu), C.byref(lg)), "klara_gather_ess")
+        lags = int(lg.value)
+        out["rho"] = rho.ravel()[: self.ndims * (lags + 1)].reshape(self.ndims, lags + 1).copy()
+        out["pairs"] = pairs
+        out["window_exhausted"] = pairs == (max(lags - 1, 0) // 2 + 1)
+        out["nunits"], out["nper"], out["lags"] = int(nu.value), int(npu.value), lags
+        return out
+
     def chain(self, local_chain: int) -> np.ndarray:
         """One chain's saved values in Klara's NState layout: (ndims, nsaved), column-major."""
         n = C.c_int64(0)

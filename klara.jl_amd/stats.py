@@ -165,6 +165,63 @@ def rhat(values, split: bool = False) -> np.ndarray:
         return np.sqrt(((n - 1) / n * W + Bn) / W)
 
 
+def ess_from_sums(csum, wsum, bsum, m, n):
+    """The pooled effective sample size from the across-unit sums, operation for operation as klara_gather_ess's host step evaluates it: csum (D, L + 1)
+    = sum over the m units of their lagged sums c_j(k), wsum = csum[:, 0], bsum = sum (unit mean - mean)^2, n samples per unit.  Returns (ess[D], tau[D],
+    rho[D, L + 1], pairs[D]): rho[0] = 1, Geyer's pair sum with pair 0 always summed, the stop at the first later pair <= 0, the monotone clamp; nothing
+    capped; n < 4: NaN for ess, tau and rho[1:]."""
+    csum = np.atleast_2d(np.asarray(csum, dtype=np.float64)); wsum = np.asarray(wsum, dtype=np.float64).ravel(); bsum = np.asarray(bsum, dtype=np.float64).ravel()
+    D, R = csum.shape
+    lags = R - 1
+    dm, dn = float(m), float(n)
+    rho = np.full((D, R), np.nan); rho[:, 0] = 1.0
+    ess = np.full(D, np.nan); tau = np.full(D, np.nan); pairs = np.zeros(D, dtype=np.int32)
+    if n < 4 or lags < 1:
+        return ess, tau, rho, pairs
+    with np.errstate(all="ignore"):
+        W = wsum / (dm * (dn - 1.0))
+        varp = ((dn - 1.0) / dn) * W + (bsum / (dm - 1.0) if m > 1 else 0.0)
+        rho[:, 1:] = 1.0 - (W[:, None] - csum[:, 1:] / (dm * dn)) / varp[:, None]
+        kk = (lags - 1) // 2
+        for j in range(D):
+            total = prev = 0.0
+            for p in range(kk + 1):
+                P = float(rho[j, 2 * p]) + float(rho[j, 2 * p + 1])
+                if p >= 1 and P <= 0.0:
+                    break
+                Pm = prev if (p >= 1 and P > prev) else P
+                total = total + Pm; prev = Pm; pairs[j] += 1
+            tau[j] = -1.0 + 2.0 * total
+        ess = (dm * dn) / tau
+    return ess, tau, rho, pairs
+
+
+def pooled_ess(hist, maxlag, split: bool = False) -> dict:
+    """The pooled (multi-chain) effective sample size per dimension of `hist` (n saved steps, m chains, D) — the literal NumPy form of klara_gather_ess
+    (BDA3 section 11.5; Vehtari et al. 2021), two-pass: with mu_j the mean of unit j (a chain; split=True: the half-chains [0, h) and [n - h, n),
+    h = n // 2, as rhat's split form) and c_j(k) = sum_(t >= k) (x_jt - mu_j)(x_j,t-k - mu_j) for k = 0 .. L = min(maxlag, n - 1),
+      csum[k] = sum_j c_j(k), wsum = csum[0], mean = mean of the mu_j, bsum = sum (mu_j - mean)^2, W = wsum / (m (n - 1)),
+      var+ = (n - 1) / n W + bsum / (m - 1) (0 between term for m = 1), rho[0] = 1, rho[k] = 1 - (W - csum[k] / (m n)) / var+,
+    then ess_from_sums.  Returns a dict as Engine.pooled_ess: ess, tau, rho, mean, wsum, bsum, csum, pairs, window_exhausted, nunits, nper, lags."""
+    x = np.asarray(hist, dtype=np.float64)
+    if x.ndim == 2:
+        x = x[:, :, None]
+    if split:
+        h = x.shape[0] // 2
+        x = np.stack([x[:h], x[x.shape[0] - h:]], axis=2).reshape(h, 2 * x.shape[1], x.shape[2])       # unit 2 c + half
+    n, m, D = x.shape
+    lags = max(min(int(maxlag), n - 1), 0)
+    mu = np.mean(x, axis=0)                                       # (m, D)
+    z = x - mu
+    csum = np.stack([np.sum(np.sum(z[k:] * z[:n - k], axis=0), axis=0) for k in range(lags + 1)], axis=1)        # (D, L + 1)
+    mean = np.mean(mu, axis=0)
+    bsum = np.sum((mu - mean) ** 2, axis=0)
+    wsum = csum[:, 0].copy()
+    ess, tau, rho, pairs = ess_from_sums(csum, wsum, bsum, m, n)
+    return {"ess": ess, "tau": tau, "rho": rho, "mean": mean, "wsum": wsum, "bsum": bsum, "csum": csum, "pairs": pairs,
+            "window_exhausted": pairs == (max(lags - 1, 0) // 2 + 1), "nunits": m, "nper": n, "lags": lags}
+
+
 def _per_dim(fn, value: np.ndarray, *args) -> np.ndarray:
     value = np.asarray(value)
     return np.array([fn(value[i, :], *args) for i in range(value.shape[0])])
