@@ -210,6 +210,7 @@ typedef enum klara_tuner_mode {
                                      ndims > KLARA_COV_MAX_DIMS: KLARA_ERR_UNSUPPORTED.  The transition kernels never see the bit: the chains of a job are the
                                      same bits with and without it. */
 #define KLARA_COV_MAX_DIMS 256
+#define KLARA_DERIVED_MAX_OUT 64   /* outputs of a derived-quantity closure at most (klara_desc.derived_nout) */
 
 typedef struct klara_desc {
     uint32_t struct_size;        /* = sizeof(klara_desc), ABI check                                  */
@@ -324,6 +325,32 @@ typedef struct klara_desc {
     uint64_t seed;               /* Philox key                                                       */
     uint32_t monitor;            /* KLARA_MON_* bits                                                 */
     int32_t  steps_per_launch;   /* transitions fused in one kernel launch (>=1; 0 = library default) */
+    const char* derived_src;     /* derived quantities — a user function of the state, summarised on the device (the reference's Transformation,
+                                    src/variables/variables.jl:102-119, on the one-parameter job): C text compiled for gfx950 at klara_create, for ANY target
+                                    family, that defines
+                                      KLARA_USER_FN void klara_user_derived(const double* x, int D, const double* data, long long ndata, double* out, int K);
+                                    x: one saved sample (read-only), data: the closure's own block (derived_data), out: K = derived_nout doubles, all of which
+                                    it must write.  KLARA_D and KLARA_K are defined before the text.  It may call the kd_* functions of detmath.h that need no table of
+                                    their own in dynamic LDS (kd_exp, kd_exp_neg, kd_log, kd_log_u01, kd_log12, kd_erf, kd_sincos2pi, kd_softplus_logistic, kd_fma:
+                                    every one but kd_sincos2pi_tab20 and the other readers of kd_screm_lds, a table in dynamic LDS that would alias the kernel's rows) and nothing
+                                    else from the library, and must be a pure function of its arguments: the same text built by a host compiler with
+                                    -ffp-contract=off then gives the same bits.  After every launch that saved m > 0 columns, for each chain c and saved step
+                                    t in ascending t, y = klara_user_derived(x_ct):  dsum[c][k] = dsum[c][k] + y[k];  dsumsq[c][k] = dsumsq[c][k] + y[k] * y[k]
+                                    (the product rounded, then added; no contraction).  A chain's sums depend on that chain only; the bits are the same
+                                    however the steps are cut into launches; no floating-point atomics.  A non-finite y flows through as IEEE arithmetic.
+                                    A consumer of the saved samples exactly as marg_nbins is (value ring, one chain partition, the status of
+                                    KLARA_MON_HISTORY where a job cannot keep values); the transition kernels never see it: the chains of a job are the same
+                                    bits with and without it.  klara_set_state and klara_reset clear the accumulators.  NULL exactly when derived_nout = 0
+                                    (else KLARA_ERR_INVALID_ARG); a text that does not compile: KLARA_ERR_COMPILE (klara_compile_log, klara_check_derived).
+                                    Read with klara_get_derived_sums and the klara_gather_derived_* calls.  Copied at create (klara.jl_amd/csrc/klara_derived.h) */
+    const double* derived_data;  /* the closure's data block, derived_ndata doubles, copied to the device at create; NULL when derived_ndata = 0 */
+    int64_t  derived_ndata;      /* >= 0; > 0 needs derived_data and derived_nout > 0 */
+    int64_t  derived_nout;       /* K: 0 = off (nothing changes), 1..KLARA_DERIVED_MAX_OUT */
+    int64_t  derived_nbins;      /* 0: no histograms of the outputs; 1..KLARA_MARG_MAX_BINS (needs derived_nout > 0): y is also staged as [column][chain][K] and
+                                    counted by the marginals' kernel with the geometry of (nchains, K, derived_nbins) and the slot rule stated at
+                                    klara_gather_histogram — a NaN output is counted in the overflow slot (klara_gather_derived_histogram) */
+    const double* derived_lo;    /* the histograms' lower bounds, K doubles ... */
+    const double* derived_hi;    /* ... and upper bounds, K doubles, all finite, lo[k] < hi[k].  Both NULL when derived_nbins = 0 (else KLARA_ERR_INVALID_ARG) */
     void*    stream;             /* hipStream_t to launch on, or NULL for a library-owned stream     */
 } klara_desc;
 
@@ -491,6 +518,41 @@ klara_status klara_gather_histogram(klara_handle* h, klara_comm* comm, uint64_t*
  * KLARA_ERR_INVALID_ARG for a NULL argument, ndims < 1, nbins outside 1..KLARA_MARG_MAX_BINS, nprobs < 1 or a p outside (0, 1]. */
 klara_status klara_histogram_quantiles(const uint64_t* counts, int32_t ndims, int64_t nbins, const double* lo, const double* hi, int32_t nprobs,
                                        const double* probs, double* out);
+
+/* ---- Derived quantities (klara_desc.derived_src / derived_nout = K > 0; a job without them: KLARA_ERR_STATE from the calls below).  Every pooled diagnostic
+ * of the coordinates, applied to the K outputs of the user's klara_user_derived: the calls hand the per-chain sums dsum / dsumsq (klara_desc.derived_src) to
+ * the very reductions klara_gather_moments, klara_gather_rhat (split = 0) and klara_gather_histogram run — the same kernels, the same between-rank merge —
+ * with K where those have ndims.  No history of the derived values is kept: nothing that needs one (per-chain ESS, split R-hat, pooled ESS, covariance).
+ * Before the first saved sample: zeros or NaN and KLARA_OK, as their counterparts.  The calls only read the job's state. */
+/* the per-chain running sums: sum and sumsq nchains x K row-major (either may be NULL), *nsaved_out = saved steps consumed */
+klara_status klara_get_derived_sums(klara_handle* h, double* sum, double* sumsq, int64_t* nsaved_out);
+/* klara_gather_moments over the outputs: mean[K], m2[K] = sum (y - mean)^2 over all saved samples of all chains, *nsamples = chains x saved steps */
+klara_status klara_gather_derived_moments(klara_handle* h, klara_comm* comm, double* mean, double* m2, uint64_t* nsamples, uint64_t* nchains);
+/* klara_gather_rhat's plain (unsplit) form over the outputs: rhat, mean, wsum, bsum K each */
+klara_status klara_gather_derived_rhat(klara_handle* h, klara_comm* comm, double* rhat, double* mean, double* wsum, double* bsum, uint64_t* nchains,
+                                       int64_t* nper);
+/* klara_gather_histogram over the outputs (needs derived_nbins > 0, else KLARA_ERR_STATE): counts K x (derived_nbins + 2), the slot rule stated there with
+ * lo = derived_lo[k], hi = derived_hi[k]; klara_histogram_quantiles turns the table into quantiles.  With a communicator the ranks' (derived_nbins, lo, hi)
+ * are compared first, as there. */
+klara_status klara_gather_derived_histogram(klara_handle* h, klara_comm* comm, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains);
+/* Compile `src` as a derived-quantity closure for gfx950 exactly as klara_create would for ndims and nout outputs, without a handle and without a GPU.
+ * KLARA_OK or KLARA_ERR_COMPILE (the log in klara_compile_log; a source without the function names klara_user_derived there); ndims outside 1..1024 or nout
+ * outside 1..KLARA_DERIVED_MAX_OUT: KLARA_ERR_INVALID_ARG. */
+klara_status klara_check_derived(const char* src, int32_t ndims, int32_t nout);
+/* Self-test hook, no device needed: the geometry of the derived-quantity kernel for (nchains, ndims, nout) — a function of those three alone
+ * (klara.jl_amd/csrc/klara_derived.h): chains per workgroup, doubles per LDS row, threads per workgroup, workgroups, LDS bytes.  Any output may be NULL.
+ * KLARA_ERR_INVALID_ARG for nchains <= 0, ndims outside 1..1024, nout outside 1..KLARA_DERIVED_MAX_OUT. */
+klara_status klara_selftest_derived_plan(int64_t nchains, int32_t ndims, int32_t nout, int32_t* chains_per_wg, int32_t* stride, int32_t* threads,
+                                         int64_t* workgroups, int64_t* lds_bytes);
+/* Self-test hook: the derived-quantity kernel on a caller's value history.  hist holds ncols (>= 1) saved steps of nchains x ndims values (column t at
+ * hist + t * nchains * ndims); it is fed launch by launch through the launch function the job path uses — launch j brings splits[j] >= 0 saved steps, the
+ * splits sum to ncols; a launch of more than 32 columns goes in pieces, as in a job — starting from zeroed accumulators.  sum, sumsq: nchains x nout, read
+ * back as klara_get_derived_sums reads them; values (may be NULL; not NULL compiles the kernel with staging on): ncols x nchains x nout, the staged outputs.
+ * data may be NULL when ndata = 0.  KLARA_ERR_INVALID_ARG (before any HIP call or compilation) for a NULL hist, splits, src, sum or sumsq, nchains <= 0,
+ * ndims outside 1..1024, nout outside 1..KLARA_DERIVED_MAX_OUT, ncols < 1, ndata < 0 or data missing, a negative split or splits that do not sum to ncols. */
+klara_status klara_selftest_derived(int32_t device, int64_t nchains, int32_t ndims, int64_t ncols, const double* hist, int32_t nsplits,
+                                    const int64_t* splits, const char* src, int32_t nout, const double* data, int64_t ndata, double* sum, double* sumsq,
+                                    double* values);
 
 /* Memory-safety aid (tests only).  With KLARA_DEBUG_CANARY=1 in the environment every device array the library allocates lies between
  * two 4 KiB canaries of a signalling-NaN pattern; klara_destroy returns KLARA_ERR_STATE when a kernel of the job wrote into one, and this

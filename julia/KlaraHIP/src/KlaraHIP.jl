@@ -39,7 +39,8 @@ export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, Log
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
        check_custom_target_softabs, SoftAbs, ramfactor, amstate,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat, pooledess, gather_ess,
-       pooledhistogram, pooledquantiles, gather_histogram, KlaraDesc, klara_desc
+       pooledhistogram, pooledquantiles, gather_histogram, Derived, derivedsums, derivedmoments, derivedrhat, derivedhistogram, derivedquantiles,
+       gather_derived_moments, gather_derived_rhat, gather_derived_histogram, check_derived, KlaraDesc, klara_desc
 const lib = "libklara_hip"            # klara.jl_amd/lib/libklara_hip.so on LD_LIBRARY_PATH
 
 # ---------------------------------------------------------------- Julia 0.6 / >= 0.7 compatibility (the only version-dependent code)
@@ -63,6 +64,7 @@ const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
 const MON_ACCEPT, MON_HISTORY, MON_SUMMARIES, MON_HIST_LT, MON_HIST_GRAD, MON_HIST_LLLP = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 const MARG_MAX_BINS = 1024             # KLARA_MARG_MAX_BINS
+const DERIVED_MAX_OUT = 64             # KLARA_DERIVED_MAX_OUT
 const MON_COVARIANCE = 0x40            # KLARA_MON_COVARIANCE: the pooled D x D cross-products, accumulated while sampling (pooledcovariance)
 
 # struct klara_desc — field order/types exactly as include/klara_hip.h
@@ -86,7 +88,10 @@ struct KlaraDesc
     am_C0::Ptr{Float64}; am_corescale::Float64; am_minorscale::Float64; am_c::Float64; am_t0::Int64
     ram_S0::Ptr{Float64}; ram_targetrate::Float64; ram_gamma::Float64
     marg_lo::Ptr{Float64}; marg_hi::Ptr{Float64}; marg_nbins::Int64
-    seed::UInt64; monitor::UInt32; steps_per_launch::Int32; stream::Ptr{Cvoid}
+    seed::UInt64; monitor::UInt32; steps_per_launch::Int32
+    derived_src::Cstring; derived_data::Ptr{Float64}; derived_ndata::Int64; derived_nout::Int64; derived_nbins::Int64
+    derived_lo::Ptr{Float64}; derived_hi::Ptr{Float64}
+    stream::Ptr{Cvoid}
 end
 
 # every field by keyword, defaults = "not used"; the positional call below must list the fields in struct order (checked by
@@ -106,7 +111,9 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
                     am_C0=Ptr{Float64}(C_NULL), am_corescale=0.0, am_minorscale=0.0, am_c=0.0, am_t0=0,
                     ram_S0=Ptr{Float64}(C_NULL), ram_targetrate=0.0, ram_gamma=0.0,
                     marg_lo=Ptr{Float64}(C_NULL), marg_hi=Ptr{Float64}(C_NULL), marg_nbins=0,
-                    seed=UInt64(0), monitor=UInt32(0), steps_per_launch=0, stream=C_NULL)
+                    seed=UInt64(0), monitor=UInt32(0), steps_per_launch=0,
+                    derived_src=Cstring(C_NULL), derived_data=Ptr{Float64}(C_NULL), derived_ndata=0, derived_nout=0, derived_nbins=0,
+                    derived_lo=Ptr{Float64}(C_NULL), derived_hi=Ptr{Float64}(C_NULL), stream=C_NULL)
     KlaraDesc(UInt32(sizeof(KlaraDesc)), KLARA_ABI_VERSION,
               sampler, target, tuner, tuner_mode,
               nchains, chain_offset, ndims, device,
@@ -125,8 +132,19 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               am_C0, am_corescale, am_minorscale, am_c, am_t0,
               ram_S0, ram_targetrate, ram_gamma,
               marg_lo, marg_hi, marg_nbins,
-              seed, monitor, steps_per_launch, stream)
+              seed, monitor, steps_per_launch,
+              derived_src, derived_data, derived_ndata, derived_nout, derived_nbins,
+              derived_lo, derived_hi, stream)
 end
+
+# Derived(nout, src; data, marginals): a function of the state, summarised on the device (klara_desc.derived_src ...; the reference's Transformation,
+# src/variables/variables.jl:102-119, on the one-parameter job).  src is C text defining
+#     KLARA_USER_FN void klara_user_derived(const double* x, int D, const double* data, long long ndata, double* out, int K);
+# data its own block of doubles, marginals = (nbins, lo, hi) over the nout outputs (lo, hi scalars or nout values) for their pooled histograms.
+struct Derived
+    nout::Int; src::String; data::Vector{Float64}; marginals
+end
+Derived(nout::Integer, src::AbstractString; data=Float64[], marginals=nothing) = Derived(Int(nout), String(src), convert(Vector{Float64}, data), marginals)
 
 # H -> softabs(H, a) (stats/metrics.jl:1-4) as a callable the device path can recognise: SMMALA(1.25, SoftAbs(1000.)) is Klara's own sampler — it
 # runs on the CPU through Klara unchanged — and HIPMCJob maps it to klara_desc.smmala_softabs = a (an anonymous closure H -> softabs(H, a) cannot be
@@ -246,7 +264,7 @@ end
 function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
                   tuner=nothing, outopts::Dict=Dict{Symbol, Any}(), pooled::Bool=false, nchains::Integer=1,
                   seed::Integer=rand(UInt64), chain_offset::Integer=0, device::Integer=0, steps_per_launch::Integer=0,
-                  summaries::Bool=true, bm_batchlen::Integer=0, covariance::Bool=false, marginals=nothing)
+                  summaries::Bool=true, bm_batchlen::Integer=0, covariance::Bool=false, marginals=nothing, derived=nothing)
     X0 = startmatrix(v0[parameter.key], nchains)                          # D x N: column = chain == N x D row-major
     D, N = size(X0)
     t = parameter.target
@@ -359,6 +377,25 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         push!(keep, vlo); push!(keep, vhi)
         kw[:marg_lo] = pointer(vlo); kw[:marg_hi] = pointer(vhi); kw[:marg_nbins] = Int64(nb)
         oo[:marginals] = (Int64(nb), vlo, vhi)
+    end
+    if derived !== nothing                                                # Derived(nout, src; data, marginals): a function of the state, summed per chain
+        isa(derived, Derived) || error("derived= takes a Derived(nout, src; data, marginals)")
+        push!(keep, derived.src); push!(keep, derived.data)
+        kw[:derived_src] = Base.unsafe_convert(Cstring, derived.src); kw[:derived_nout] = Int64(derived.nout)
+        if length(derived.data) > 0
+            kw[:derived_data] = pointer(derived.data); kw[:derived_ndata] = Int64(length(derived.data))
+        end
+        dmarg = nothing
+        if derived.marginals !== nothing
+            dnb, dlo, dhi = derived.marginals
+            wlo = isa(dlo, Number) ? fill(Float64(dlo), derived.nout) : convert(Vector{Float64}, dlo)
+            whi = isa(dhi, Number) ? fill(Float64(dhi), derived.nout) : convert(Vector{Float64}, dhi)
+            (length(wlo) == derived.nout && length(whi) == derived.nout) || error("derived marginals: lo and hi must be scalars or have one entry per output")
+            push!(keep, wlo); push!(keep, whi)
+            kw[:derived_lo] = pointer(wlo); kw[:derived_hi] = pointer(whi); kw[:derived_nbins] = Int64(dnb)
+            dmarg = (Int64(dnb), wlo, whi)
+        end
+        oo[:derived] = (derived.nout, dmarg)
     end
     desc = klara_desc(; kw...)
     h = Ref{Ptr{Cvoid}}(C_NULL)
@@ -638,13 +675,78 @@ pooledhistogram(job::HIPMCJob) = histogram_of(job, Ptr{Cvoid}(C_NULL))
 # [lo, hi) — a range chosen badly is never clipped silently —, NaN before the first saved sample
 function pooledquantiles(job::HIPMCJob, probs)
     nb, lo, hi = marginals_of(job)
-    counts = pooledhistogram(job)[1]
+    quantiles_of(pooledhistogram(job)[1], nb, lo, hi, probs)
+end
+# ... the one call behind pooledquantiles and derivedquantiles: counts (nbins + 2) x W, lo and hi W each
+function quantiles_of(counts::Matrix{UInt64}, nb, lo, hi, probs)
+    W = size(counts, 2)
     p = convert(Vector{Float64}, collect(probs))
-    out = newarray(Float64, length(p), job.ndims)
+    out = newarray(Float64, length(p), W)
     check(ccall((:klara_histogram_quantiles, lib), Cint,
                 (Ptr{UInt64}, Int32, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}),
-                counts, Int32(job.ndims), Int64(nb), lo, hi, Int32(length(p)), p, out), "klara_histogram_quantiles")
+                counts, Int32(W), Int64(nb), lo, hi, Int32(length(p)), p, out), "klara_histogram_quantiles")
     out
+end
+# ---- derived quantities: a job built with derived=Derived(nout, src; data, marginals).  (nout, marginals) of the job, then the calls; comm: a communicator's
+# handle or C_NULL (this job's chains alone)
+function derived_of(job::HIPMCJob)
+    haskey(job.outopts, :derived) || error("the job was built without derived=Derived(nout, src)")
+    job.outopts[:derived]
+end
+# (sum, sumsq, nsaved): every chain's running sums of the closure's outputs and of their squares, nout x nchains (column c = chain c: the C arrays' rows)
+function derivedsums(job::HIPMCJob)
+    K = derived_of(job)[1]
+    s = newarray(Float64, K, job.nchains); q = similar(s); n = Ref{Int64}(0)
+    check(ccall((:klara_get_derived_sums, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}), job.handle, s, q, n), "klara_get_derived_sums")
+    (s, q, n[])
+end
+function derived_moments_of(job::HIPMCJob, comm::Ptr{Cvoid})
+    K = derived_of(job)[1]
+    m = newarray(Float64, K); m2 = similar(m); ns = Ref{UInt64}(0); nc = Ref{UInt64}(0)
+    check(ccall((:klara_gather_derived_moments, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{UInt64}),
+                job.handle, comm, m, m2, ns, nc), "klara_gather_derived_moments")
+    (m, m2 ./ Float64(ns[]), ns[], nc[])
+end
+# (mean, var, nsamples, chains) of the outputs over every chain of every GPU (klara_gather_derived_moments: klara_gather_moments on the derived sums) ...
+gather_derived_moments(job::HIPMCJob, comm::HIPComm) = derived_moments_of(job, comm.handle)
+# ... and of this job's chains alone
+derivedmoments(job::HIPMCJob) = derived_moments_of(job, Ptr{Cvoid}(C_NULL))
+function derived_rhat_of(job::HIPMCJob, comm::Ptr{Cvoid})
+    K = derived_of(job)[1]
+    r = newarray(Float64, K); m = similar(r); w = similar(r); b = similar(r); nc = Ref{UInt64}(0); np = Ref{Int64}(0)
+    check(ccall((:klara_gather_derived_rhat, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{UInt64}, Ref{Int64}),
+                job.handle, comm, r, m, w, b, nc, np), "klara_gather_derived_rhat")
+    (r, m, w, b, nc[], np[])
+end
+# R-hat of the outputs (the plain form of rhat): (rhat, mean of the chain means, wsum, bsum, chains, samples per chain)
+gather_derived_rhat(job::HIPMCJob, comm::HIPComm) = derived_rhat_of(job, comm.handle)
+derivedrhat(job::HIPMCJob) = derived_rhat_of(job, Ptr{Cvoid}(C_NULL))
+function derived_marginals_of(job::HIPMCJob)
+    dm = derived_of(job)[2]
+    dm === nothing && error("the job's Derived was built without marginals=(nbins, lo, hi)")
+    dm
+end
+function derived_histogram_of(job::HIPMCJob, comm::Ptr{Cvoid})
+    K = derived_of(job)[1]
+    nb, lo, hi = derived_marginals_of(job)
+    counts = zeros(UInt64, nb + 2, K); ns = Ref{UInt64}(0); nc = Ref{UInt64}(0)
+    check(ccall((:klara_gather_derived_histogram, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{UInt64}, Ref{UInt64}, Ref{UInt64}),
+                job.handle, comm, counts, ns, nc), "klara_gather_derived_histogram")
+    (counts, histogram_edges(nb, lo, hi), ns[], nc[])
+end
+# the pooled histograms of the outputs, as pooledhistogram's of the coordinates: (counts (nbins + 2) x nout, edges, nsamples, chains)
+gather_derived_histogram(job::HIPMCJob, comm::HIPComm) = derived_histogram_of(job, comm.handle)
+derivedhistogram(job::HIPMCJob) = derived_histogram_of(job, Ptr{Cvoid}(C_NULL))
+# quantiles of the outputs from those counts (klara_histogram_quantiles): length(probs) x nout
+function derivedquantiles(job::HIPMCJob, probs)
+    nb, lo, hi = derived_marginals_of(job)
+    quantiles_of(derivedhistogram(job)[1], nb, lo, hi, probs)
+end
+# compile a derived-quantity closure for gfx950 as klara_create would, without a GPU; the compiler's log on failure
+function check_derived(src::String, ndims::Integer, nout::Integer)
+    st = ccall((:klara_check_derived, lib), Cint, (Cstring, Cint, Cint), src, ndims, nout)
+    st == 0 || error(unsafe_string(ccall((:klara_compile_log, lib), Cstring, ())))
+    true
 end
 # The Gelman–Rubin diagnostic over all chains (klara_gather_rhat; Klara has no counterpart: its job is one chain): (rhat, mean of the chain means, wsum =
 # sum of the chains' M2, bsum = sum (chain mean - mean)^2, units, samples per unit).  split=false works from the running sums; split=true is the split

@@ -33,6 +33,7 @@ MON_ACCEPT, MON_HISTORY, MON_SUMMARIES, MON_HIST_LT, MON_HIST_GRAD, MON_HIST_LLL
 MON_COVARIANCE = 0x40            # KLARA_MON_COVARIANCE: the pooled D x D cross-products, accumulated while sampling (klara_gather_covariance)
 COV_MAX_DIMS = 256                # KLARA_COV_MAX_DIMS
 MARG_MAX_BINS = 1024              # KLARA_MARG_MAX_BINS
+DERIVED_MAX_OUT = 64              # KLARA_DERIVED_MAX_OUT
 
 ZV_LINEAR, ZV_QUADRATIC, ZV_MAX_TERMS = 1, 2, 128      # KLARA_ZV_*
 ESS_STREAMED, ESS_HISTORY, ESS_SPLIT = 0, 1, 2           # KLARA_ESS_*: the modes of klara_gather_ess
@@ -66,6 +67,8 @@ class KlaraDesc(C.Structure):
         ("ram_S0", _dp), ("ram_targetrate", C.c_double), ("ram_gamma", C.c_double),
         ("marg_lo", _dp), ("marg_hi", _dp), ("marg_nbins", C.c_int64),
         ("seed", C.c_uint64), ("monitor", C.c_uint32), ("steps_per_launch", C.c_int32),
+        ("derived_src", C.c_char_p), ("derived_data", _dp), ("derived_ndata", C.c_int64), ("derived_nout", C.c_int64), ("derived_nbins", C.c_int64),
+        ("derived_lo", _dp), ("derived_hi", _dp),
         ("stream", C.c_void_p),
     ]
 
@@ -94,6 +97,8 @@ EXPORTS = [
     "klara_gather_rhat", "klara_selftest_rhat",
     "klara_gather_ess", "klara_selftest_ess", "klara_selftest_ess_ranks",
     "klara_gather_histogram", "klara_histogram_quantiles", "klara_selftest_marginals", "klara_selftest_histogram_ranks",
+    "klara_get_derived_sums", "klara_gather_derived_moments", "klara_gather_derived_rhat", "klara_gather_derived_histogram", "klara_check_derived",
+    "klara_selftest_derived_plan", "klara_selftest_derived",
     "klara_check_custom_target", "klara_check_custom_target_softabs", "klara_compile_log", "klara_selftest_plan", "klara_selftest_canary", "klara_abi_version",
 ]
 
@@ -178,6 +183,14 @@ def load() -> C.CDLL:
         "klara_selftest_marginals": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                      C.c_void_p],
         "klara_selftest_histogram_ranks": [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p],
+        "klara_get_derived_sums": [H, C.c_void_p, C.c_void_p, i64p],
+        "klara_gather_derived_moments": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+        "klara_gather_derived_rhat": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+        "klara_gather_derived_histogram": [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+        "klara_check_derived": [C.c_char_p, C.c_int32, C.c_int32],
+        "klara_selftest_derived_plan": [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), i64p, i64p],
+        "klara_selftest_derived": [C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_selftest_canary": [C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
         "klara_check_custom_target": [C.c_char_p, C.c_int32, C.c_int32],
         "klara_check_custom_target_softabs": [C.c_char_p, C.c_int32],

@@ -514,6 +514,38 @@ def pooled_quantiles(job_or_chains, probs, comm=None) -> np.ndarray:
     return histogram_quantiles(counts, m.nbins, m.lo, m.hi, probs)
 
 
+def derived_mean(job_or_chains, comm=None) -> np.ndarray:
+    """(K,) posterior mean of every output of the job's derived= closure over all chains and saved steps (Engine.derived_moments); `comm`: a klara_comm
+    handle, to pool over every rank's chains."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    return job.engine.derived_moments(comm)[0]
+
+
+def derived_var(job_or_chains, comm=None) -> np.ndarray:
+    """(K,) pooled variance M2 / n of every output of the job's derived= closure — var(chain) over the pooled chains, without the cancellation of
+    sumsq / n - mean^2 (Engine.derived_moments)."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    _, m2, ns, _ = job.engine.derived_moments(comm)
+    if ns < 1:
+        raise ValueError("derived_var needs at least one saved sample")
+    return m2 / ns
+
+
+def derived_rhat(job_or_chains, comm=None) -> np.ndarray:
+    """(K,) R-hat of every output of the job's derived= closure over all chains, from their running sums (Engine.derived_rhat)."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    return job.engine.derived_rhat(comm)["rhat"]
+
+
+def derived_quantiles(job_or_chains, probs, comm=None) -> np.ndarray:
+    """(K, len(probs)) posterior quantiles of the outputs of a derived= closure built with marginals=, from their pooled histograms
+    (Engine.derived_histogram, klara_histogram_quantiles): as pooled_quantiles for the coordinates."""
+    job = getattr(job_or_chains, "_job", job_or_chains)
+    counts, _, _, _ = job.engine.derived_histogram(comm)
+    m = job.engine.derived.marginals
+    return histogram_quantiles(counts, m.nbins, m.lo, m.hi, probs)
+
+
 def rhat(job_or_chains, split: bool = False, comm=None) -> np.ndarray:
     """The potential scale reduction factor R-hat (Gelman & Rubin 1992) per dimension over all chains of a job, formed on the device (Engine.rhat):
     from the running sums, or with split=True the split form (BDA3 section 11.4) from the stored history; `comm`: a klara_comm handle, to take every
@@ -596,12 +628,14 @@ class BasicMCJob:
     `chain_mcvar(chain, "imse" | "ipse", maxlag=acov_maxlag)` (autocovariances accumulated while sampling); `covariance=True` accumulates the
     pooled D x D cross-products of all chains' saved samples on the matrix cores (`pooled_cov`, `pooled_cor`), again with no stored history;
     `marginals=Marginals(nbins, lo, hi)` counts every dimension's saved samples into bins (`pooled_hist`, `pooled_quantiles`), likewise.
+    `derived=Derived(nout, source, data, marginals)` evaluates a user function of the state on every saved sample of every chain and sums its outputs
+    (`derived_mean`, `derived_var`, `derived_rhat`, `derived_quantiles`), likewise.
     """
 
     def __init__(self, model: GenericModel, sampler: MCSampler, mcrange: BasicMCRange, v0: Dict[str, Sequence],
                  tuner: Optional[MCTuner] = None, outopts: Optional[dict] = None, *, seed: Optional[int] = None,
                  chain_offset: int = 0, device: int = 0, steps_per_launch: int = 0, summaries: bool = True,
-                 bm_batchlen: int = 0, acov_maxlag: int = 0, sparse_moves: int = 0, covariance: bool = False, marginals=None):
+                 bm_batchlen: int = 0, acov_maxlag: int = 0, sparse_moves: int = 0, covariance: bool = False, marginals=None, derived=None):
         self.model, self.sampler, self.range = model, sampler, mcrange
         self.seed = _next_job_seed() if seed is None else int(seed)
         seed = self.seed
@@ -657,7 +691,7 @@ class BasicMCJob:
                   burnin=mcrange.burnin, thinning=mcrange.thinning, tuner=self.tuner.kind,
                   period=self.tuner.period, verbose=self.tuner.verbose, seed=seed, chain_offset=chain_offset,
                   device=device, monitor=monitor, steps_per_launch=steps_per_launch, bm_batchlen=int(bm_batchlen),
-                  acov_maxlag=int(acov_maxlag), sparse_moves=int(sparse_moves), marginals=marginals,
+                  acov_maxlag=int(acov_maxlag), sparse_moves=int(sparse_moves), marginals=marginals, derived=derived,
                   hist_ring_cols=int(self.outopts["chunk"]) if self.outopts["destination"] == "iostream" else 0)
         self.bm_batchlen, self.acov_maxlag = int(bm_batchlen), int(acov_maxlag)
         if isinstance(sampler, MH):

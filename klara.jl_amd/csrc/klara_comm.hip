@@ -193,36 +193,45 @@ static bool comm_merge(CommSeq& q, const MergeLayout& L, unsigned long long cnt[
     return !q.bad;
 }
 
+klara_status gather_moments_arrays(klara_handle* h, klara_comm* c, int W, const double* sum, const double* sumsq, const double* X, const long long* held,
+                                   const unsigned long long* naccept, long long nsaved, double* partial, double* out, double* mean, double* m2,
+                                   uint64_t* nsamples, uint64_t* naccept_out, uint64_t* ntransitions, uint64_t* nchains)
+{
+    const size_t D = (size_t)W;
+    const long long N = (long long)h->d.nchains;
+    const MergeLayout L{ D, D };
+    unsigned long long cnt[MergeLayout::NCOUNTERS];
+    local_counters(h, nsaved, cnt);
+    std::vector<double> host(L.size());
+    if (!c) {                                                               // this handle's chains only: mean | M2 | accept total
+        HIPCHK(pool_moments_async(h->stream, sum, sumsq, X, held, naccept, N, W, nsaved, partial, out));
+        HIPCHK(hipMemcpyAsync(host.data(), out, (L.counters() + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        memcpy(&cnt[0], host.data() + L.counters(), sizeof(cnt[0]));
+    } else {
+        HIPCHK(comm_reserve(c, L.size()));
+        CommSeq q{ c, h->stream };
+        q.H(pool_moments_async(h->stream, sum, sumsq, X, held, naccept, N, W, nsaved, partial, c->buf));       // mean_r | M2_r | accept total = counter slot 0
+        q.H(hipMemcpyAsync(c->buf + L.counters() + 1, cnt + 1, 3 * sizeof(cnt[0]), hipMemcpyHostToDevice, h->stream));
+        if (!comm_merge(q, L, cnt, host)) return KLARA_ERR_HIP;
+    }
+    if (mean) memcpy(mean, host.data() + (c ? L.mean() : L.mean_r()), D * sizeof(double));
+    if (m2) memcpy(m2, host.data() + L.M(), D * sizeof(double));
+    if (naccept_out) *naccept_out = cnt[MergeLayout::ACCEPTED];
+    if (ntransitions) *ntransitions = cnt[MergeLayout::TRANSITIONS];
+    if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
+    if (nchains) *nchains = cnt[MergeLayout::CHAINS];
+    return KLARA_OK;
+}
+
 extern "C" klara_status klara_gather_moments(klara_handle* h, klara_comm* c, double* mean, double* m2, uint64_t* nsamples,
                                              uint64_t* naccept, uint64_t* ntransitions, uint64_t* nchains)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;
     if (!h->have_state || !h->sum) return KLARA_ERR_STATE;
     HIPCHK(hipSetDevice(h->d.device));
-    const size_t D = (size_t)h->d.ndims;
-    const MergeLayout L{ D, D };
-    unsigned long long cnt[MergeLayout::NCOUNTERS];
-    local_counters(h, h->nsaved, cnt);
-    std::vector<double> host(L.size());
-    if (!c) {                                                               // this handle's chains only: mean | M2 | accept total
-        HIPCHK(pool_moments_async(h, h->pooled_out));
-        HIPCHK(hipMemcpyAsync(host.data(), h->pooled_out, (L.counters() + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        memcpy(&cnt[0], host.data() + L.counters(), sizeof(cnt[0]));
-    } else {
-        HIPCHK(comm_reserve(c, L.size()));
-        CommSeq q{ c, h->stream };
-        q.H(pool_moments_async(h, c->buf));                                 // mean_r | M2_r | accept total = counter slot 0
-        q.H(hipMemcpyAsync(c->buf + L.counters() + 1, cnt + 1, 3 * sizeof(cnt[0]), hipMemcpyHostToDevice, h->stream));
-        if (!comm_merge(q, L, cnt, host)) return KLARA_ERR_HIP;
-    }
-    if (mean) memcpy(mean, host.data() + (c ? L.mean() : L.mean_r()), D * sizeof(double));
-    if (m2) memcpy(m2, host.data() + L.M(), D * sizeof(double));
-    if (naccept) *naccept = cnt[MergeLayout::ACCEPTED];
-    if (ntransitions) *ntransitions = cnt[MergeLayout::TRANSITIONS];
-    if (nsamples) *nsamples = cnt[MergeLayout::SAMPLES];
-    if (nchains) *nchains = cnt[MergeLayout::CHAINS];
-    return KLARA_OK;
+    return gather_moments_arrays(h, c, h->d.ndims, h->sum, h->sumsq, h->X, h->held, h->naccept, (long long)h->nsaved, h->pool_partial, h->pooled_out, mean, m2,
+                                 nsamples, naccept, ntransitions, nchains);
 }
 
 // The pooled covariance (klara_cov.h): this rank's (mean_r, M_r) from its accumulators, then — with a communicator — the D x D form of the same merge
@@ -267,28 +276,26 @@ extern "C" klara_status klara_gather_covariance(klara_handle* h, klara_comm* c, 
 // all return KLARA_ERR_STATE here — before the sum, whose length D (nbins + 2) would differ between ranks that differ in nbins.  (2) The 64-bit integer sum
 // of the counts and the two counters.  A local HIP failure before (1) is remembered and (1) is still entered; a rank that cannot read (1)'s result back
 // cannot know what the others decided and returns KLARA_ERR_HIP without entering (2).  NV comes from this rank's D: ranks of different ndims are not one job.
-extern "C" klara_status klara_gather_histogram(klara_handle* h, klara_comm* c, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains)
+klara_status gather_histogram_arrays(klara_handle* h, klara_comm* c, int W, const KMargGeom& geom, const unsigned long long* table, long long nsaved,
+                                     const double* lohi, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains)
 {
-    if (!h) return KLARA_ERR_INVALID_ARG;
-    if (!h->have_state || !h->marg_counts) return KLARA_ERR_STATE;
-    HIPCHK(hipSetDevice(h->d.device));
-    const size_t D = (size_t)h->d.ndims, K = klara_marg_count_elems(h->marg), NV = 2 * D + 1;
-    const uint64_t cnt[2] = { (uint64_t)h->marg_n * (uint64_t)h->d.nchains, (uint64_t)h->d.nchains };
+    const size_t D = (size_t)W, K = klara_marg_count_elems(geom), NV = 2 * D + 1;
+    const uint64_t cnt[2] = { (uint64_t)nsaved * (uint64_t)h->d.nchains, (uint64_t)h->d.nchains };
     std::vector<uint64_t> host(K + 2);                          // counts | saved samples, chains
     if (!c) {
-        HIPCHK(hipMemcpyAsync(host.data(), h->marg_counts, K * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(host.data(), table, K * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         memcpy(host.data() + K, cnt, sizeof(cnt));
     } else {
         HIPCHK(comm_reserve(c, 2 * NV + K + 2));
         std::vector<uint64_t> v(2 * NV);
-        klara_marg_agreement_words(h->marg.nbins, h->marg_host.data(), h->marg_host.data() + D, (int32_t)D, v.data());
+        klara_marg_agreement_words(geom.nbins, lohi, lohi + D, (int32_t)D, v.data());
         CommSeq q{ c, h->stream };
         q.H(hipMemcpyAsync(c->buf, v.data(), v.size() * sizeof(uint64_t), hipMemcpyHostToDevice, h->stream));
         q.reduce(0, 2 * NV, true, ncclMax);
         if (!q.finish(v.data(), v.size() * sizeof(uint64_t))) return KLARA_ERR_HIP;
         if (!klara_marg_words_agree(v.data(), NV)) return KLARA_ERR_STATE;      // the same verdict on every rank: none enters the sum
-        q.H(hipMemcpyAsync(c->buf + 2 * NV, h->marg_counts, K * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
+        q.H(hipMemcpyAsync(c->buf + 2 * NV, table, K * sizeof(uint64_t), hipMemcpyDeviceToDevice, h->stream));
         q.H(hipMemcpyAsync(c->buf + 2 * NV + K, cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream));
         q.reduce(2 * NV, K + 2, true);
         q.H(hipMemcpyAsync(host.data(), c->buf + 2 * NV, host.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
@@ -299,6 +306,14 @@ extern "C" klara_status klara_gather_histogram(klara_handle* h, klara_comm* c, u
     if (nsamples) *nsamples = host[K];
     if (nchains) *nchains = host[K + 1];
     return KLARA_OK;
+}
+
+extern "C" klara_status klara_gather_histogram(klara_handle* h, klara_comm* c, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains)
+{
+    if (!h) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state || !h->marg_counts) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    return gather_histogram_arrays(h, c, h->d.ndims, h->marg, h->marg_counts, h->marg_n, h->marg_host.data(), counts, nsamples, nchains);
 }
 
 // ---- the Gelman–Rubin diagnostic (klara_rhat.h): the same merge with units (chains, or half-chains) where the samples stand — rank r stages the mean of
@@ -329,34 +344,31 @@ klara_status rhat_finish(size_t D, const double* host, bool merged, double* rhat
     return KLARA_OK;
 }
 
-extern "C" klara_status klara_gather_rhat(klara_handle* h, klara_comm* c, int32_t split, double* rhat, double* mean, double* wsum, double* bsum,
-                                          uint64_t* nchains, int64_t* nper)
+klara_status gather_rhat_arrays(klara_handle* h, klara_comm* c, int32_t split, int W, const double* sum, const double* sumsq, const double* X,
+                                const long long* held, long long nsaved, double** ws, double* rhat, double* mean, double* wsum, double* bsum, uint64_t* nchains,
+                                int64_t* nper)
 {
-    if (!h) return KLARA_ERR_INVALID_ARG;
-    if (!h->have_state) return KLARA_ERR_STATE;
-    if (split ? (!h->hist || h->ring || !(h->d.monitor & KLARA_MON_HISTORY)) : !h->sum) return KLARA_ERR_STATE;   // (split: needs every saved step)
-    HIPCHK(hipSetDevice(h->d.device));
-    const int D = h->d.ndims;
+    const int D = W;
     const long long N = h->d.nchains;
     const MergeLayout L{ (size_t)D, (size_t)D, (size_t)D };
-    if (!h->rhat_ws) HIPCHK(h->mem.alloc(&h->rhat_ws, klara_rhat_partial_elems(D) + L.size()));
+    if (!*ws) HIPCHK(h->mem.alloc(ws, klara_rhat_partial_elems(D) + L.size()));
     if (split && !h->rhat_half) HIPCHK(h->mem.alloc(&h->rhat_half, (size_t)4 * (size_t)N * (size_t)D));
     // units and samples per unit.  A split of 1 to 3 saved steps is refused, but only after the reductions: no rank leaves the others waiting in theirs
-    const long long nsaved = h->nsaved, n = split ? nsaved / 2 : nsaved;
+    const long long n = split ? nsaved / 2 : nsaved;
     const bool too_short = split && nsaved > 0 && nsaved < 4;
     unsigned long long cnt[MergeLayout::NCOUNTERS];
     rhat_counters((unsigned long long)(split ? 2 * N : N), (unsigned long long)n, cnt);
     const auto stage = [&](double* buf) -> hipError_t {                     // zeros | this rank's mean_r, Bsum_r, Wsum_r | its counters
         hipError_t e = hipMemsetAsync(buf, 0, L.size() * sizeof(double), h->stream);
         if (e == hipSuccess && n > 0 && !too_short)
-            e = split ? rhat_split_async(h->stream, h->hist, nsaved, N, D, h->rhat_half, h->rhat_ws, buf + L.mean_r(), buf + L.extra())
-                      : rhat_sums_async(h->stream, h->sum, h->sumsq, h->X, h->held, N, D, nsaved, h->rhat_ws, buf + L.mean_r(), buf + L.extra());
+            e = split ? rhat_split_async(h->stream, h->hist, nsaved, N, D, h->rhat_half, *ws, buf + L.mean_r(), buf + L.extra())
+                      : rhat_sums_async(h->stream, sum, sumsq, X, held, N, D, nsaved, *ws, buf + L.mean_r(), buf + L.extra());
         if (e == hipSuccess) e = hipMemcpyAsync(buf + L.counters(), cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream);
         return e;
     };
     std::vector<double> host(L.size());
     if (!c) {
-        double* buf = h->rhat_ws + klara_rhat_partial_elems(D);
+        double* buf = *ws + klara_rhat_partial_elems(D);
         HIPCHK(stage(buf));
         HIPCHK(hipMemcpyAsync(host.data(), buf, L.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -368,6 +380,17 @@ extern "C" klara_status klara_gather_rhat(klara_handle* h, klara_comm* c, int32_
     }
     const klara_status st = rhat_finish((size_t)D, host.data(), c != nullptr, rhat, mean, wsum, bsum, nchains, nper);
     return st != KLARA_OK ? st : too_short ? KLARA_ERR_STATE : KLARA_OK;
+}
+
+// (the split form reads the stored history of the coordinates: W = ndims only)
+extern "C" klara_status klara_gather_rhat(klara_handle* h, klara_comm* c, int32_t split, double* rhat, double* mean, double* wsum, double* bsum,
+                                          uint64_t* nchains, int64_t* nper)
+{
+    if (!h) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    if (split ? (!h->hist || h->ring || !(h->d.monitor & KLARA_MON_HISTORY)) : !h->sum) return KLARA_ERR_STATE;   // (split: needs every saved step)
+    HIPCHK(hipSetDevice(h->d.device));
+    return gather_rhat_arrays(h, c, split, h->d.ndims, h->sum, h->sumsq, h->X, h->held, (long long)h->nsaved, &h->rhat_ws, rhat, mean, wsum, bsum, nchains, nper);
 }
 
 // ---- the pooled effective sample size (klara_ess.h): R-hat's merge with the units' lagged sums riding in the X slot — rank r stages the mean of its units'

@@ -92,6 +92,13 @@ static klara_status validate_fields(const klara_desc* d)
     if (d->marg_nbins == 0 ? (d->marg_lo != nullptr || d->marg_hi != nullptr) : (!d->marg_lo || !d->marg_hi)) return KLARA_ERR_INVALID_ARG;
     for (int i = 0; d->marg_nbins > 0 && i < d->ndims; ++i)
         if (!std::isfinite(d->marg_lo[i]) || !std::isfinite(d->marg_hi[i]) || !(d->marg_lo[i] < d->marg_hi[i])) return KLARA_ERR_INVALID_ARG;
+    // derived quantities: 0 = off and nothing else set; a source and 1 .. KLARA_DERIVED_MAX_OUT outputs; histograms of the outputs as the marginals' fields
+    if (d->derived_nout < 0 || d->derived_nout > KLARA_DERIVED_MAX_OUT || (d->derived_src != nullptr) != (d->derived_nout > 0)) return KLARA_ERR_INVALID_ARG;
+    if (d->derived_ndata < 0 || (d->derived_ndata > 0) != (d->derived_data != nullptr) || (d->derived_ndata > 0 && d->derived_nout == 0)) return KLARA_ERR_INVALID_ARG;
+    if (d->derived_nbins < 0 || d->derived_nbins > KLARA_MARG_MAX_BINS || (d->derived_nbins > 0 && d->derived_nout == 0)) return KLARA_ERR_INVALID_ARG;
+    if (d->derived_nbins == 0 ? (d->derived_lo != nullptr || d->derived_hi != nullptr) : (!d->derived_lo || !d->derived_hi)) return KLARA_ERR_INVALID_ARG;
+    for (int64_t i = 0; d->derived_nbins > 0 && i < d->derived_nout; ++i)
+        if (!std::isfinite(d->derived_lo[i]) || !std::isfinite(d->derived_hi[i]) || !(d->derived_lo[i] < d->derived_hi[i])) return KLARA_ERR_INVALID_ARG;
     if (d->steps_per_launch < 0 || d->tuner_score < 0 || d->tuner_score > 1) return KLARA_ERR_INVALID_ARG;   // (int32: a launch length always fits KLaunch::nsteps)
     return KLARA_OK;
 }
@@ -126,6 +133,7 @@ static bool free_all(klara_handle* h)
     if (h->auto_mirror) hipHostFree(h->auto_mirror);
     if (h->flag_host) hipHostFree(h->flag_host);
     klara_jit_destroy(h->jit);
+    klara_jit_destroy(h->der_jit);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     for (int j = 0; j < 3; ++j) { if (h->side[j]) hipStreamDestroy(h->side[j]); if (h->join_ev[j]) hipEventDestroy(h->join_ev[j]); }
@@ -324,7 +332,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
         h->accept_cap = desc->nsteps;
         HIPCHK(mem.alloc(&h->accept, (size_t)desc->nsteps * N));
     }
-    const bool acov = desc->acov_maxlag > 0, cov = plan.cov, marg = desc->marg_nbins > 0, keeps = acov || cov || marg;      // the consumers of the saved samples keep values
+    const bool acov = desc->acov_maxlag > 0, cov = plan.cov, marg = desc->marg_nbins > 0, der = desc->derived_nout > 0, keeps = acov || cov || marg || der;      // the consumers of the saved samples keep values
     if ((desc->monitor & (KLARA_MON_HISTORY | KLARA_MON_HIST_LT | KLARA_MON_HIST_GRAD | KLARA_MON_HIST_LLLP)) || keeps) {
         // npoststeps = length((burnin+1):thinning:nsteps)  (BasicMCRange.jl:26)
         h->hist_cols = (desc->nsteps - desc->burnin - 1) / desc->thinning + 1;
@@ -353,6 +361,29 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
             KCHK(upload(mem, &h->marg_par, par.data(), par.size()));
             HIPCHK(mem.alloc(&h->marg_counts, klara_marg_count_elems(h->marg)));
             HIPCHK(hipMemset(h->marg_counts, 0, klara_marg_count_elems(h->marg) * sizeof(unsigned long long)));
+        }
+        if (der) {                                               // the closure's kernel, its data block and the chains' sums; the reductions' workspaces
+            const int K = (int)desc->derived_nout;
+            const size_t NK = N * (size_t)K;
+            if (!klara_derived_plan((long long)N, (int)D, K, &h->der)) return KLARA_ERR_UNSUPPORTED;
+            KCHK(klara_jit_create_derived(desc->derived_src, (int)D, K, desc->derived_nbins > 0, true, &h->der_jit));
+            if (desc->derived_ndata > 0) KCHK(upload(mem, &h->der_data, desc->derived_data, (size_t)desc->derived_ndata));
+            h->der_ndata = desc->derived_ndata;
+            HIPCHK(mem.alloc(&h->der_sum, NK)); HIPCHK(mem.alloc(&h->der_sumsq, NK)); HIPCHK(mem.alloc(&h->der_zero, N));
+            HIPCHK(hipMemset(h->der_sum, 0, NK * sizeof(double))); HIPCHK(hipMemset(h->der_sumsq, 0, NK * sizeof(double)));
+            HIPCHK(hipMemset(h->der_zero, 0, N * sizeof(long long)));
+            HIPCHK(mem.alloc(&h->der_partial, (size_t)1024 * (2 * (size_t)K + 1))); HIPCHK(mem.alloc(&h->der_out, 2 * (size_t)K + 2));
+            if (desc->derived_nbins > 0) {
+                if (!klara_marg_plan((long long)N, K, desc->derived_nbins, &h->der_marg)) return KLARA_ERR_UNSUPPORTED;
+                h->der_marg_host.assign(desc->derived_lo, desc->derived_lo + K);
+                h->der_marg_host.insert(h->der_marg_host.end(), desc->derived_hi, desc->derived_hi + K);
+                std::vector<double> par(h->der_marg_host);
+                for (int i = 0; i < K; ++i) par.push_back(klara_marg_inv_w(desc->derived_nbins, desc->derived_lo[i], desc->derived_hi[i]));
+                KCHK(upload(mem, &h->der_marg_par, par.data(), par.size()));
+                HIPCHK(mem.alloc(&h->der_stage, (size_t)KLARA_DERIVED_MAX_COLS * NK));
+                HIPCHK(mem.alloc(&h->der_counts, klara_marg_count_elems(h->der_marg)));
+                HIPCHK(hipMemset(h->der_counts, 0, klara_marg_count_elems(h->der_marg) * sizeof(unsigned long long)));
+            }
         }
         if (desc->monitor & KLARA_MON_HIST_LT) HIPCHK(mem.alloc(&h->hist_lt, (size_t)h->hist_cols * N));
         if (desc->monitor & KLARA_MON_HIST_LLLP) { HIPCHK(mem.alloc(&h->hist_ll, (size_t)h->hist_cols * N)); HIPCHK(mem.alloc(&h->hist_lp, (size_t)h->hist_cols * N)); }
@@ -409,6 +440,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     h->d.mh_sigma = nullptr; h->d.slice_widths = nullptr; h->d.gauss_w = nullptr; h->d.gauss_mu = nullptr;
     h->d.gauss_prec = nullptr; h->d.logit_X = nullptr; h->d.logit_y = nullptr; h->d.hier_Y = nullptr; h->d.hier_xc = nullptr; h->d.stream = nullptr;
     h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.am_C0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
+    h->d.derived_src = nullptr; h->d.derived_data = nullptr; h->d.derived_lo = nullptr; h->d.derived_hi = nullptr;
     {   // static kernel parameters live in device memory (read with scalar loads at the point of use)
         const KParams hp = make_params(h);
         HIPCHK(mem.alloc(&h->d_params, 1));

@@ -11,6 +11,7 @@
 #include "klara_plan.h"
 #include "klara_cov.h"
 #include "klara_marg.h"
+#include "klara_derived.h"
 
 #define HIPCHK(expr)                                                                   \
     do {                                                                               \
@@ -69,6 +70,15 @@ struct klara_handle {
     // pooled marginal histograms (klara_desc.marg_nbins > 0, klara_marg.h): lo | hi | inv_w, the uint64 [D][nbins + 2] table; saved steps consumed
     KMargGeom marg = {}; double* marg_par = nullptr; unsigned long long* marg_counts = nullptr; long long marg_n = 0;
     std::vector<double> marg_host;  // lo | hi as given at create: what klara_gather_histogram compares between ranks
+    // derived quantities (klara_desc.derived_nout > 0, klara_derived.h): the kernel compiled with the user's closure (a second run-time module beside `jit`), its
+    // geometry and data block, the chains' sums [N][K]; N zeros that stand where the coordinate reductions read `held` and `naccept`; the reductions' workspaces
+    // (moments: stage-1 partials and mean | M2 | accept word; R-hat: allocated at its first call); with derived_nbins > 0 the staging array [32][N][K], the
+    // histogram's geometry over (N, K, nbins), lo | hi | inv_w, the uint64 [K][nbins + 2] table and lo | hi as given at create; saved steps consumed
+    KlaraJit* der_jit = nullptr; KDerivedGeom der = {}; double* der_data = nullptr; long long der_ndata = 0;
+    double *der_sum = nullptr, *der_sumsq = nullptr; long long* der_zero = nullptr;
+    double *der_partial = nullptr, *der_out = nullptr, *der_rhat_ws = nullptr;
+    double* der_stage = nullptr; KMargGeom der_marg = {}; double* der_marg_par = nullptr; unsigned long long* der_counts = nullptr;
+    std::vector<double> der_marg_host; long long der_n = 0;
     double *hist_lt = nullptr, *hist_g = nullptr, *hist_ll = nullptr, *hist_lp = nullptr;
     unsigned long long* clock_probe = nullptr;        // pair-transposed kernels: (s_memtime, s_memrealtime) at the end / start of one workgroup of the last launch
     bool pair_enqueued = false;                       // a launch of this handle has enqueued both kernel families (their one-time scratch set-up is behind us)
@@ -142,6 +152,24 @@ hipError_t pool_moments_async(hipStream_t stream, const double* sum, const doubl
                               const unsigned long long* naccept, long long N, int D, long long nsaved, double* partial, double* out);
 hipError_t pool_summaries_async(klara_handle* h, bool with_sums, double* out);      // ... with the handle's arrays, on its stream
 hipError_t pool_moments_async(klara_handle* h, double* out);
+
+// ---- klara_derived.hip: the derived-quantity update on plain buffers (the job path and klara_selftest_derived run the same function): columns
+// [col0, col0 + m) of hist through k_derived_update in pieces of at most KLARA_DERIVED_MAX_COLS; with a staging array each piece's outputs then go through
+// klara_marg_launch_update (marg, par, counts; skipped when counts is null) and, when values_out is not null, to values_out + (piece's first column) N K
+hipError_t klara_derived_launch_update(KlaraJit* jit, const KDerivedGeom& g, const double* hist, long long col0, long long m, const double* data, long long ndata,
+                                       double* dsum, double* dsumsq, double* stage, const KMargGeom* marg, const double* par, unsigned long long* counts,
+                                       double* values_out, hipStream_t st);
+
+// ---- klara_comm.hip: the bodies of klara_gather_moments, klara_gather_rhat and klara_gather_histogram over arrays of any width W (the coordinates: W = ndims,
+// the handle's own arrays; the derived quantities: W = derived_nout) — per-chain sums N x W, the state and sojourn counts the reductions read, workspaces
+struct klara_comm;
+klara_status gather_moments_arrays(klara_handle* h, klara_comm* c, int W, const double* sum, const double* sumsq, const double* X, const long long* held,
+                                   const unsigned long long* naccept, long long nsaved, double* partial, double* out, double* mean, double* m2,
+                                   uint64_t* nsamples, uint64_t* naccept_out, uint64_t* ntransitions, uint64_t* nchains);
+klara_status gather_rhat_arrays(klara_handle* h, klara_comm* c, int32_t split, int W, const double* sum, const double* sumsq, const double* X,
+                                const long long* held, long long nsaved, double** ws, double* rhat, double* mean, double* wsum, double* bsum, uint64_t* nchains, int64_t* nper);
+klara_status gather_histogram_arrays(klara_handle* h, klara_comm* c, int W, const KMargGeom& geom, const unsigned long long* table, long long nsaved,
+                                     const double* lohi, uint64_t* counts, uint64_t* nsamples, uint64_t* nchains);
 
 // ---- klara_comm.hip: the between-rank merge of the pooled moments, the pooled covariance and R-hat — its staging layout, its rank-local steps and the one
 // sequence of reductions that the gather calls and the simulated-rank self tests both run

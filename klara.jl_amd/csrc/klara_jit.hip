@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include "klara_plan.h"
+#include "klara_derived.h"
 #include "klara_jit_headers.inc"
 
 namespace {
@@ -199,18 +200,13 @@ std::string init_expr(int sampler, int E, int G)
     return b;
 }
 
-// compile (or fetch) the code object of one (source, sampler, D, modes) combination
-klara_status compile(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, const CodeObject** out, const PairForm* pf = nullptr,
-                     bool softabs = false)
+// The part every run-time compiled translation unit goes through: the code object of `key` from this process' cache or the disk cache, else `tu` compiled
+// for gfx950 with the library's arithmetic contract, the lowered names of `ie` (kept as the code object's init_name) and of te[i] (as trans_names[modes[i]])
+// looked up, and the result stored in both caches.  The caller has cleared g_log and found libhiprtc.
+klara_status compile_tu(const std::string& key, const std::string& tu, const char* tu_name, const std::string& ie, const std::vector<std::string>& te,
+                        const int* modes, int nmodes, const CodeObject** out)
 {
-    g_log.clear();
     Rtc* r = rtc();
-    if (!r->ok) { g_log = "libhiprtc.so could not be loaded"; return KLARA_ERR_UNSUPPORTED; }
-    std::string key = std::to_string(sampler) + "/" + std::to_string(D) + "/" + std::to_string(E) + "x" + std::to_string(G) + "/";
-    if (pf) key += "pair/" + std::to_string(pf->NP) + "/" + std::to_string(pf->Q) + "/" + std::to_string((int)pf->mon) + std::to_string((int)pf->tune) + std::to_string((int)pf->da) + "/";
-    for (int i = 0; i < nmodes; ++i) key += std::to_string(modes[i]) + ",";
-    if (softabs) key += "softabs/";
-    key += (getenv("KLARA_JIT_UNROLL_MAX_E") ? getenv("KLARA_JIT_UNROLL_MAX_E") : ""); key += "\n"; key += src;
     {
         std::lock_guard<std::mutex> lk(g_cache_mutex);
         auto it = g_cache.find(key);
@@ -234,6 +230,53 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
                 return KLARA_OK;
             }
         }
+    }
+    hiprtcProgram prog;
+    if (r->CreateProgram(&prog, tu.c_str(), tu_name, klara_jit_nheaders, klara_jit_header_sources, klara_jit_header_names) != HIPRTC_SUCCESS) {
+        g_log = "hiprtcCreateProgram failed";
+        return KLARA_ERR_COMPILE;
+    }
+    r->AddNameExpression(prog, ie.c_str());
+    for (int i = 0; i < nmodes; ++i) r->AddNameExpression(prog, te[i].c_str());
+    const hiprtcResult cr = r->CompileProgram(prog, (int)(sizeof opts / sizeof *opts), opts);
+    size_t ls = 0;
+    if (r->GetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) { g_log.resize(ls); r->GetProgramLog(prog, &g_log[0]); }
+    if (cr != HIPRTC_SUCCESS) { r->DestroyProgram(&prog); if (g_log.empty()) g_log = "compilation failed"; return KLARA_ERR_COMPILE; }
+    CodeObject co;
+    const char* low = nullptr;
+    bool ok = r->GetLoweredName(prog, ie.c_str(), &low) == HIPRTC_SUCCESS && low;
+    if (ok) co.init_name = low;
+    for (int i = 0; ok && i < nmodes; ++i) {
+        ok = r->GetLoweredName(prog, te[i].c_str(), &low) == HIPRTC_SUCCESS && low;
+        if (ok) co.trans_names[modes[i]] = low;
+    }
+    size_t cs = 0;
+    ok = ok && r->GetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
+    if (ok) { co.code.resize(cs); ok = r->GetCode(prog, co.code.data()) == HIPRTC_SUCCESS; }
+    r->DestroyProgram(&prog);
+    if (!ok) { g_log += "\n(could not retrieve the code object)"; return KLARA_ERR_COMPILE; }
+    if (!disk.empty()) cache_write(disk, co);
+    std::lock_guard<std::mutex> lk(g_cache_mutex);
+    auto ins = g_cache.emplace(key, std::move(co));
+    *out = &ins.first->second;
+    return KLARA_OK;
+}
+
+// compile (or fetch) the code object of one (source, sampler, D, modes) combination
+klara_status compile(const char* src, int sampler, int D, int E, int G, const int* modes, int nmodes, const CodeObject** out, const PairForm* pf = nullptr,
+                     bool softabs = false)
+{
+    g_log.clear();
+    if (!rtc()->ok) { g_log = "libhiprtc.so could not be loaded"; return KLARA_ERR_UNSUPPORTED; }
+    std::string key = std::to_string(sampler) + "/" + std::to_string(D) + "/" + std::to_string(E) + "x" + std::to_string(G) + "/";
+    if (pf) key += "pair/" + std::to_string(pf->NP) + "/" + std::to_string(pf->Q) + "/" + std::to_string((int)pf->mon) + std::to_string((int)pf->tune) + std::to_string((int)pf->da) + "/";
+    for (int i = 0; i < nmodes; ++i) key += std::to_string(modes[i]) + ",";
+    if (softabs) key += "softabs/";
+    key += (getenv("KLARA_JIT_UNROLL_MAX_E") ? getenv("KLARA_JIT_UNROLL_MAX_E") : ""); key += "\n"; key += src;
+    {
+        std::lock_guard<std::mutex> lk(g_cache_mutex);
+        auto it = g_cache.find(key);
+        if (it != g_cache.end()) { *out = &it->second; return KLARA_OK; }
     }
     // (MH, the slice sampler, RAM and AM evaluate no gradient: k_transitions<KLARA_SAMPLER_RAM, ...>, k_transitions<KLARA_SAMPLER_AM, ...> and k_init are instantiated
     //  by the names below like MH's)
@@ -279,38 +322,38 @@ klara_status compile(const char* src, int sampler, int D, int E, int G, const in
     // declared by now, so klara_diagt.h's USERPAIR branches can call it
     tu += pf ? "\n#line 1 \"klara_custom_pair_glue\"\n#include \"klara_diagt.h\"\n" : "\n#line 1 \"klara_custom_glue\"\n#include \"klara_custom.h\"\n";
 
-    hiprtcProgram prog;
-    if (r->CreateProgram(&prog, tu.c_str(), "klara_custom_target.hip", klara_jit_nheaders, klara_jit_header_sources,
-                         klara_jit_header_names) != HIPRTC_SUCCESS) {
-        g_log = "hiprtcCreateProgram failed";
+    const std::string ie = pf ? pair_init_expr(*pf) : init_expr(sampler, E, G);
+    std::vector<std::string> te;
+    for (int i = 0; i < nmodes; ++i) te.push_back(pf ? pair_trans_expr(sampler, *pf, modes[i]) : trans_expr(sampler, E, G, modes[i]));
+    return compile_tu(key, tu, "klara_custom_target.hip", ie, te, modes, nmodes, out);
+}
+
+// compile (or fetch) the derived-quantity kernel (klara_derived.h) of one (source, D, K, staging on / off) combination: a translation unit of its own —
+// the fixed-width typedefs, detmath.h, the user's text, the kernel — that never sees klara_kernels.h.  The 8 KB of math tables are staged into LDS only
+// for a text that names a kd_ function.
+klara_status compile_derived(const char* src, int D, int K, bool stage, const CodeObject** out)
+{
+    g_log.clear();
+    if (!rtc()->ok) { g_log = "libhiprtc.so could not be loaded"; return KLARA_ERR_UNSUPPORTED; }
+    if (strstr(src, "klara_user_derived") == nullptr) {
+        g_log = "a derived-quantity source needs KLARA_USER_FN void klara_user_derived(const double* x, int D, const double* data, long long ndata, double* out, int K)";
         return KLARA_ERR_COMPILE;
     }
-    const std::string ie = pf ? pair_init_expr(*pf) : init_expr(sampler, E, G);
-    r->AddNameExpression(prog, ie.c_str());
-    std::vector<std::string> te;
-    for (int i = 0; i < nmodes; ++i) { te.push_back(pf ? pair_trans_expr(sampler, *pf, modes[i]) : trans_expr(sampler, E, G, modes[i])); r->AddNameExpression(prog, te.back().c_str()); }
-    const hiprtcResult cr = r->CompileProgram(prog, (int)(sizeof opts / sizeof *opts), opts);
-    size_t ls = 0;
-    if (r->GetProgramLogSize(prog, &ls) == HIPRTC_SUCCESS && ls > 1) { g_log.resize(ls); r->GetProgramLog(prog, &g_log[0]); }
-    if (cr != HIPRTC_SUCCESS) { r->DestroyProgram(&prog); if (g_log.empty()) g_log = "compilation failed"; return KLARA_ERR_COMPILE; }
-    CodeObject co;
-    const char* low = nullptr;
-    bool ok = r->GetLoweredName(prog, ie.c_str(), &low) == HIPRTC_SUCCESS && low;
-    if (ok) co.init_name = low;
-    for (int i = 0; ok && i < nmodes; ++i) {
-        ok = r->GetLoweredName(prog, te[i].c_str(), &low) == HIPRTC_SUCCESS && low;
-        if (ok) co.trans_names[modes[i]] = low;
-    }
-    size_t cs = 0;
-    ok = ok && r->GetCodeSize(prog, &cs) == HIPRTC_SUCCESS && cs > 0;
-    if (ok) { co.code.resize(cs); ok = r->GetCode(prog, co.code.data()) == HIPRTC_SUCCESS; }
-    r->DestroyProgram(&prog);
-    if (!ok) { g_log += "\n(could not retrieve the code object)"; return KLARA_ERR_COMPILE; }
-    if (!disk.empty()) cache_write(disk, co);
-    std::lock_guard<std::mutex> lk(g_cache_mutex);
-    auto ins = g_cache.emplace(key, std::move(co));
-    *out = &ins.first->second;
-    return KLARA_OK;
+    KDerivedGeom g;
+    if (!klara_derived_plan(1, D, K, &g)) return KLARA_ERR_INVALID_ARG;
+    const std::string key = "derived/" + std::to_string(D) + "/" + std::to_string(K) + "/" + std::to_string((int)stage) + "\n" + src;
+    std::string tu;
+    tu += "#define KLARA_D " + std::to_string(D) + "\n#define KLARA_K " + std::to_string(K) + "\n";
+    tu += "#define KLARA_DERIVED_THREADS " + std::to_string(g.threads) + "\n#define KLARA_DERIVED_STAGE " + std::to_string((int)stage) + "\n";
+    if (strstr(src, "kd_") != nullptr) tu += "#define KLARA_DERIVED_TABLES 1\n";
+    tu += "typedef signed char int8_t; typedef unsigned char uint8_t; typedef short int16_t; typedef unsigned short uint16_t;\n"
+          "typedef int int32_t; typedef unsigned int uint32_t; typedef long long int64_t; typedef unsigned long long uint64_t;\n"
+          "#include \"detmath.h\"\n"
+          "#define KLARA_USER_FN static __device__ __forceinline__\n"
+          "#line 1 \"klara_user_derived\"\n";
+    tu += src;
+    tu += "\n#line 1 \"klara_derived_glue\"\n#define KLARA_DERIVED_KERNEL 1\n#include \"klara_derived.h\"\n";
+    return compile_tu(key, tu, "klara_derived.hip", "k_derived_update", std::vector<std::string>(), nullptr, 0, out);
 }
 
 }  // namespace
@@ -359,6 +402,29 @@ klara_status klara_jit_create(const char* src, int sampler, int D, int E, int G,
     if (!ok) { klara_jit_destroy(j); return KLARA_ERR_HIP; }
     *out = j;
     return KLARA_OK;
+}
+
+// the derived-quantity kernel: a module of its own, its one function kept as `init`
+klara_status klara_jit_create_derived(const char* src, int D, int K, bool stage, bool load, KlaraJit** out)
+{
+    const CodeObject* co = nullptr;
+    klara_status st = compile_derived(src, D, K, stage, &co);
+    if (st != KLARA_OK || !load) return st;
+    KlaraJit* j = new (std::nothrow) KlaraJit();
+    if (!j) return KLARA_ERR_NOMEM;
+    const bool ok = hipModuleLoadData(&j->mod, co->code.data()) == hipSuccess && hipModuleGetFunction(&j->init, j->mod, co->init_name.c_str()) == hipSuccess;
+    if (!ok) { klara_jit_destroy(j); return KLARA_ERR_HIP; }
+    *out = j;
+    return KLARA_OK;
+}
+
+hipError_t klara_jit_launch_derived(KlaraJit* j, const KDerivedGeom& g, const double* hist, long long col0, int m, const double* data, long long ndata,
+                                    double* dsum, double* dsumsq, double* stage, hipStream_t st)
+{
+    long long N = g.N;
+    int CH = g.CH;
+    void* args[] = { &hist, &N, &CH, &col0, &m, &data, &ndata, &dsum, &dsumsq, &stage };
+    return hipModuleLaunchKernel(j->init, (unsigned)g.nwg, 1, 1, (unsigned)g.threads, 1, 1, (unsigned)g.lds_bytes, st, args, nullptr);
 }
 
 void klara_jit_destroy(KlaraJit* j)

@@ -217,6 +217,13 @@ void klara_jit_destroy(KlaraJit* j);
 hipError_t klara_jit_launch_init(KlaraJit* j, const KParams& p, int needgrad, dim3 grid, size_t lds, hipStream_t st, int block = 256);
 hipError_t klara_jit_launch(KlaraJit* j, int mode, const KParams* p, const KLaunch& kl, dim3 grid, size_t lds, hipStream_t st, int block = 256);
 const char* klara_jit_log();
+// derived quantities (klara_desc.derived_nout > 0, klara_derived.h): k_derived_update compiled with the user's klara_user_derived for (D, K, staging on / off)
+// — a second module beside the target's, for any target family; load = false only compiles (klara_check_derived).  The launch is one piece of at most
+// KLARA_DERIVED_MAX_COLS columns.
+struct KDerivedGeom;
+klara_status klara_jit_create_derived(const char* src, int D, int K, bool stage, bool load, KlaraJit** out);
+hipError_t klara_jit_launch_derived(KlaraJit* j, const KDerivedGeom& g, const double* hist, long long col0, int m, const double* data, long long ndata,
+                                    double* dsum, double* dsumsq, double* stage, hipStream_t st);
 
 // the group-layout transition kernels' MODE — 7: mode 3 with exactly one transition per launch; 3: nothing counts/tunes and nothing is monitored;
 // 1: nothing counts/tunes; 0: general — from the launch's mode bits.  (The logistic target's data rows may need more LDS than a launch gets without asking.)

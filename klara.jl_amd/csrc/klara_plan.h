@@ -102,7 +102,7 @@ static bool diagt_eligible(const klara_desc& d, const KlaraOverrides& o)
 static bool slice_free_eligible(const klara_desc& d, const KlaraOverrides& o, bool plain)
 {
     const uint32_t lane_local = KLARA_MON_ACCEPT | KLARA_MON_SUMMARIES | KLARA_MON_HISTORY | KLARA_MON_HIST_LT | KLARA_MON_COVARIANCE;       // (the last one: a consumer's flag, no kernel sees it)
-    const bool values_kept = (d.monitor & KLARA_MON_HISTORY) != 0 || d.acov_maxlag > 0 || (d.monitor & KLARA_MON_COVARIANCE) != 0 || d.marg_nbins > 0;       // (the log-target history is formed from the saved values)
+    const bool values_kept = (d.monitor & KLARA_MON_HISTORY) != 0 || d.acov_maxlag > 0 || (d.monitor & KLARA_MON_COVARIANCE) != 0 || d.marg_nbins > 0 || d.derived_nout > 0;       // (the log-target history is formed from the saved values)
     return diagt_eligible(d, o) && d.sampler == KLARA_SAMPLER_SLICE && plain && !o.slice_lockstep &&
            (d.monitor & ~lane_local) == 0 && (!(d.monitor & KLARA_MON_HIST_LT) || values_kept);
 }
@@ -298,7 +298,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     klara_desc d = desc;
     p.cov = (d.monitor & KLARA_MON_COVARIANCE) != 0;
     d.monitor &= ~(uint32_t)KLARA_MON_COVARIANCE;                // (a consumer's flag: the kernels and the run-time compiler never see it)
-    if (d.acov_maxlag > 0 || p.cov || d.marg_nbins > 0) d.monitor |= KLARA_MON_HISTORY;       // (the streaming autocovariances and the pooled covariance keep values: klara_create turns the value history on)
+    if (d.acov_maxlag > 0 || p.cov || d.marg_nbins > 0 || d.derived_nout > 0) d.monitor |= KLARA_MON_HISTORY;       // (the streaming autocovariances and the pooled covariance keep values: klara_create turns the value history on)
     const int D = d.ndims;
     p.plain = !cnt_predicate(d) && d.tuner_mode == KLARA_TUNE_PER_CHAIN && d.tuner != KLARA_TUNER_DUAL_AVERAGING;
     // plain and nothing monitored -> MODE 3 and its one-transition-per-launch form 7; plain -> 1; general -> 0
@@ -350,7 +350,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
         int np = groups >= 4096 ? 2 : 1;                       // >= one full round of wavefronts (4 per SIMD) per partition
         if (d.nstreams >= 1 && d.nstreams <= 4) np = d.nstreams;
         if (d.tuner_mode == KLARA_TUNE_POOLED) np = 1;         // the pooled tuner update sits between launches, on one stream
-        if (d.acov_maxlag > 0 || p.cov || d.marg_nbins > 0) np = 1;                // ... and so does the consumer of the launch's saved samples
+        if (d.acov_maxlag > 0 || p.cov || d.marg_nbins > 0 || d.derived_nout > 0) np = 1;                // ... and so does the consumer of the launch's saved samples
         if (np > groups) np = (int)groups;
         p.nparts = np;
         // which kernel family runs a launch (q4_ok jobs: same bits either way); with running sums and no klara_desc.sparse_moves, the device decides

@@ -138,6 +138,12 @@ static klara_status init_common(klara_handle* h)
     h->cov_n = 0;
     if (h->marg_counts) HIPCHK(hipMemsetAsync(h->marg_counts, 0, klara_marg_count_elems(h->marg) * sizeof(unsigned long long), st));
     h->marg_n = 0;
+    if (h->der_sum) {
+        const size_t NK = N * (size_t)h->der.K * sizeof(double);
+        HIPCHK(hipMemsetAsync(h->der_sum, 0, NK, st)); HIPCHK(hipMemsetAsync(h->der_sumsq, 0, NK, st));
+        if (h->der_counts) HIPCHK(hipMemsetAsync(h->der_counts, 0, klara_marg_count_elems(h->der_marg) * sizeof(unsigned long long), st));
+    }
+    h->der_n = 0;
     // tuner_state: samplers.jl:29-45 — step per sampler, accepted = proposed = 0, totproposed = period
     const double step0 = sampler_step0(d);
     hipLaunchKernelGGL(k_fill_tune, dim3((unsigned)((NT + 255) / 256)), dim3(256), 0, st, h->tune_step,
@@ -457,11 +463,11 @@ struct RunCursor { long long steps_done, m_prop, m_tot, bm_count; };
 struct PlannedLaunch { long long k; int save_phase0; long long save_col0; bool tune_after, bm_close_after; long long saved; };
 
 // columns of the history ring of a job (0: every saved step is kept) — klara_desc.hist_ring_cols, or the 32-column value ring the
-// streaming autocovariances, the pooled covariance and the pooled marginal histograms keep for themselves when no value history was asked for
+// streaming autocovariances, the pooled covariance, the pooled marginal histograms and the derived quantities keep for themselves when no value history was asked for
 static long long ring_cols(const klara_desc& d)
 {
     long long r = d.hist_ring_cols;
-    if ((d.acov_maxlag > 0 || (d.monitor & KLARA_MON_COVARIANCE) || d.marg_nbins > 0) && !(d.monitor & KLARA_MON_HISTORY) && r == 0) r = 32;
+    if ((d.acov_maxlag > 0 || (d.monitor & KLARA_MON_COVARIANCE) || d.marg_nbins > 0 || d.derived_nout > 0) && !(d.monitor & KLARA_MON_HISTORY) && r == 0) r = 32;
     const long long npost = (d.nsteps - d.burnin - 1) / d.thinning + 1;
     return (r > 0 && r < npost) ? r : 0;
 }
@@ -568,6 +574,11 @@ extern "C" klara_status klara_run_async(klara_handle* h, int64_t nsteps)
         if (err == hipSuccess && h->marg_counts && pl.saved > 0) {              // ... and the pooled marginal histograms (klara_marg.h)
             err = klara_marg_launch_update(h->marg, h->hist, pl.save_col0, pl.saved, h->marg_par, h->marg_counts, h->stream);
             h->marg_n += pl.saved;
+        }
+        if (err == hipSuccess && h->der_jit && pl.saved > 0) {                  // ... and the derived quantities (klara_derived.h)
+            err = klara_derived_launch_update(h->der_jit, h->der, h->hist, pl.save_col0, pl.saved, h->der_data, h->der_ndata, h->der_sum, h->der_sumsq,
+                                              h->der_stage, &h->der_marg, h->der_marg_par, h->der_counts, nullptr, h->stream);
+            h->der_n += pl.saved;
         }
         if (err != hipSuccess) break;
         advance_cursor(d, cur, pl);

@@ -166,7 +166,8 @@ def _local_moments(s: np.ndarray, q: np.ndarray, n: float):
 def allreduce_moments(local: Dict[str, np.ndarray], group=None, device=None) -> Dict[str, np.ndarray]:
     """Chan's merge of per-rank moments: `local` holds mean[D], m2[D], nsamples, naccept, ntransitions of this rank's chains.
     Three SUM all-reduces — (nsamples, naccept, ntransitions), n_r mean_r, M2_r + n_r (mean_r - mean)^2 — every rank takes part in
-    all three whatever its values are.  Works without torch.distributed initialised (single process)."""
+    all three whatever its values are.  The arrays may have any width: with Engine.derived_moments()'s mean[K], m2[K], nsamples (and naccept =
+    ntransitions = 0) this is the merge of a derived= closure's outputs.  Works without torch.distributed initialised (single process)."""
     import torch
     import torch.distributed as dist
 
@@ -247,7 +248,8 @@ def allreduce_covariance(local: Dict[str, np.ndarray], group=None, device=None) 
 def allreduce_histogram(counts, group=None, device=None) -> np.ndarray:
     """The pooled marginal histogram of every rank's chains for hosts with their own transport: `counts` is this rank's (D, nbins + 2) table
     (Engine.pooled_histogram without a communicator; every rank built with the same marginals=).  One SUM all-reduce of 64-bit integers — exact in any
-    order, so the result is the unsharded table; gloo works.  Works without torch.distributed initialised (single process)."""
+    order, so the result is the unsharded table; gloo works.  A table of any height: Engine.derived_histogram()'s (K, nbins + 2) counts merge the same
+    way.  Works without torch.distributed initialised (single process)."""
     import torch
     import torch.distributed as dist
 
@@ -285,7 +287,8 @@ def allreduce_rhat(local: Dict[str, np.ndarray], group=None, device=None) -> Dic
     """klara_gather_rhat's between-rank merge through torch.distributed, for a host that brings its own transport: `local` is this rank's
     Engine.rhat() (mean[D], wsum[D], bsum[D], nchains, nper).  Four SUM all-reduces in the library's order — the counters (m_r n_r, m_r n_r^2, m_r),
     m_r mean_r, bsum_r + m_r (mean_r - mean)^2, wsum_r — entered by every rank whatever its values are.  Raises ValueError, on every rank, when the
-    ranks do not hold the same number of samples per chain.  Works without torch.distributed initialised (single process)."""
+    ranks do not hold the same number of samples per chain.  The arrays may have any width: Engine.derived_rhat()'s dict merges the same way.  Works
+    without torch.distributed initialised (single process)."""
     import torch
     import torch.distributed as dist
 

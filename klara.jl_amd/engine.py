@@ -281,6 +281,32 @@ def histogram_quantiles(counts, nbins: int, lo, hi, probs) -> np.ndarray:
     return out
 
 
+# ------------------------------------------------------------------ derived quantities
+class Derived:
+    """Derived(nout, source, data=None, marginals=None): a function of the state, summarised on the device.  `source` is C text that defines
+
+        KLARA_USER_FN void klara_user_derived(const double* x, int D, const double* data, long long ndata, double* out, int K);
+
+    (x: one saved sample, data: the closure's own block, out: K = nout <= 64 doubles; KLARA_D and KLARA_K are defined; the kd_* functions of detmath.h may
+    be called; a pure function of its arguments).  Handed to Engine / BasicMCJob as derived=: after every launch the closure is evaluated on every saved
+    sample of every chain and its outputs and their squares are summed per chain (Engine.derived_sums, derived_moments, derived_rhat; K.derived_mean,
+    K.derived_var, K.derived_rhat) — no stored history.  `marginals`: a Marginals over the nout outputs, for their pooled histograms and quantiles
+    (Engine.derived_histogram, K.derived_quantiles).  check_derived compiles a text without a GPU."""
+
+    def __init__(self, nout: int, source: str, data=None, marginals=None):
+        self.nout = int(nout)
+        self.source = str(source)
+        self.data = None if data is None else _f64(np.asarray(data, dtype=np.float64).ravel())
+        self.marginals = None if marginals is None else marginals if isinstance(marginals, Marginals) else Marginals(*marginals)
+
+
+def check_derived(source: str, ndims: int, nout: int) -> bool:
+    """klara_check_derived: compile a derived-quantity closure for gfx950 as klara_create would (no handle, no GPU); raises KlaraError with the
+    compiler's log when it does not compile."""
+    L.check(L.load().klara_check_derived(str(source).encode(), int(ndims), int(nout)), "klara_check_derived")
+    return True
+
+
 # ------------------------------------------------------------------ engine
 class Engine:
     def __init__(self, *, sampler: int, target, nchains: int, nsteps: int, burnin: int = 0, thinning: int = 1,
@@ -293,7 +319,7 @@ class Engine:
                  seed: int = 20260927, chain_offset: int = 0, device: int = 0, monitor: int = 0,
                  steps_per_launch: int = 0, stream: int = 0, nstreams: int = 0, bm_batchlen: int = 0, hist_ring_cols: int = 0,
                  acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0,
-                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None,
+                 ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None, derived=None,
                  am_C0=None, am_corescale: float = 0.0, am_minorscale: float = 0.0, am_c: float = 0.0, am_t0: int = 0):
         self._lib = L.load()
         self.target = target
@@ -375,6 +401,20 @@ class Engine:
             lo, hi = m.bounds(self.ndims)
             keep.extend((lo, hi)); d.marg_lo, d.marg_hi, d.marg_nbins = _ptr(lo), _ptr(hi), m.nbins
             self.marginals = Marginals(m.nbins, lo.copy(), hi.copy())
+        # derived quantities (klara_desc.derived_*): a Derived
+        self.derived = None
+        if derived is not None:
+            if not isinstance(derived, Derived):
+                raise TypeError("derived= takes a Derived(nout, source, data=None, marginals=None)")
+            src = derived.source.encode(); keep.append(src); d.derived_src, d.derived_nout = src, derived.nout
+            if derived.data is not None and derived.data.size:
+                keep.append(derived.data); d.derived_data, d.derived_ndata = _ptr(derived.data), int(derived.data.size)
+            dm = None
+            if derived.marginals is not None:
+                lo, hi = derived.marginals.bounds(derived.nout)
+                keep.extend((lo, hi)); d.derived_lo, d.derived_hi, d.derived_nbins = _ptr(lo), _ptr(hi), derived.marginals.nbins
+                dm = Marginals(derived.marginals.nbins, lo.copy(), hi.copy())
+            self.derived = Derived(derived.nout, derived.source, derived.data, dm)
         d.stream = C.c_void_p(int(stream)) if stream else None
         self._h = C.c_void_p()
         L.check(self._lib.klara_create(C.byref(d), C.byref(self._h)), "klara_create")
@@ -494,6 +534,51 @@ class Engine:
         ns, nc = C.c_uint64(0), C.c_uint64(0)
         L.check(self._lib.klara_gather_histogram(self._h, comm, counts.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_histogram")
         return counts, m.edges(self.ndims), int(ns.value), int(nc.value)
+
+    # -- derived quantities (a job built with derived=)
+    def _derived(self):
+        if self.derived is None:
+            raise ValueError("the job was built without derived=")
+        return self.derived
+
+    def derived_sums(self):
+        """(sum[nchains, K], sumsq[nchains, K], nsaved): every chain's running sums of the closure's outputs and of their squares (klara_get_derived_sums)."""
+        K = self._derived().nout
+        s = np.empty((self.nchains, K)); q = np.empty((self.nchains, K)); n = C.c_int64(0)
+        L.check(self._lib.klara_get_derived_sums(self._h, s.ctypes.data, q.ctypes.data, C.byref(n)), "klara_get_derived_sums")
+        return s, q, int(n.value)
+
+    def derived_moments(self, comm=None):
+        """(mean[K], M2[K], nsamples, nchains) of the closure's outputs over this handle's chains — or, with a klara_comm handle, over every rank's: the
+        reduction of pooled_moments on the derived sums (klara_gather_derived_moments); var = M2 / nsamples."""
+        K = self._derived().nout
+        mean = np.empty(K); m2 = np.empty(K)
+        ns, nc = C.c_uint64(0), C.c_uint64(0)
+        L.check(self._lib.klara_gather_derived_moments(self._h, comm, mean.ctypes.data, m2.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_derived_moments")
+        return mean, m2, int(ns.value), int(nc.value)
+
+    def derived_rhat(self, comm=None):
+        """The Gelman–Rubin diagnostic of the closure's outputs (klara_gather_derived_rhat, the plain form of rhat()): dict of rhat[K], mean[K], wsum[K],
+        bsum[K], nchains and nper."""
+        K = self._derived().nout
+        out = {k: np.empty(K) for k in ("rhat", "mean", "wsum", "bsum")}
+        nc, npu = C.c_uint64(0), C.c_int64(0)
+        L.check(self._lib.klara_gather_derived_rhat(self._h, comm, out["rhat"].ctypes.data, out["mean"].ctypes.data, out["wsum"].ctypes.data,
+                                                    out["bsum"].ctypes.data, C.byref(nc), C.byref(npu)), "klara_gather_derived_rhat")
+        out["nchains"], out["nper"] = int(nc.value), int(npu.value)
+        return out
+
+    def derived_histogram(self, comm=None):
+        """(counts[K, nbins + 2] uint64, edges[K, nbins + 1], nsamples, nchains): the pooled histograms of the closure's outputs, as pooled_histogram's of
+        the coordinates (klara_gather_derived_histogram); needs Derived(..., marginals=)."""
+        dq = self._derived()
+        if dq.marginals is None:
+            raise ValueError("the job's Derived was built without marginals=")
+        m = dq.marginals
+        counts = np.zeros((dq.nout, m.nbins + 2), dtype=np.uint64)
+        ns, nc = C.c_uint64(0), C.c_uint64(0)
+        L.check(self._lib.klara_gather_derived_histogram(self._h, comm, counts.ctypes.data, C.byref(ns), C.byref(nc)), "klara_gather_derived_histogram")
+        return counts, m.edges(dq.nout), int(ns.value), int(nc.value)
 
     def rhat(self, split: bool = False, comm=None):
         """The Gelman–Rubin diagnostic over this handle's chains — or, with a klara_comm handle, over every rank's (klara_gather_rhat): dict of rhat[D],

@@ -82,6 +82,26 @@ def pooled_cov(values) -> np.ndarray:
     return (xc @ xc.T) / (x.shape[1] - 1)
 
 
+def derived_sums(values, f):
+    """(sum[N, K], sumsq[N, K]) of y = f(x) over the saved steps of every chain — the literal NumPy form of what a job with derived= accumulates on the
+    device (klara_get_derived_sums): `values` is (nsaved, N, D), `f` a Python callable from a (D,) sample to K numbers; per chain, in ascending saved
+    step, sum = sum + y and sumsq = sumsq + y * y, one rounded product and one addition per step."""
+    x = np.asarray(values, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError(f"values must be (nsaved, nchains, ndims), not {x.shape}")
+    nsaved, N, _ = x.shape
+    s = q = None
+    with np.errstate(all="ignore"):
+        for t in range(nsaved):
+            for c in range(N):
+                y = np.atleast_1d(np.asarray(f(x[t, c]), dtype=np.float64)).ravel()
+                if s is None:
+                    s = np.zeros((N, y.size)); q = np.zeros((N, y.size))
+                s[c] = s[c] + y
+                q[c] = q[c] + y * y
+    return s, q
+
+
 def hist_slots(x, nbins: int, lo, hi) -> np.ndarray:
     """The slot of every value of x (..., D) among the nbins + 2 of its dimension — the index formula of klara_gather_histogram, operation for operation:
     inv_w = nbins / (hi - lo); 0 if x < lo; nbins + 1 if not x < hi (x >= hi, +inf, NaN); else 1 + min(nbins - 1, floor((x - lo) * inv_w)) — a subtraction
