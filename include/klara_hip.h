@@ -67,7 +67,7 @@ typedef enum klara_status {
     KLARA_ERR_COMPILE = 8          /* CUSTOM target: the user's source did not compile (klara_compile_log) */
 } klara_status;
 
-/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM,AM}.jl */
+/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM,AM,AMWG}.jl */
 typedef enum klara_sampler {
     KLARA_SAMPLER_MH = 0,      /* MH(sigma): symmetric normal random walk, MH.jl:63-66            */
     KLARA_SAMPLER_MALA = 1,    /* MALA(driftstep), MALA.jl:61-70                                   */
@@ -105,7 +105,24 @@ typedef enum klara_sampler {
      * iterate/AM.jl:102-106 cancel and are not formed; where corescale C does not factor the chain proposes from the minor component and the
      * handle counts it (klara_get_am_state).  klara_set_state and klara_reset put C = am_C0, both means = the start value and restart the
      * count.  DESIGN.md section 2, A1-A5. */
-    KLARA_SAMPLER_AM = 8
+    KLARA_SAMPLER_AM = 8,
+    /* (9 is reserved like 5 and 7) */
+    /* MuvAMWG(sigma) with RobertsRosenthalMCTuner(targetrate, period), samplers/AMWG.jl:139-151, iterate/AMWG.jl:82-171,
+     * tuners/RobertsRosenthalMCTuner.jl (Roberts and Rosenthal 2009, section 3): adaptive Metropolis-within-Gibbs.  A transition is a sweep over
+     * the D coordinates in order; coordinate i proposes x_i' = x_i + sqrt(exp(logsigma_i)) z_i with MH's i-th normal of the transition, evaluates
+     * the log-target at the current state with coordinate i replaced, and accepts iff ratio > 0 || ratio > log(u_i), u_i from block slot
+     * ceil(D/2) + (i >> 1) of the transition (words (x, y) for even i, (z, w) for odd i, 44 bits as the accept draw; u_0 is MH's accept draw, the
+     * normals use only the slots below ceil(D/2): the stream does not move).  Every chain keeps logsigma[D] and a window count accepted[D]; when
+     * count = t + 1 is a multiple of klara_desc.period, batch = count / period, delta = min(0.01, 1 / sqrt(batch)) and every coordinate moves
+     * its logsigma_i by -delta where accepted_i / period < klara_desc.targetrate, by +delta otherwise, and clears accepted_i.  Adaptation never
+     * stops.  Needs no gradient; D evaluations of the log-target per transition.  Only KLARA_TUNER_ROBERTS_ROSENTHAL per chain (any other tuner,
+     * the pooled mode, and that tuner with any other sampler: KLARA_ERR_UNSUPPORTED; klara_desc.verbose changes nothing on the device).
+     * KLARA_TARGET_LOGISTIC up to 16 parameters whose rows fit the LDS (layout kinds 0 and 2) and KLARA_TARGET_CUSTOM whole-vector closures
+     * (plain, likelihood + prior, autodiff sources) with D <= 32 at one chain per lane; pair closures, staged closures, the Gaussian and
+     * hierarchical families: KLARA_ERR_UNSUPPORTED.  The accept count and the accept mask record whether at least one coordinate moved;
+     * klara_get_amwg_state / klara_get_amwg_accept_mask have the per-coordinate view.  klara_set_state and klara_reset put
+     * logsigma = klara_desc.amwg_logsigma0, clear the counts and restart the schedule.  DESIGN.md section 2, W1-W6. */
+    KLARA_SAMPLER_AMWG = 10
 } klara_sampler;
 
 /* Target families evaluated on device (stand-ins for the user closures of
@@ -187,7 +204,11 @@ typedef enum klara_tuner {
     /* DualAveragingMCTuner (src/tuners/DualAveragingMCTuner.jl:54-101), HMC only (HMC.jl:124-133): Nesterov dual
      * averaging of the leapfrog step during the first da_nadapt transitions, nleaps = max(1, round(lambda/step))
      * per transition (iterate/HMC.jl:142-144), step = eps_bar afterwards (iterate/HMC.jl:246-248).  Per chain. */
-    KLARA_TUNER_DUAL_AVERAGING = 2
+    KLARA_TUNER_DUAL_AVERAGING = 2,
+    /* RobertsRosenthalMCTuner(targetrate = 0.44, period = 50) (src/tuners/RobertsRosenthalMCTuner.jl:84-101), KLARA_SAMPLER_AMWG only: every
+     * `period` transitions a coordinate's log proposal scale moves by delta = min(0.01, batch^-1/2) towards the target rate (see
+     * KLARA_SAMPLER_AMWG).  Reads klara_desc.targetrate (in (0, 1)) and klara_desc.period.  Per chain. */
+    KLARA_TUNER_ROBERTS_ROSENTHAL = 3
 } klara_tuner;
 
 typedef enum klara_tuner_mode {
@@ -233,6 +254,10 @@ typedef struct klara_desc {
     int32_t  nleaps;             /* HMC  (HMC.jl:95: > 0)                                            */
     int32_t  slice_stepout;      /* SliceSampler.stepout                                             */
     const double* slice_widths;  /* SliceSampler.widths, D doubles (> 0, SliceSampler.jl:27)         */
+    const double* amwg_logsigma0; /* MuvAMWG.logσ0, D doubles: the initial log proposal scales (the log of the constructor's σ, AMWG.jl:139-151; the
+                                    proposal's standard deviation is sqrt(exp(logsigma)), iterate/AMWG.jl:96), all finite.  Required for
+                                    KLARA_SAMPLER_AMWG; NULL for every other sampler (else KLARA_ERR_INVALID_ARG).  Copied at create.  (Beside the
+                                    other samplers' vectors: the fields behind steps_per_launch and in front of stream are the derived quantities') */
 
     /* tuner (AcceptanceRateMCTuner.jl:38-44; VanillaMCTuner: only period/verbose are used) */
     double   targetrate;         /* in (0,1)                                                         */
@@ -636,6 +661,16 @@ klara_status klara_set_ram_factor(klara_handle* h, const double* S);
  * proposed from the minor component instead.  Any pointer may be NULL.  KLARA_ERR_INVALID_ARG on a handle of
  * another sampler. */
 klara_status klara_get_am_state(klara_handle* h, double* C, double* lastmean, double* secondlastmean, int64_t* fallbacks);
+/* KLARA_SAMPLER_AMWG: the chains' current log proposal scales (nchains x D), the accepted proposals of the current tuning window per coordinate
+ * (nchains x D int32) and the accepted proposals per coordinate since klara_set_state / klara_reset (nchains x D uint64).  Any pointer may be NULL.
+ * KLARA_ERR_INVALID_ARG on a handle of another sampler; before klara_set_state: KLARA_ERR_STATE. */
+klara_status klara_get_amwg_state(klara_handle* h, double* logsigma, int32_t* accepted, uint64_t* naccept_coord);
+/* KLARA_SAMPLER_AMWG: per-chain log proposal scales for a warm start (nchains x D, all finite, else KLARA_ERR_INVALID_ARG); the transition count,
+ * the window counts and the schedule are kept.  Before klara_set_state: KLARA_ERR_STATE. */
+klara_status klara_set_amwg_logsigma(klara_handle* h, const double* logsigma);
+/* KLARA_SAMPLER_AMWG with KLARA_MON_ACCEPT: one uint32 per transition and chain, step-major like klara_get_accept_mask, bit i set where coordinate i
+ * moved (D <= 32).  *nsteps_out receives the number of recorded steps.  Without the monitor: KLARA_ERR_STATE. */
+klara_status klara_get_amwg_accept_mask(klara_handle* h, uint32_t* mask, int64_t capacity_steps, int64_t* nsteps_out);
 
 /* Measurement: duration (ms, HIP events on the launch stream) and launch count of the transition
  * kernels enqueued by the last klara_run / klara_run_async (after synchronisation). */

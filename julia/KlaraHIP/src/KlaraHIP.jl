@@ -29,7 +29,7 @@
 # `finalizer(f, obj)`): the three differences are confined to the compatibility block below, everything else is common syntax.
 module KlaraHIP
 import Klara
-import Klara: output, MCJob, MH, MALA, SMMALA, RAM, AM, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner,
+import Klara: output, MCJob, MH, MALA, SMMALA, RAM, AM, MuvAMWG, HMC, SliceSampler, VanillaMCTuner, AcceptanceRateMCTuner, DualAveragingMCTuner, RobertsRosenthalMCTuner,
               BasicContMuvParameterState, BasicContMuvParameterNState, erf_rate_score, logistic_rate_score,
               Parameter, GenericModel, VariableState, VariableStateVector, DiffOptions
 import Distributions
@@ -37,7 +37,7 @@ import Distributions: Continuous, Multivariate
 import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
-       check_custom_target_softabs, SoftAbs, ramfactor, amstate,
+       check_custom_target_softabs, SoftAbs, ramfactor, amstate, amwgstate,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat, pooledess, gather_ess,
        pooledhistogram, pooledquantiles, gather_histogram, Derived, derivedsums, derivedmoments, derivedrhat, derivedhistogram, derivedquantiles,
        gather_derived_moments, gather_derived_rhat, gather_derived_histogram, check_derived, KlaraDesc, klara_desc
@@ -59,8 +59,10 @@ const SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE = Int32(0), Int32(1),
 const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothing or SoftAbs(a); the logistic target or a CustomTarget's tensor, D <= 8
 const SAMPLER_RAM = Int32(6)         # RAM(S0; targetrate, γ): the logistic target or a CustomTarget's whole-vector closure, D <= 8 (5 is reserved)
 const SAMPLER_AM = Int32(8)          # AM(C0; corescale, minorscale, c, t0): RAM's targets, D <= 8 (7 is reserved)
+const SAMPLER_AMWG = Int32(10)       # MuvAMWG(σ) with RobertsRosenthalMCTuner: the logistic target up to 16 parameters or a CustomTarget's whole-vector closure, D <= 32 (9 is reserved)
 const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
+const TUNER_ROBERTS_ROSENTHAL = Int32(3)      # RobertsRosenthalMCTuner(targetrate, period): MuvAMWG only
 const TUNE_PER_CHAIN, TUNE_POOLED = Int32(0), Int32(1)
 const MON_ACCEPT, MON_HISTORY, MON_SUMMARIES, MON_HIST_LT, MON_HIST_GRAD, MON_HIST_LLLP = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 const MARG_MAX_BINS = 1024             # KLARA_MARG_MAX_BINS
@@ -73,7 +75,7 @@ struct KlaraDesc
     sampler::Int32; target::Int32; tuner::Int32; tuner_mode::Int32
     nchains::Int64; chain_offset::Int64; ndims::Int32; device::Int32
     mh_sigma::Ptr{Float64}; driftstep::Float64; leapstep::Float64
-    nleaps::Int32; slice_stepout::Int32; slice_widths::Ptr{Float64}
+    nleaps::Int32; slice_stepout::Int32; slice_widths::Ptr{Float64}; amwg_logsigma0::Ptr{Float64}
     targetrate::Float64; score_k::Float64; period::Int32; verbose::Int32
     da_nadapt::Int64; da_eps0bar::Float64; da_h0bar::Float64; da_gamma::Float64; da_kappa::Float64
     da_t0::Int32; tuner_score::Int32
@@ -99,6 +101,7 @@ end
 function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_VANILLA, tuner_mode=TUNE_PER_CHAIN,
                     nchains=1, chain_offset=0, ndims=1, device=0,
                     mh_sigma=Ptr{Float64}(C_NULL), driftstep=1.0, leapstep=0.1, nleaps=10, slice_stepout=1, slice_widths=Ptr{Float64}(C_NULL),
+                    amwg_logsigma0=Ptr{Float64}(C_NULL),
                     targetrate=0.0, score_k=7.0, period=100, verbose=0,
                     da_nadapt=0, da_eps0bar=1.0, da_h0bar=0.0, da_gamma=0.05, da_kappa=0.75, da_t0=10, tuner_score=0,
                     nsteps=100, burnin=0, thinning=1,
@@ -118,7 +121,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               sampler, target, tuner, tuner_mode,
               nchains, chain_offset, ndims, device,
               mh_sigma, driftstep, leapstep,
-              nleaps, slice_stepout, slice_widths,
+              nleaps, slice_stepout, slice_widths, amwg_logsigma0,
               targetrate, score_k, period, verbose,
               da_nadapt, da_eps0bar, da_h0bar, da_gamma, da_kappa,
               da_t0, tuner_score,
@@ -290,6 +293,12 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         kw[:sampler] = SAMPLER_AM; kw[:am_C0] = pointer(C0)
         kw[:am_corescale] = Float64(sampler.corescale); kw[:am_minorscale] = Float64(sampler.minorscale)
         kw[:am_c] = Float64(sampler.c); kw[:am_t0] = Int64(sampler.t0)
+    elseif isa(sampler, MuvAMWG)                            # samplers/AMWG.jl:139-151: logσ0; the truncated proposals of finite bounds are not built (W5)
+        all(isinf, sampler.lower) || error("MuvAMWG: a finite `lower` bound asks for the truncated-normal proposal (iterate/AMWG.jl:100-115), which is not built on the device")
+        all(isinf, sampler.upper) || error("MuvAMWG: a finite `upper` bound asks for the truncated-normal proposal (iterate/AMWG.jl:100-115), which is not built on the device")
+        ls0 = convert(Vector{Float64}, sampler.logσ0); push!(keep, ls0)
+        length(ls0) == D || error("MuvAMWG: σ must have one entry per dimension")
+        kw[:sampler] = SAMPLER_AMWG; kw[:amwg_logsigma0] = pointer(ls0)
     elseif isa(sampler, MALA)
         kw[:sampler] = SAMPLER_MALA; kw[:driftstep] = Float64(sampler.driftstep)
     elseif isa(sampler, HMC)
@@ -304,10 +313,11 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         sig = sqrt.(Distributions.var(prop)); push!(keep, sig)
         kw[:sampler] = SAMPLER_MH; kw[:mh_sigma] = pointer(sig)
     else
-        error("sampler $(typeof(sampler)) is not on the device path (MH, RAM, AM, MALA, SMMALA, HMC, SliceSampler are)")
+        error("sampler $(typeof(sampler)) is not on the device path (MH, RAM, AM, MuvAMWG, MALA, SMMALA, HMC, SliceSampler are)")
     end
     # --- tuner
-    tn = tuner === nothing ? VanillaMCTuner() : tuner
+    tn = tuner === nothing ? (isa(sampler, MuvAMWG) ? RobertsRosenthalMCTuner() : VanillaMCTuner()) : tuner
+    isa(sampler, MuvAMWG) == isa(tn, RobertsRosenthalMCTuner) || error("MuvAMWG and RobertsRosenthalMCTuner go together, and with nothing else (AMWG.jl:165-170)")
     kw[:period] = Int32(tn.period); kw[:verbose] = Int32(tn.verbose)
     if isa(tn, VanillaMCTuner)
         kw[:tuner] = TUNER_VANILLA
@@ -322,6 +332,8 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         else
             error("AcceptanceRateMCTuner score must be logistic_rate_score or erf_rate_score on the device")
         end
+    elseif isa(tn, RobertsRosenthalMCTuner)                 # tuners/RobertsRosenthalMCTuner.jl:84-97: target rate and period; per chain and coordinate
+        kw[:tuner] = TUNER_ROBERTS_ROSENTHAL; kw[:targetrate] = Float64(tn.targetrate)
     elseif isa(tn, DualAveragingMCTuner)
         isa(sampler, HMC) || error("DualAveragingMCTuner is wired into HMC only (HMC.jl:124-133)")
         kw[:tuner] = TUNER_DUAL_AVERAGING; kw[:targetrate] = Float64(tn.targetrate); kw[:da_nadapt] = Int64(tn.nadapt)
@@ -457,6 +469,16 @@ function amstate(job::HIPMCJob)
     check(ccall((:klara_get_am_state, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Clonglong}), job.handle, Cm, m, m2, fallbacks),
           "klara_get_am_state")
     (Cm, m, m2, Int(fallbacks[]))
+end
+
+# amwgstate(job): (logσ, accepted, naccept) of a MuvAMWG job — logσ[:, c] is chain c's current log proposal scales (tune.logσ of iterate/AMWG.jl:96),
+# accepted[:, c] the accepted proposals of its current tuning window per coordinate (tune.accepted), naccept[:, c] those since the start state
+function amwgstate(job::HIPMCJob)
+    ls = newarray(Float64, job.ndims, job.nchains)                  # nchains x D row-major == D x nchains column-major
+    acc = newarray(Int32, job.ndims, job.nchains)
+    nacc = newarray(UInt64, job.ndims, job.nchains)
+    check(ccall((:klara_get_amwg_state, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}, Ptr{UInt64}), job.handle, ls, acc, nacc), "klara_get_amwg_state")
+    (ls, acc, nacc)
 end
 
 # value matrix of chain c exactly as BasicContMuvParameterNState.value (D x npoststeps)

@@ -150,6 +150,46 @@ class AM(MCSampler):
         self.C0, self.corescale, self.minorscale, self.c, self.t0 = a.copy(), float(corescale), float(minorscale), float(c), int(t0)
 
 
+class MuvAMWG(MCSampler):
+    """MuvAMWG(σ::Vector) / MuvAMWG(d; lower=fill(-Inf, d), upper=fill(Inf, d), σ=1.) — AMWG.jl:139-151: adaptive Metropolis-within-Gibbs (Roberts and
+    Rosenthal 2009, section 3).  A transition updates the coordinates one at a time, each with a normal proposal of its own scale; with
+    RobertsRosenthalMCTuner every chain learns one scale per coordinate.  `logsigma0` is the reference's logσ0 = log.(σ) (the proposal's standard deviation is
+    sqrt(exp(logσ)), iterate/AMWG.jl:98, kept).  Gradient-free, D <= 32 on the device: the logistic regression up to 16 parameters and user-defined
+    whole-vector targets.  The truncated proposals of finite bounds are not built: a finite `lower` or `upper` is refused
+    (BasicMCJob.engine.amwg_state())."""
+    kind = L.SAMPLER_AMWG
+
+    def __init__(self, sigma_or_d=None, *, lower=None, upper=None, sigma=None, **kw):
+        if "σ" in kw:
+            sigma = kw.pop("σ")
+        if kw:
+            raise TypeError(f"MuvAMWG: unexpected keyword arguments {sorted(kw)}")
+        if sigma_or_d is None:
+            raise TypeError("MuvAMWG needs the vector of σ or the number of dimensions d")
+        if isinstance(sigma_or_d, (int, np.integer)) and not isinstance(sigma_or_d, bool):       # MuvAMWG(d::Integer; lower, upper, σ::Real=1.)
+            d = int(sigma_or_d)
+            s = np.full(d, 1.0 if sigma is None else float(sigma))
+        else:                                                                                    # MuvAMWG(σ::RealVector)
+            if lower is not None or upper is not None or sigma is not None:
+                raise TypeError("MuvAMWG(σ::Vector) takes no keywords; use MuvAMWG(d; lower, upper, σ)")
+            s = np.asarray(sigma_or_d, dtype=np.float64).ravel().copy()
+            d = s.size
+        self.lower = np.full(d, -np.inf) if lower is None else np.asarray(lower, dtype=np.float64).ravel().copy()
+        self.upper = np.full(d, np.inf) if upper is None else np.asarray(upper, dtype=np.float64).ravel().copy()
+        if self.lower.size != d or self.upper.size != d:
+            raise ValueError("MuvAMWG: lower and upper must have d elements")
+        for name, b in (("lower", self.lower), ("upper", self.upper)):
+            if np.any(np.isfinite(b)):
+                raise NotImplementedError(f"MuvAMWG: a finite `{name}` bound asks for the truncated-normal proposal (iterate/AMWG.jl:100-115), "
+                                          "which is not built on the device")
+        with np.errstate(all="ignore"):
+            self.logsigma0 = np.log(s)                                                           # map(log, σ)
+        self.sigma = s
+
+
+AMWG = MuvAMWG      # (the reference's abstract type over UnvAMWG / MuvAMWG; the univariate sampler is the vector one at d = 1)
+
+
 class HMC(MCSampler):
     """HMC(leapstep=0.1, nleaps=10) — HMC.jl:89-100."""
     kind = L.SAMPLER_HMC
@@ -184,6 +224,17 @@ class VanillaMCTuner(MCTuner):
     def __init__(self, period: int = 100, verbose: bool = False):
         assert period > 0, "Tuning period should be positive"
         self.period, self.verbose = int(period), bool(verbose)
+
+
+class RobertsRosenthalMCTuner(MCTuner):
+    """RobertsRosenthalMCTuner(targetrate=0.44, period=50, verbose=false) — RobertsRosenthalMCTuner.jl:84-97: every `period` transitions a coordinate's
+    log proposal scale moves by δ = min(0.01, batch^-1/2) towards the target acceptance rate.  The tuner of MuvAMWG, and of nothing else."""
+    kind = L.TUNER_ROBERTS_ROSENTHAL
+
+    def __init__(self, targetrate: float = 0.44, period: int = 50, verbose: bool = False):
+        assert 0 < targetrate < 1, "Target acceptance rate should be between 0 and 1"
+        assert period > 0, "Tuning period should be positive"
+        self.targetrate, self.period, self.verbose = float(targetrate), int(period), bool(verbose)
 
 
 def logistic(x, l=1.0, k=1.0, x0=0.0, y0=0.0):
@@ -586,6 +637,10 @@ def pooled_cor(job_or_chains, comm=None) -> np.ndarray:
 def acceptance(chains: MuvChains, diagnostics: bool = True) -> np.ndarray:
     """acceptance(s::MultivariateParameterNState; key=:accept) — stats/acceptance.jl:28-34:
     mean of the accept diagnostics over the saved steps (per chain)."""
+    if isinstance(chains._job.sampler, MuvAMWG):
+        # MuvAMWG: a rate per coordinate — the accepted proposals of every coordinate since the start state over the transitions done (nchains x D)
+        eng = chains._job.engine
+        return eng.amwg_state()[2].astype(np.float64) / float(max(eng.accept_counts()[1], 1))
     if chains._acc is None:
         raise ValueError("request outopts diagnostics=['accept'] to record the accept diagnostics")
     return chains._acc.mean(axis=0)
@@ -711,6 +766,13 @@ class BasicMCJob:
                 raise NotImplementedError("AM adapts by itself: only VanillaMCTuner (which counts proposals when verbose) is accepted")
             kw["am_C0"], kw["am_corescale"], kw["am_minorscale"] = sampler.C0, sampler.corescale, sampler.minorscale
             kw["am_c"], kw["am_t0"] = sampler.c, sampler.t0
+        elif isinstance(sampler, MuvAMWG):                                             # AMWG.jl:139-151 with RobertsRosenthalMCTuner.jl:84-97
+            if tuner is None:
+                self.tuner = RobertsRosenthalMCTuner()
+                kw.update(tuner=self.tuner.kind, period=self.tuner.period, verbose=self.tuner.verbose)
+            if not isinstance(self.tuner, RobertsRosenthalMCTuner):
+                raise NotImplementedError("MuvAMWG is tuned by RobertsRosenthalMCTuner alone (AMWG.jl:165-170)")
+            kw["amwg_logsigma0"], kw["targetrate"] = sampler.logsigma0, self.tuner.targetrate
         elif isinstance(sampler, HMC):
             kw["leapstep"], kw["nleaps"] = sampler.leapstep, sampler.nleaps
         elif isinstance(sampler, SliceSampler):
@@ -724,6 +786,8 @@ class BasicMCJob:
             kw["targetrate"], kw["score_k"] = self.tuner.targetrate, self.tuner.score_k
             kw["tuner_score"] = self.tuner.score_kind
             kw["tuner_mode"] = L.TUNE_POOLED if self.tuner.mode == "pooled" else L.TUNE_PER_CHAIN
+        if isinstance(self.tuner, RobertsRosenthalMCTuner) and not isinstance(sampler, MuvAMWG):
+            raise NotImplementedError("RobertsRosenthalMCTuner is the tuner of MuvAMWG alone")
         self.engine = Engine(**kw)
         # initialize!(pstate, parameter, sampler, outopts): BasicMCJob.jl:73 (finite asserts on device)
         try:

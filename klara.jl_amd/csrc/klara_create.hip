@@ -11,7 +11,7 @@ static klara_status validate_fields(const klara_desc* d)
     if (d->nchains <= 0 || d->ndims <= 0 || d->chain_offset < 0) return KLARA_ERR_INVALID_ARG;
     if (!sampler_valid(d->sampler)) return KLARA_ERR_INVALID_ARG;
     if (d->target < KLARA_TARGET_GAUSS_DIAG || d->target > KLARA_TARGET_CUSTOM) return KLARA_ERR_INVALID_ARG;
-    if (d->tuner < KLARA_TUNER_VANILLA || d->tuner > KLARA_TUNER_DUAL_AVERAGING) return KLARA_ERR_INVALID_ARG;
+    if (d->tuner < KLARA_TUNER_VANILLA || d->tuner > KLARA_TUNER_ROBERTS_ROSENTHAL) return KLARA_ERR_INVALID_ARG;
     if (d->tuner == KLARA_TUNER_DUAL_AVERAGING) {                // DualAveragingMCTuner.jl:65-70
         if (!(d->targetrate > 0.0 && d->targetrate < 1.0) || d->da_nadapt <= 0 || !(d->da_eps0bar > 0.0) || d->da_t0 <= 0 ||
             !(d->da_gamma > 0.0))
@@ -61,6 +61,14 @@ static klara_status validate_fields(const klara_desc* d)
         // the tuner only counts proposals (iterate/AM.jl:80-82, 123-125, 137-151): VanillaMCTuner, per chain
         if (d->tuner != KLARA_TUNER_VANILLA || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
         break;
+    case KLARA_SAMPLER_AMWG:                                     // AMWG.jl:139-151, RobertsRosenthalMCTuner.jl:89-93
+        if (!d->amwg_logsigma0) return KLARA_ERR_INVALID_ARG;
+        if (d->ndims <= 32) {                                    // (beyond: KLARA_ERR_UNSUPPORTED from the planner, whatever the scales)
+            for (int i = 0; i < d->ndims; ++i) if (!std::isfinite(d->amwg_logsigma0[i])) return KLARA_ERR_INVALID_ARG;
+        }
+        if (d->tuner != KLARA_TUNER_ROBERTS_ROSENTHAL || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
+        if (!(d->targetrate > 0.0 && d->targetrate < 1.0) || d->period > 0x7fffffff) return KLARA_ERR_INVALID_ARG;
+        break;
     default:                                                     // SliceSampler.jl:27
         if (!d->slice_widths) return KLARA_ERR_INVALID_ARG;
         for (int i = 0; i < d->ndims; ++i) if (!(d->slice_widths[i] > 0.0)) return KLARA_ERR_INVALID_ARG;
@@ -85,6 +93,8 @@ static klara_status validate_fields(const klara_desc* d)
     if (d->smmala_softabs > 0.0 && d->sampler != KLARA_SAMPLER_SMMALA) return KLARA_ERR_INVALID_ARG;
     if (d->smmala_softabs > 0.0 && d->target != KLARA_TARGET_CUSTOM) return KLARA_ERR_UNSUPPORTED;
     if (d->sampler != KLARA_SAMPLER_RAM && (d->ram_S0 != nullptr || d->ram_targetrate != 0.0 || d->ram_gamma != 0.0)) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler != KLARA_SAMPLER_AMWG && d->amwg_logsigma0 != nullptr) return KLARA_ERR_INVALID_ARG;
+    if (d->sampler != KLARA_SAMPLER_AMWG && d->tuner == KLARA_TUNER_ROBERTS_ROSENTHAL) return KLARA_ERR_UNSUPPORTED;
     if (d->sampler != KLARA_SAMPLER_AM && (d->am_C0 != nullptr || d->am_corescale != 0.0 || d->am_minorscale != 0.0 || d->am_c != 0.0 || d->am_t0 != 0))
         return KLARA_ERR_INVALID_ARG;
     // pooled marginal histograms: 0 = off and no pointers; 1 .. KLARA_MARG_MAX_BINS with finite lo[d] < hi[d]
@@ -403,6 +413,11 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
         KCHK(upload(mem, &h->am_C0, tri.data(), tri.size()));
         HIPCHK(mem.alloc(&h->am_C, tri.size() * N)); HIPCHK(mem.alloc(&h->am_mean, 2 * D * N)); HIPCHK(mem.alloc(&h->am_fallbacks, 1));
     }
+    if (desc->sampler == KLARA_SAMPLER_AMWG) {                   // D planes of scales, window counts and accepted proposals; the coordinate masks beside the accept mask
+        KCHK(upload(mem, &h->amwg_logsig0, desc->amwg_logsigma0, D));
+        HIPCHK(mem.alloc(&h->amwg_logsig, D * N)); HIPCHK(mem.alloc(&h->amwg_acc, D * N)); HIPCHK(mem.alloc(&h->amwg_nacc, D * N));
+        if (desc->monitor & KLARA_MON_ACCEPT) HIPCHK(mem.alloc(&h->amwg_mask, (size_t)desc->nsteps * N));
+    }
     if (desc->target == KLARA_TARGET_GAUSS_DIAG) {
         if (desc->gauss_w) KCHK(upload(mem, &h->gw, desc->gauss_w, D));
         if (desc->gauss_mu) KCHK(upload(mem, &h->gmu, desc->gauss_mu, D));
@@ -439,7 +454,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     // the descriptor's host pointers are not retained
     h->d.mh_sigma = nullptr; h->d.slice_widths = nullptr; h->d.gauss_w = nullptr; h->d.gauss_mu = nullptr;
     h->d.gauss_prec = nullptr; h->d.logit_X = nullptr; h->d.logit_y = nullptr; h->d.hier_Y = nullptr; h->d.hier_xc = nullptr; h->d.stream = nullptr;
-    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.am_C0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
+    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.am_C0 = nullptr; h->d.amwg_logsigma0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
     h->d.derived_src = nullptr; h->d.derived_data = nullptr; h->d.derived_lo = nullptr; h->d.derived_hi = nullptr;
     {   // static kernel parameters live in device memory (read with scalar loads at the point of use)
         const KParams hp = make_params(h);
@@ -536,6 +551,8 @@ KParams make_params(klara_handle* h)
     p.ram_S = (decltype(p.ram_S))h->ram_S; p.ram_skipped = (decltype(p.ram_skipped))h->ram_skipped; p.ram_targetrate = d.ram_targetrate; p.ram_gamma = d.ram_gamma;
     p.am_C = (decltype(p.am_C))h->am_C; p.am_mean = (decltype(p.am_mean))h->am_mean; p.am_fallbacks = (decltype(p.am_fallbacks))h->am_fallbacks;
     p.am_corescale = d.am_corescale; p.am_sqrtminor = std::sqrt(d.am_minorscale); p.am_w1 = 1.0 - d.am_c; p.am_t0 = d.am_t0;     // AM.jl:235-236: sqrtminorscale, w = [1 - c, c]
+    p.amwg_logsig = (decltype(p.amwg_logsig))h->amwg_logsig; p.amwg_acc = (decltype(p.amwg_acc))h->amwg_acc; p.amwg_nacc = (decltype(p.amwg_nacc))h->amwg_nacc;
+    p.amwg_mask = (decltype(p.amwg_mask))h->amwg_mask;
     return p;
 }
 

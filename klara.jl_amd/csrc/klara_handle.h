@@ -95,6 +95,9 @@ struct klara_handle {
     // AM: the chains' covariances (D (D + 1) / 2 planes, KParams::am_C), their running means (2 D planes, KParams::am_mean), the packed upper triangle of
     // klara_desc.am_C0 they restart from, the counter of transitions that fell back to the minor component
     double *am_C = nullptr, *am_C0 = nullptr, *am_mean = nullptr; unsigned long long* am_fallbacks = nullptr;
+    // AMWG: the chains' log proposal scales, window counts and accepted proposals per coordinate (D planes of nchains each, KParams::amwg_*), the D scales of
+    // klara_desc.amwg_logsigma0 they restart from, the coordinate masks of the transitions (KLARA_MON_ACCEPT: nsteps x nchains)
+    double *amwg_logsig = nullptr, *amwg_logsig0 = nullptr; int* amwg_acc = nullptr; unsigned long long* amwg_nacc = nullptr; uint32_t* amwg_mask = nullptr;
     // streaming batch means (bm_batchlen > 0): running sum at the last batch boundary, Welford mean / M2 of the batch means
     double *bm_prev = nullptr, *bm_mean = nullptr, *bm_m2 = nullptr; long long bm_count = 0;
     KParams* d_params = nullptr;    // device copy of the handle's static kernel parameters

@@ -94,6 +94,12 @@ __host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { re
 #define KLARA_AM_WAVES(E, MODE) ((E) == 8 ? 1 : 2)
 #endif
 
+// AMWG kernels, wavefronts per SIMD asked of the compiler: the chain's 2 D scales and counts next to x and z, and one whole evaluation of the target per
+// coordinate (the compiler's resource table is in DESIGN.md section 2)
+#ifndef KLARA_AMWG_WAVES
+#define KLARA_AMWG_WAVES(E, MODE) ((E) >= 16 ? 1 : (E) == 2 ? 3 : 2)
+#endif
+
 // Device pointers inside KParams are typed as address space 1 (global) in device compilation: the struct is read
 // from memory, and without the qualifier hipcc treats the loaded pointers as generic and emits flat_load/flat_store
 // (vmcnt + lgkmcnt, 64-bit VGPR addresses) instead of global_load v, v_off32, s[base:base+1].  Host code sees plain
@@ -163,6 +169,10 @@ struct KParams {
     // means, 2 D planes (lastmean_i at plane i, secondlastmean_i at plane D + i); the handle's counter of transitions that fell back to the minor component;
     // AM.corescale, sqrt(AM.minorscale), the core component's weight 1 - AM.c, AM.t0
     gdouble* am_C; gdouble* am_mean; gulong* am_fallbacks; double am_corescale; double am_sqrtminor; double am_w1; long long am_t0;
+    // AMWG: the chains' log proposal scales and window counts, D planes of nchains each (coordinate i of chain c at [i * nchains + c]); the accepted proposals
+    // per coordinate of the windows closed since the start state, likewise; the coordinate masks, [transition][nchains], or null (KLARA_MON_ACCEPT).  The tuner's period and
+    // target rate are `period` and `targetrate` above.
+    gdouble* amwg_logsig; gint* amwg_acc; gulong* amwg_nacc; KGLOBAL uint32_t* amwg_mask;     // (amwg_nacc: the closed windows; the open one is amwg_acc)
 };
 
 // Per-launch values, passed by value.  Everything else (KParams) is static for a handle and lives in device memory:
@@ -1385,6 +1395,99 @@ KLARA_PRAGMA_UNROLL_E
     return acc;
 }
 
+// ---- AMWG (src/samplers/AMWG.jl, iterate/AMWG.jl:82-171, tuners/RobertsRosenthalMCTuner.jl, after Roberts and Rosenthal 2009 section 3) ----
+// One chain per lane (G == 1; the row-split lanes of the logistic target replicate it): logsig and acc are the chain's log proposal scales and its accepted
+// proposals of the current tuning window.  The padding e >= D is loaded as zero, never proposed and never stored.  They travel between launches in
+// KParams::amwg_logsig / amwg_acc; a window's counts are added to KParams::amwg_nacc when the window closes (a read-modify-write per coordinate and period,
+// instead of E more registers through every evaluation of the target).
+template <int E>
+struct AmwgRegs {
+    double logsig[E];
+    int acc[E];
+};
+template <int E>
+__device__ __forceinline__ void amwg_load(const KParams& p, const LaneCtx<E>& cx, AmwgRegs<E>& r)
+{
+    const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's state and store nothing)
+    const gdouble* pl = p.amwg_logsig + c0;
+    const gint* pa = p.amwg_acc + c0;
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e) {
+        double v = 0.0; int a = 0;
+        if (e < p.D) { v = *pl; a = *pa; pl += p.nchains; pa += p.nchains; }
+        r.logsig[e] = v; r.acc[e] = a;
+    }
+}
+template <int E>
+__device__ __forceinline__ void amwg_store(const KParams& p, const LaneCtx<E>& cx, const AmwgRegs<E>& r)
+{
+    gdouble* pl = p.amwg_logsig + cx.chain;
+    gint* pa = p.amwg_acc + cx.chain;
+KLARA_PRAGMA_UNROLL_E
+    for (int e = 0; e < E; ++e)
+        if (e < p.D) { *pl = r.logsig[e]; *pa = r.acc[e]; pl += p.nchains; pa += p.nchains; }
+}
+// iterate!(job, MuvAMWG, Multivariate) — iterate/AMWG.jl:82-171 as DESIGN.md section 2 (W1-W6) states it: the sweep over the coordinates in order, each
+// one MH step on its own coordinate (the candidate replaces x_i in a copy of the state, W1), then — `tuning`: count is a multiple of the period — the
+// tuner's move of every coordinate's log scale by `delta` (RobertsRosenthalMCTuner.jl:99-108; a coordinate's scale is read by its own step alone, so moving
+// them after the sweep is the reference's order).  The coordinate loop is a loop (one copy of the target's evaluation in the code, whatever E); the
+// registers of coordinate i are read and written through selects, and its draws are formed inside the loop.  Returns the coordinates that moved, bit i for coordinate i.
+template <class T, int E>
+__device__ __forceinline__ uint32_t step_amwg(const KParams& p, const T& tg, const LaneCtx<E>& cx,
+                                              unsigned long long gchain, unsigned long long t,
+                                              bool tuning, double delta, AmwgRegs<E>& ws,
+                                              double (&x)[E], double& lt)
+{
+    static_assert(E <= 32, "the coordinate mask is 32 bits");
+    uint32_t moved = 0u;
+    const int D = p.D;
+    const uint32_t npairs = (uint32_t)((D + 1) >> 1);
+    kd_u32x4 blk = { 0u, 0u, 0u, 0u };
+    double z0 = 0.0, z1 = 0.0;
+_Pragma("nounroll")
+    for (int i = 0; i < D; ++i) {
+        // the draws of a coordinate pair, formed when the sweep gets to it (not D normals held through every evaluation): MH's normals of element pair
+        // i >> 1 (the same function lane_normals calls: the same bits) and the block of the pair's two accept uniforms, slot ceil(D/2) + (i >> 1)
+        if ((i & 1) == 0) {
+            double u1, lg1;
+            kd_normal_pair_at(p.seed, gchain, t, (uint32_t)(i >> 1), npairs, &z0, &z1, &u1, &lg1);
+            blk = kd_stream_block(p.seed, gchain, t, npairs + (uint32_t)(i >> 1));
+        }
+        const double zi = (i & 1) ? z1 : z0;
+        double xi = 0.0, ls = 0.0;
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) { xi = (e == i) ? x[e] : xi; ls = (e == i) ? ws.logsig[e] : ls; }
+        const double sigma = __builtin_sqrt(kd_exp(ls));                                   // iterate/AMWG.jl:96 sqrt(exp(logσ))
+        const double cand = xi + sigma * zi;                                               // :96
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) x[e] = (e == i) ? cand : x[e];                         // the candidate in place (W1): an accepted one simply stays
+        const double ltp = eval_lt<T, E>(tg, cx, x);                                       // :97
+        const double ratio = ltp - lt;                                                     // :99
+        const double u = (i & 1) ? kd_u44(blk.z, blk.w) : kd_u44(blk.x, blk.y);
+        const bool acc = ratio > 0.0 || ratio > kd_log_u01(u);                             // :117 (W4: the uniform is drawn whatever the ratio)
+        lt = acc ? ltp : lt;
+        moved |= acc ? (1u << i) : 0u;
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) {
+            x[e] = (e == i && !acc) ? xi : x[e];                                           // a rejected candidate goes back
+            ws.acc[e] += (acc && e == i) ? 1 : 0;                                          // :135
+        }
+    }
+    if (tuning) {                                                                          // :148-170 (uniform over the launch's chains: no divergence)
+        const double per = (double)p.period;
+        const bool writer = cx.chain_ok && cx.q == 0 && cx.rq == 0;
+        gulong* pn = p.amwg_nacc + (cx.chain_ok ? cx.chain : 0);
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) {
+            const double rate = (double)ws.acc[e] / per;                                   // rate!, RobertsRosenthalMCTuner.jl:80 (:149)
+            ws.logsig[e] = ws.logsig[e] + (rate < p.targetrate ? -delta : delta);          // tune!, RobertsRosenthalMCTuner.jl:104-108 (:163)
+            if (e < p.D) { if (writer) *pn += (unsigned long long)ws.acc[e]; pn += p.nchains; }     // the closed window's counts
+            ws.acc[e] = 0;
+        }
+    }
+    return moved;
+}
+
 // iterate!(job, HMC, Multivariate) — iterate/HMC.jl:124-201; leapfrog! samplers.jl:122-134;
 // hamiltonian samplers.jl:103
 template <class T, int E, bool PLAIN, bool COMMIT = true>
@@ -1720,6 +1823,7 @@ template <int SAMPLER, int TARGET, int E, int GT, int MODE>
 //  kernel uses scratch; DESIGN.md section 2 and profiles/ram.txt have the table)
 __global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_RAM ? KLARA_RAM_WAVES(E, MODE) :
                                    SAMPLER == KLARA_SAMPLER_AM ? KLARA_AM_WAVES(E, MODE) :
+                                   SAMPLER == KLARA_SAMPLER_AMWG ? KLARA_AMWG_WAVES(E, MODE) :
                                    SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
                                                                                                   metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2; with the
                                                                                                   softabs transform's eigenvectors: 20-120 B in every mode) */ :
@@ -1730,20 +1834,21 @@ __global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_RAM ? KLARA_RAM_WAVE
                                                   : (E == 8 && TARGET == KLARA_TARGET_LOGISTIC ? KLARA_E8_WAVES_LOGISTIC : 1))))
 void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
 {
-    constexpr bool PLAIN = (MODE & 1) != 0, NOMON = (MODE & 2) != 0;
+    constexpr bool PLAIN = (MODE & 1) != 0 || SAMPLER == KLARA_SAMPLER_AMWG /* (no step-size tuner state: nothing counts, cnt_predicate) */, NOMON = (MODE & 2) != 0;
     constexpr bool ONESTEP = (MODE & 4) != 0;          // exactly one transition per launch (= one iterate!)
     const int nsteps = ONESTEP ? 1 : kl.nsteps;
     constexpr bool RSPL = TARGET == KLARA_TARGET_LOGISTIC;
     // single unmonitored transition: an accepted proposal goes from the proposal registers straight to HBM
-    constexpr bool DIRECT = ONESTEP && NOMON && SAMPLER != KLARA_SAMPLER_SLICE;
+    constexpr bool DIRECT = ONESTEP && NOMON && SAMPLER != KLARA_SAMPLER_SLICE && SAMPLER != KLARA_SAMPLER_AMWG;
     // monitored jobs: the step functions hand the proposal back and the commit happens here, after the state being left has been
     // folded into the running sums (KParams::held)
-    constexpr bool OUTER = !NOMON && SAMPLER != KLARA_SAMPLER_SLICE;
+    constexpr bool OUTER = !NOMON && SAMPLER != KLARA_SAMPLER_SLICE && SAMPLER != KLARA_SAMPLER_AMWG;     // (the slice sampler and AMWG commit coordinate by coordinate, in place)
     // The logistic targets fold the running sums of a chain that moves straight into memory (a read-modify-write of 2 D values per
     // accepted transition, against ~3,000 vector instructions of a transition) instead of keeping 4 E registers of sums resident:
     // with them the 128-register kernels of cfg 4 (4 wavefronts per SIMD) spilled.  Everything else keeps resident sums (the README
     // job runs a transition in ~60 instructions: a memory round trip per accepted move would dominate it).
-    constexpr bool MEMSUMS = TARGET == KLARA_TARGET_LOGISTIC;
+    // (AMWG at E = 32 likewise: 4 E registers of sums next to the chain's 3 E of scales and counts spilled, 60 B in the compiler's report; a sweep is D evaluations)
+    constexpr bool MEMSUMS = TARGET == KLARA_TARGET_LOGISTIC || (SAMPLER == KLARA_SAMPLER_AMWG && E >= 32);
     const KParams& p = *pp;
     kd_tables_to_lds();
     guchar* const accept_out = (!NOMON && p.accept != nullptr) ? p.accept + kl.t0 * (unsigned long long)p.nchains : nullptr;
@@ -1753,7 +1858,7 @@ void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using T = typename TargetSel<TARGET, E>::type;
     constexpr bool NEEDG = (SAMPLER == KLARA_SAMPLER_MALA || SAMPLER == KLARA_SAMPLER_HMC || SAMPLER == KLARA_SAMPLER_SMMALA);
-    constexpr bool NEEDZ = (SAMPLER != KLARA_SAMPLER_SLICE);
+    constexpr bool NEEDZ = (SAMPLER != KLARA_SAMPLER_SLICE && SAMPLER != KLARA_SAMPLER_AMWG);     // (AMWG draws coordinate by coordinate, step_amwg)
 
     LaneCtx<E> cx = make_ctx<E, GT, RSPL>(p);
     T tg;
@@ -1781,7 +1886,7 @@ void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
         // difference between fitting 128 registers and spilling).
         // (AM at E = 8 does not prefetch either: with the second lane context the kernel's scalar registers spill into vector registers it has none left for,
         //  28 B of scratch in the compiler's report; the order of the loads changes no bit)
-        constexpr bool PREFETCH = ONESTEP && !(SAMPLER == KLARA_SAMPLER_AM && E == 8);
+        constexpr bool PREFETCH = ONESTEP && !(SAMPLER == KLARA_SAMPLER_AM && E == 8) && !(SAMPLER == KLARA_SAMPLER_AMWG && E >= 8);
         const long long grp_next = grp + nwaves;
         const bool has_next = grp_next * cpw < p.nchains;
         LaneCtx<E> cxn = cx;
@@ -1836,6 +1941,16 @@ KLARA_PRAGMA_UNROLL_E
         // AM: the group's covariances and running means likewise
         AmRegs<SAMPLER == KLARA_SAMPLER_AM ? E : 2> ams;
         if constexpr (SAMPLER == KLARA_SAMPLER_AM) am_load<E>(p, cx, ams);
+        // AMWG: the group's log proposal scales and window counts likewise; the tuner's schedule follows from the transition index alone (count = t + 1:
+        // phase = count mod period, batch = count / period), so it is formed once per launch and stepped without a division
+        AmwgRegs<(SAMPLER == KLARA_SAMPLER_AMWG && E <= 32) ? E : 2> wms;
+        int wphase = 0; long long wbatch = 0;
+        KGLOBAL uint32_t* wmask_out = nullptr;
+        if constexpr (SAMPLER == KLARA_SAMPLER_AMWG) {
+            amwg_load<E>(p, cx, wms);
+            wphase = (int)((long long)kl.t0 % (long long)p.period); wbatch = (long long)kl.t0 / (long long)p.period;
+            if (!NOMON && p.amwg_mask != nullptr) wmask_out = p.amwg_mask + kl.t0 * (unsigned long long)p.nchains;
+        }
 
         TuneRegs tn;
         if (per_chain_tune) tn = { cur.step, cur.accepted, cur.proposed, cur.totproposed, 0, 0.0, 0.0 };
@@ -1858,6 +1973,16 @@ KLARA_PRAGMA_UNROLL_E
                 acc = step_smmala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, sms, prop);
             else if constexpr (SAMPLER == KLARA_SAMPLER_RAM) acc = step_ram<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, rms, cur.x, cur.lt, prop);
             else if constexpr (SAMPLER == KLARA_SAMPLER_AM) acc = step_am<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, ams, cur.x, cur.lt, prop);
+            else if constexpr (SAMPLER == KLARA_SAMPLER_AMWG) {
+                if (do_sum && held > 0) fold_state();                      // fold first, whatever the sweep will do: the position does not depend on data
+                wphase = (wphase + 1 == p.period) ? 0 : wphase + 1;
+                const bool tuning = wphase == 0;                           // count % period == 0
+                wbatch += tuning ? 1 : 0;                                  // count / period
+                const double rs = 1.0 / __builtin_sqrt((double)wbatch);   // (W2: batch^-0.5)
+                const uint32_t moved = step_amwg<T, E>(p, tg, cx, gchain, t, tuning, rs < 0.01 ? rs : 0.01, wms, cur.x, cur.lt);
+                acc = moved != 0u;
+                if (wmask_out != nullptr && cx.chain_ok && cx.q == 0 && cx.rq == 0) wmask_out[(long long)s * p.nchains + cx.chain] = moved;
+            }
             else if (SAMPLER == KLARA_SAMPLER_MH) acc = step_mh<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_MALA) acc = step_mala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, prop);
             else if (SAMPLER == KLARA_SAMPLER_HMC) {
@@ -1933,6 +2058,7 @@ KLARA_PRAGMA_UNROLL_E
         if (cx.chain_ok && cx.q == 0 && cx.rq == 0) {
             if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_store<E>(p, cx, rms);
             if constexpr (SAMPLER == KLARA_SAMPLER_AM) am_store<E>(p, cx, ams);
+            if constexpr (SAMPLER == KLARA_SAMPLER_AMWG) amwg_store<E>(p, cx, wms);
             if (do_sum) p.held[cx.chain] = held;
             if (nacc != 0) { p.LT[cx.chain] = cur.lt; p.naccept[cx.chain] += nacc; }
             if (da) { p.tune_step[cx.chain] = tn.step; p.da_epsbar[cx.chain] = tn.epsbar; p.da_hbar[cx.chain] = tn.hbar; }

@@ -82,6 +82,9 @@ hipError_t klara_launch_ram(const KParams* p, const KLaunch& kl, int mode, int t
 // AM on the logistic target, E in {2, 4, 8}, one chain per lane (klara_am.hip); its start-state kernel is k_init
 hipError_t klara_launch_am(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
                            hipStream_t st);
+// AMWG on the logistic target, E in {2, 4, 8, 16}, one chain per lane (klara_amwg.hip); its start-state kernel is k_init
+hipError_t klara_launch_amwg(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
+                             hipStream_t st);
 // dense (MFMA) kernels; NE in {8,16,25,32}
 // (Pfrag: the fragment-ordered precision matrix, followed — hasmu — by the 4 NE zero-padded entries of the mean)
 hipError_t klara_launch_dense(const KParams* p, const KLaunch& kl, int sampler, int tuner, bool plain, int NE, const double* Pfrag, bool hasmu,

@@ -771,6 +771,63 @@ extern "C" klara_status klara_get_am_state(klara_handle* h, double* Cout, double
     return KLARA_OK;
 }
 
+// the D planes of an AMWG array as nchains x D rows, and back
+template <class T>
+static klara_status amwg_read_planes(const T* dev, size_t N, size_t D, T* out)
+{
+    std::vector<T> planes(D * N);
+    HIPCHK(hipMemcpy(planes.data(), dev, planes.size() * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < N; ++c) for (size_t i = 0; i < D; ++i) out[c * D + i] = planes[i * N + c];
+    return KLARA_OK;
+}
+
+extern "C" klara_status klara_get_amwg_state(klara_handle* h, double* logsigma, int32_t* accepted, uint64_t* naccept_coord)
+{
+    if (!h || h->d.sampler != KLARA_SAMPLER_AMWG) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
+    if (logsigma) KCHK(amwg_read_planes(h->amwg_logsig, N, D, logsigma));
+    if (accepted) KCHK(amwg_read_planes((const int32_t*)h->amwg_acc, N, D, accepted));
+    if (naccept_coord) {                                         // the closed windows' counts + the open window's
+        std::vector<int32_t> open(N * D);
+        KCHK(amwg_read_planes((const uint64_t*)h->amwg_nacc, N, D, naccept_coord));
+        KCHK(amwg_read_planes((const int32_t*)h->amwg_acc, N, D, open.data()));
+        for (size_t k = 0; k < N * D; ++k) naccept_coord[k] += (uint64_t)open[k];
+    }
+    return KLARA_OK;
+}
+
+extern "C" klara_status klara_set_amwg_logsigma(klara_handle* h, const double* logsigma)
+{
+    if (!h || h->d.sampler != KLARA_SAMPLER_AMWG || !logsigma) return KLARA_ERR_INVALID_ARG;
+    if (!h->have_state) return KLARA_ERR_STATE;
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
+    std::vector<double> planes(D * N);
+    for (size_t c = 0; c < N; ++c)
+        for (size_t i = 0; i < D; ++i) {
+            if (!std::isfinite(logsigma[c * D + i])) return KLARA_ERR_INVALID_ARG;
+            planes[i * N + c] = logsigma[c * D + i];
+        }
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpy(h->amwg_logsig, planes.data(), planes.size() * sizeof(double), hipMemcpyHostToDevice));
+    return KLARA_OK;
+}
+
+extern "C" klara_status klara_get_amwg_accept_mask(klara_handle* h, uint32_t* mask, int64_t capacity_steps, int64_t* nsteps_out)
+{
+    if (!h || h->d.sampler != KLARA_SAMPLER_AMWG || capacity_steps < 0) return KLARA_ERR_INVALID_ARG;
+    if (!h->amwg_mask) return KLARA_ERR_STATE;
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    const long long n = h->steps_done < capacity_steps ? h->steps_done : capacity_steps;
+    if (mask && n > 0) HIPCHK(hipMemcpy(mask, h->amwg_mask, (size_t)n * (size_t)h->d.nchains * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (nsteps_out) *nsteps_out = h->steps_done;
+    return KLARA_OK;
+}
+
 extern "C" klara_status klara_device_ptrs(klara_handle* h, void** x, void** logtarget, void** gradlogtarget)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;

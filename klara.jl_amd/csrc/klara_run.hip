@@ -44,6 +44,14 @@ __global__ void k_fill_am(double* Cm, const double* tri, double* mean, const dou
     for (int k = 0; k < D; ++k) { const double v = X[i * D + k]; mean[(long long)k * n + i] = v; mean[(long long)(D + k) * n + i] = v; }
 }
 
+// AMWG: every chain's log proposal scales restart from logsigma0, its counts from zero (AMWG.jl:165-170, 205-214)
+__global__ void k_fill_amwg(double* logsig, const double* logsig0, int* acc, unsigned long long* nacc, long long n, int D)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int k = 0; k < D; ++k) { logsig[(long long)k * n + i] = logsig0[k]; acc[(long long)k * n + i] = 0; nacc[(long long)k * n + i] = 0ull; }
+}
+
 __global__ void k_fill2(double* a, double* b, long long n, double va, double vb)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -163,6 +171,10 @@ static klara_status init_common(klara_handle* h)
         hipLaunchKernelGGL(k_fill_am, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->am_C, h->am_C0, h->am_mean, h->X, (long long)N, (int)D);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(h->am_fallbacks, 0, sizeof(unsigned long long), st));
+    }
+    if (h->amwg_logsig) {
+        hipLaunchKernelGGL(k_fill_amwg, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->amwg_logsig, h->amwg_logsig0, h->amwg_acc, h->amwg_nacc, (long long)N, (int)D);
+        HIPCHK(hipGetLastError());
     }
     const int needgrad = sampler_needs_gradient(d.sampler);
     KParams p = make_params(h);
@@ -450,6 +462,7 @@ hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
     case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     case KLARA_SAMPLER_RAM: return klara_launch_ram(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     case KLARA_SAMPLER_AM: return klara_launch_am(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    case KLARA_SAMPLER_AMWG: return klara_launch_amwg(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     default: return klara_launch_slice(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     }
 }

@@ -320,7 +320,8 @@ class Engine:
                  steps_per_launch: int = 0, stream: int = 0, nstreams: int = 0, bm_batchlen: int = 0, hist_ring_cols: int = 0,
                  acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0,
                  ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None, derived=None,
-                 am_C0=None, am_corescale: float = 0.0, am_minorscale: float = 0.0, am_c: float = 0.0, am_t0: int = 0):
+                 am_C0=None, am_corescale: float = 0.0, am_minorscale: float = 0.0, am_c: float = 0.0, am_t0: int = 0,
+                 amwg_logsigma0=None):
         self._lib = L.load()
         self.target = target
         self.ndims = int(target.ndims)
@@ -394,6 +395,9 @@ class Engine:
                 raise ValueError(f"am_C0 must be {self.ndims} x {self.ndims} (or its diagonal), not {a.shape}")
             keep.append(a); d.am_C0 = _ptr(a)
         d.am_corescale, d.am_minorscale, d.am_c, d.am_t0 = float(am_corescale), float(am_minorscale), float(am_c), int(am_t0)
+        # MuvAMWG(sigma): the D initial log proposal scales (klara_desc.amwg_logsigma0; a number serves every coordinate), AMWG.jl:139-151
+        if amwg_logsigma0 is not None:
+            a = _f64(np.broadcast_to(_f64(amwg_logsigma0).ravel(), (self.ndims,))); keep.append(a); d.amwg_logsigma0 = _ptr(a)
         # pooled marginal histograms (klara_desc.marg_lo / marg_hi / marg_nbins): a Marginals, or (nbins, lo, hi)
         self.marginals = None
         if marginals is not None:
@@ -751,6 +755,27 @@ class Engine:
         k = C.c_int64(0)
         L.check(self._lib.klara_get_am_state(self._h, Cm.ctypes.data, m.ctypes.data, m2.ctypes.data, C.byref(k)), "klara_get_am_state")
         return Cm, m, m2, int(k.value)
+
+    def amwg_state(self):
+        """(logsigma (nchains, ndims), accepted (nchains, ndims) int32, naccept_coord (nchains, ndims) uint64): the AMWG sampler's current log proposal
+        scales, the accepted proposals of the current tuning window and the accepted proposals since set_state / reset, per chain and coordinate
+        (klara_get_amwg_state)."""
+        ls = np.empty((self.nchains, self.ndims)); a = np.empty((self.nchains, self.ndims), dtype=np.int32); n = np.empty((self.nchains, self.ndims), dtype=np.uint64)
+        L.check(self._lib.klara_get_amwg_state(self._h, ls.ctypes.data, a.ctypes.data, n.ctypes.data), "klara_get_amwg_state")
+        return ls, a, n
+
+    def set_amwg_logsigma(self, logsigma) -> None:
+        """warm start of the AMWG sampler: log proposal scales per chain ((nchains, ndims); (ndims,) serves every chain); the schedule is kept"""
+        a = _f64(np.broadcast_to(_f64(logsigma), (self.nchains, self.ndims)))
+        L.check(self._lib.klara_set_amwg_logsigma(self._h, a.ctypes.data), "klara_set_amwg_logsigma")
+
+    def amwg_accept_mask(self) -> np.ndarray:
+        """(transitions, nchains) uint32, bit i set where coordinate i moved (needs MON_ACCEPT; klara_get_amwg_accept_mask)"""
+        n = C.c_int64(0)
+        L.check(self._lib.klara_get_amwg_accept_mask(self._h, None, 0, C.byref(n)), "klara_get_amwg_accept_mask")
+        m = np.empty((n.value, self.nchains), dtype=np.uint32)
+        L.check(self._lib.klara_get_amwg_accept_mask(self._h, m.ctypes.data, n.value, C.byref(n)), "klara_get_amwg_accept_mask")
+        return m
 
     def dual_averaging(self):
         eb = np.empty(self.nchains); hb = np.empty(self.nchains)
