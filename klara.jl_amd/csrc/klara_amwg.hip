@@ -2,10 +2,4 @@
 // The start state is k_init's (the log-target, as for MH); a user-defined target gets the same kernels from the run-time compiler (klara_jit.hip).
 #include "klara_launch.h"
 
-hipError_t klara_launch_amwg(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
-{
-    if (target != KLARA_TARGET_LOGISTIC || G != 1) return hipErrorInvalidValue;
-    return klara_pick<2, 4, 8, 16>(E, [&](auto e) {
-        return launch_transitions<KLARA_SAMPLER_AMWG, KLARA_TARGET_LOGISTIC, decltype(e)::value, 0>(p, kl, mode, grid, lds, st);
-    });
-}
+KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_AMWG) { return launch_group<KLARA_SAMPLER_AMWG>(p, kl, mode, target, E, G, grid, lds, st); }

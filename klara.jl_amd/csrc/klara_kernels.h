@@ -75,30 +75,14 @@ __host__ __device__ __forceinline__ constexpr int ktri(int a, int b, int E) { re
 #ifndef KLARA_E4_WAVES_PLAIN
 #define KLARA_E4_WAVES_PLAIN 3   // the specialised (no tuner, no monitor) E=4 kernels fit 168 VGPRs
 #endif
-#ifdef KLARA_SMMALA_SOFTABS        // the SMMALA kernels with the softabs transform of the metric (run-time compiled only): see k_transitions' launch bounds
+#ifdef KLARA_SMMALA_SOFTABS        // the SMMALA kernels with the softabs transform of the metric (run-time compiled only): see SamplerOf<KLARA_SAMPLER_SMMALA>::waves
 #define KLARA_SMMALA_SOFTABS_E4_ONE_WAVE 1
 #else
 #define KLARA_SMMALA_SOFTABS_E4_ONE_WAVE 0
 #endif
-// RAM kernels, wavefronts per SIMD asked of the compiler (the reasoning is at k_transitions' launch bounds)
-#ifndef KLARA_RAM_WAVES
-#define KLARA_RAM_WAVES(E, MODE) ((E) == 8 ? 1 : 2)
-#endif
 #define KLARA_SLICE_ATT_BITS 14
 #define KLARA_SLICE_MAX_ATT ((1 << KLARA_SLICE_ATT_BITS) - 1)
 #define KLARA_INIT_TRANSITION ((((uint64_t)1) << 40) - 1)
-
-// AM kernels, wavefronts per SIMD asked of the compiler (the covariance's triangle is live through the target's row loop, as RAM's factor is; the second
-// triangle — the factor of corescale C — only until the proposal is formed; the compiler's resource table is in DESIGN.md section 2)
-#ifndef KLARA_AM_WAVES
-#define KLARA_AM_WAVES(E, MODE) ((E) == 8 ? 1 : 2)
-#endif
-
-// AMWG kernels, wavefronts per SIMD asked of the compiler: the chain's 2 D scales and counts next to x and z, and one whole evaluation of the target per
-// coordinate (the compiler's resource table is in DESIGN.md section 2)
-#ifndef KLARA_AMWG_WAVES
-#define KLARA_AMWG_WAVES(E, MODE) ((E) >= 16 ? 1 : (E) == 2 ? 3 : 2)
-#endif
 
 // Device pointers inside KParams are typed as address space 1 (global) in device compilation: the struct is read
 // from memory, and without the qualifier hipcc treats the loaded pointers as generic and emits flat_load/flat_store
@@ -872,6 +856,61 @@ __device__ __forceinline__ bool accept_log_test(const KParams& p, const LaneCtx<
 template <int E>
 struct Proposal { double x[E], g[E], lt; };
 
+// Per-chain registers that travel between HBM and the transition loop.
+template <int E>
+struct ChainRegs {
+    double x[E], g[E];
+    double lt;
+    double step; long long accepted, proposed, totproposed;
+    double epsbar, hbar;
+};
+
+// ------------------------------------------------------------------------------------------------
+// A sampler is one unit: SamplerOf<KLARA_SAMPLER_x>, specialised next to the sampler's step function, holds everything the transition kernel
+// (k_transitions, below) needs to know about it — the kernel names no sampler.  DESIGN.md section 1 lists what a new one has to provide.
+// ------------------------------------------------------------------------------------------------
+// What the kernel hands a sampler's step for one transition of the chain group it is on — the same list for every sampler, under these names: p, tg, cx
+// (the launch, the target, the lane's place), gchain, t (the chain's place in the stream), z, ad (the transition's normals and accept draw, formed up front for
+// the samplers that ask: NEEDZ), h (the step size, by value), vp (the per-element parameter — MH's proposal scales, the slice widths: VECPARAM), cur (the
+// chain's registers) and prop (where a proposal is handed back: COMMIT = false); the sampler's own state follows.  They are separate arguments, and the
+// tuner's registers are not among them (a sampler that adapts them does so in State::tune), because that is what keeps the compiler's registers: gathered
+// into one struct of references the same code took other register counts in 53 of the 175 built-in kernels, and a reference to the tuner's registers
+// that MALA never reads cost one of its kernels 18 (profiles/sampler_policy_resources.txt).  For the same reason what a kernel's MODE settles comes to the
+// step as template arguments (PLAIN, COMMIT, MONITORED: nothing of the monitor is stored), not as values.
+#define KLARA_STEP_ARGS(E) const KParams& p, const T& tg, const LaneCtx<E>& cx, unsigned long long gchain, unsigned long long t, const double (&z)[E], \
+                           const AccDraw& ad, double h, const double (&vp)[E], ChainRegs<E>& cur, Proposal<E>& prop
+
+// Wavefronts per SIMD asked of the compiler by the samplers that keep no matrix per chain; e4_logistic: the sampler's own figure for the logistic
+// target at E = 4 (0: none).
+constexpr int group_waves(int TARGET, int E, int GT, int MODE, int e4_logistic = 0)
+{
+    if (TARGET == KLARA_TARGET_CUSTOM && GT > 1) return 2;      // staged closures: two workgroups' rows fit a CU's LDS
+    if (E == 2) return TARGET == KLARA_TARGET_GAUSS_DIAG ? KLARA_E2_DIAG_WAVES : 3;
+    if (E == 4) return TARGET == KLARA_TARGET_LOGISTIC && e4_logistic != 0 ? e4_logistic : (MODE & 3) == 3 ? KLARA_E4_WAVES_PLAIN : KLARA_E4_WAVES;
+    return E == 8 && TARGET == KLARA_TARGET_LOGISTIC ? KLARA_E8_WAVES_LOGISTIC : 1;
+}
+
+// The answers most samplers give; a specialisation restates what differs.
+struct SamplerDefaults {
+    static constexpr bool NEEDG = false;         // carries the gradient with the state
+    static constexpr bool NEEDZ = true;          // takes the transition's normals up front (lane_normals)
+    static constexpr bool INPLACE = false;       // commits coordinate by coordinate in place: no proposal is handed back, the state being left is folded before the step
+    static constexpr bool ALWAYS_MOVES = false;  // every transition moves: accepts are not counted for the tuner, the state is always written back
+    static constexpr bool TUNED = true;          // has step-size tuner state (false: every kernel is a PLAIN one, nothing counts)
+    static constexpr bool VECPARAM = false;      // reads KParams::vecparam
+    static constexpr bool ADAPTS_STEP = false;   // adapts the tuner's registers itself after its step: State::tune<PLAIN>(p, tn, t)
+    static constexpr bool prefetch(int E) { return true; }       // one transition per launch: the next group's loads are issued before this group's transition
+    static constexpr bool memsums(int E) { return false; }       // folds the running sums straight into memory on every target (k_transitions MEMSUMS)
+    static constexpr bool built_in(int TARGET, int E) { return true; }                  // the built-in targets and elements per lane it is instantiated for (launch_group)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return group_waves(TARGET, E, GT, MODE); }
+    // per-chain state beyond ChainRegs: taken up when the wavefront gets to a group, put back by the group's writer lanes when it leaves
+    template <int E> struct State {
+        template <class T, bool MONITORED> __device__ __forceinline__ void take(const KParams&, const T&, const LaneCtx<E>&, const ChainRegs<E>&, unsigned long long) {}
+        __device__ __forceinline__ void put(const KParams&, const LaneCtx<E>&) const {}
+    };
+};
+template <int SAMPLER> struct SamplerOf;
+
 // iterate!(job, MH, Multivariate) — iterate/MH.jl:72-124 (symmetric normalised branch)
 template <class T, int E, bool COMMIT = true>
 __device__ __forceinline__ bool step_mh(const KParams& p, const T& tg, const LaneCtx<E>& cx,
@@ -899,6 +938,12 @@ KLARA_PRAGMA_UNROLL_E
     }
     return acc;
 }
+
+template <> struct SamplerOf<KLARA_SAMPLER_MH> : SamplerDefaults {
+    static constexpr bool VECPARAM = true;
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>&) { return step_mh<T, E, COMMIT>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop); }
+};
 
 // iterate!(job, MALA, Multivariate) — iterate/MALA.jl:78-128
 template <class T, int E, bool PLAIN, bool COMMIT = true>
@@ -951,6 +996,16 @@ KLARA_PRAGMA_UNROLL_E
     }
     return acc;
 }
+
+template <> struct SamplerOf<KLARA_SAMPLER_MALA> : SamplerDefaults {
+    static constexpr bool NEEDG = true;
+    // (the logistic target at E = 4 — cfg 4 — asks for 4 wavefronts per SIMD where KLARA_E4_WAVES_LOGISTIC says so: its row loop is a chain of exp / log /
+    //  division latencies that two wavefronts cannot cover; the 128-register budget spills 156-272 B outside the row loop and still measured 1.01e9 against
+    //  8.1e8 transitions/s with running sums, 1.05e9 against 9.4e8 without, same box)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return group_waves(TARGET, E, GT, MODE, KLARA_E4_WAVES_LOGISTIC); }
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>&) { return step_mala<T, E, PLAIN, COMMIT>(p, tg, cx, gchain, t, z, ad, h, cur.x, cur.g, cur.lt, prop); }
+};
 
 // ---- SMMALA (src/samplers/SMMALA.jl, iterate/SMMALA.jl:107-221): the metric G(x) of a chain, its Cholesky factor and the drift --------
 // All of it in the lane's registers, over all E elements: the padding elements i >= D get G_ii = 1 and zero off the diagonal, so their
@@ -1038,7 +1093,7 @@ KLARA_PRAGMA_UNROLL_E
 // klara_desc.smmala_softabs > 0 (run-time compiled kernels only: klara_jit.hip defines KLARA_SMMALA_SOFTABS next to KLARA_SMMALA): the metric, with T::metric_diag
 // added, becomes softabs(G, a) in the lane's registers (klara_softabs.h; KLARA_D is the job's dimension, so every loop unrolls) before it is factored.  The
 // factorisation then has nothing left to add to the diagonal: the value returned is what it is handed as `diag`.
-// The eigenvectors (D^2 doubles a lane) are registers up to D = 4, where the kernels then take one wavefront per SIMD (k_transitions' launch bounds: at two, the
+// The eigenvectors (D^2 doubles a lane) are registers up to D = 4, where the kernels then take one wavefront per SIMD (SamplerOf<KLARA_SAMPLER_SMMALA>::waves: at two, the
 // 256 registers spill 20-120 B; in LDS they spilled more, 68-336 B).  From D = 5 on (E = 8) they live in the workgroup's LDS, entry by entry interleaved over its 256
 // lanes (a wavefront's access is 64 consecutive doubles: no bank conflict): 128 registers on top of a kernel that already fills the 512 of one wavefront per
 // SIMD — 1,000-1,180 B of scratch a lane with them in registers, 280-430 B with them in LDS (128 KB at D = 8, which that occupancy leaves free: one workgroup per
@@ -1132,6 +1187,26 @@ KLARA_PRAGMA_UNROLL_E
     return acc;
 }
 
+template <> struct SamplerOf<KLARA_SAMPLER_SMMALA> : SamplerDefaults {
+    static constexpr bool NEEDG = true;
+    static constexpr bool built_in(int TARGET, int E) { return TARGET == KLARA_TARGET_LOGISTIC && E <= 8; }
+    // two factor states of E (E + 3) / 2 + 1 doubles and the metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2; with the softabs
+    // transform's eigenvectors: 20-120 B in every mode)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2; }
+    // the factor state of the group's current states, formed again from x and its gradient at every launch (the same operations as when the state was
+    // accepted, so the bits do not depend on the launch length); a state is only ever reached through a positive-definite metric (checked at the start
+    // state by k_init_smmala)
+    template <int E> struct State : SamplerDefaults::State<E> {
+        SmmalaRegs<E> s;
+        template <class T, bool MONITORED> __device__ __forceinline__ void take(const KParams& p, const T& tg, const LaneCtx<E>& cx, const ChainRegs<E>& cur, unsigned long long)
+        {
+            smmala_state_at<T, E>(p, tg, cx, cur.x, cur.g, s);
+        }
+    };
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>& st) { return step_smmala<T, E, PLAIN, COMMIT>(p, tg, cx, gchain, t, z, ad, h, cur.x, cur.g, cur.lt, st.s, prop); }
+};
+
 // ---- RAM (src/samplers/RAM.jl, iterate/RAM.jl:65-130, after Vihola 2012): the random walk x' = x + S z whose factor S the chain adapts ----
 // S is the chain's E x E lower factor in the lane's registers, packed like SmmalaRegs::L (S_ij, i >= j, at ktri(j, i, E)); the padding i >= D holds the
 // identity block and z is zero there, so every padded term below is an exact zero and the padded block of the new factor is the identity again,
@@ -1141,33 +1216,31 @@ struct RamRegs {
     static constexpr int NT = E * (E + 1) / 2;
     double S[NT];
     unsigned long long skipped;      // updates of this launch that were skipped
-};
-template <int E>
-__device__ __forceinline__ void ram_load(const KParams& p, const LaneCtx<E>& cx, RamRegs<E>& r)
-{
-    const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's factor and store nothing)
+    template <class T, bool MONITORED> __device__ __forceinline__ void take(const KParams& p, const T&, const LaneCtx<E>& cx, const ChainRegs<E>&, unsigned long long)
+    {
+        const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's factor and store nothing)
 KLARA_PRAGMA_UNROLL_E
-    for (int j = 0; j < E; ++j) {
+        for (int j = 0; j < E; ++j) {
 KLARA_PRAGMA_UNROLL_E
-        for (int i = j; i < E; ++i) {
-            double v = i == j ? 1.0 : 0.0;
-            if (i < p.D) v = p.ram_S[(long long)ktri(j, i, p.D) * p.nchains + c0];
-            r.S[ktri(j, i, E)] = v;
+            for (int i = j; i < E; ++i) {
+                double v = i == j ? 1.0 : 0.0;
+                if (i < p.D) v = p.ram_S[(long long)ktri(j, i, p.D) * p.nchains + c0];
+                S[ktri(j, i, E)] = v;
+            }
         }
+        skipped = 0;
     }
-    r.skipped = 0;
-}
-template <int E>
-__device__ __forceinline__ void ram_store(const KParams& p, const LaneCtx<E>& cx, const RamRegs<E>& r)
-{
+    __device__ __forceinline__ void put(const KParams& p, const LaneCtx<E>& cx) const
+    {
 KLARA_PRAGMA_UNROLL_E
-    for (int j = 0; j < E; ++j) {
+        for (int j = 0; j < E; ++j) {
 KLARA_PRAGMA_UNROLL_E
-        for (int i = j; i < E; ++i)
-            if (i < p.D) p.ram_S[(long long)ktri(j, i, p.D) * p.nchains + cx.chain] = r.S[ktri(j, i, E)];
+            for (int i = j; i < E; ++i)
+                if (i < p.D) p.ram_S[(long long)ktri(j, i, p.D) * p.nchains + cx.chain] = S[ktri(j, i, E)];
+        }
+        if (skipped != 0) atomicAdd((unsigned long long*)p.ram_skipped, skipped);
     }
-    if (r.skipped != 0) atomicAdd((unsigned long long*)p.ram_skipped, r.skipped);
-}
+};
 // The in-place factorisation RAM and AM share (smmala_factor's loop nest without log-determinant and diag term): the packed lower triangle A (A_ij, i >= j,
 // at ktri(j, i, E)) becomes its Cholesky factor, column by column, one sqrt and one reciprocal per pivot; false where a pivot is not a finite positive number
 template <int E>
@@ -1259,6 +1332,21 @@ KLARA_PRAGMA_UNROLL_E
     return acc;
 }
 
+template <> struct SamplerOf<KLARA_SAMPLER_RAM> : SamplerDefaults {
+    static constexpr bool built_in(int TARGET, int E) { return TARGET == KLARA_TARGET_LOGISTIC && E <= 8; }
+    // The factor S, E (E + 1) / 2 doubles, is live through the whole transition — the target's row loop included — and a second triangle while
+    // S S' + c w w' is formed and factored in place: 2 E (E + 1) registers before x, x', z and w — 144 at E = 8.  From the compiler's resource report on the
+    // logistic target: E = 2 takes 168-215 registers and E = 4 205-253 — two wavefronts per SIMD without scratch (asked for three they spill 32-160 B and
+    // 116-304 B); E = 8 takes 256 + 40-80 accumulation registers at one wavefront per SIMD without scratch, and spills 136-304 B at two.  So 2, 2, 1: no RAM
+    // kernel uses scratch; DESIGN.md section 2 and profiles/ram.txt have the table.
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return E == 8 ? 1 : 2; }
+    // the group's factors come from memory with the group and go back when the wavefront leaves it, so a launch continues where the last one stopped
+    // whatever its length
+    template <int E> using State = RamRegs<E>;
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>& st) { return step_ram<T, E, COMMIT>(p, tg, cx, gchain, t, z, ad, st, cur.x, cur.lt, prop); }
+};
+
 // ---- AM (src/samplers/AM.jl, iterate/AM.jl:77-152, after Haario, Saksman and Tamminen 2001 with the mixture proposal of Roberts and Rosenthal 2009) ----
 // C is the chain's E x E covariance in the lane's registers, its upper triangle packed (C_ij, i <= j, at ktri(i, j, E): Hermitian(C), iterate/AM.jl:91,
 // keeps that triangle); m and m2 are lastmean and secondlastmean.  The padding i >= D of C holds the identity block, the update is masked to the D x D
@@ -1269,45 +1357,43 @@ struct AmRegs {
     static constexpr int NT = E * (E + 1) / 2;
     double C[NT], m[E], m2[E];
     unsigned long long fallbacks;    // transitions of this launch at which corescale C did not factor
-};
-// (the planes of a chain are walked with running offsets: entry (i, j), i <= j < D, in this order is plane ktri(i, j, D), the next one; 52 plane
-//  offsets formed at once at E = 8 would not fit the scalar registers)
-template <int E>
-__device__ __forceinline__ void am_load(const KParams& p, const LaneCtx<E>& cx, AmRegs<E>& r)
-{
-    const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's state and store nothing)
-    const gdouble* pc = p.am_C + c0;
-    const gdouble* pm = p.am_mean + c0;
-    const long long m2off = (long long)p.D * p.nchains;
+    // (the planes of a chain are walked with running offsets: entry (i, j), i <= j < D, in this order is plane ktri(i, j, D), the next one; 52 plane
+    //  offsets formed at once at E = 8 would not fit the scalar registers)
+    template <class T, bool MONITORED> __device__ __forceinline__ void take(const KParams& p, const T&, const LaneCtx<E>& cx, const ChainRegs<E>&, unsigned long long)
+    {
+        const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's state and store nothing)
+        const gdouble* pc = p.am_C + c0;
+        const gdouble* pm = p.am_mean + c0;
+        const long long m2off = (long long)p.D * p.nchains;
 KLARA_PRAGMA_UNROLL_E
-    for (int i = 0; i < E; ++i) {
+        for (int i = 0; i < E; ++i) {
 KLARA_PRAGMA_UNROLL_E
-        for (int j = i; j < E; ++j) {
-            double v = i == j ? 1.0 : 0.0;
-            if (j < p.D) { v = *pc; pc += p.nchains; }
-            r.C[ktri(i, j, E)] = v;
+            for (int j = i; j < E; ++j) {
+                double v = i == j ? 1.0 : 0.0;
+                if (j < p.D) { v = *pc; pc += p.nchains; }
+                C[ktri(i, j, E)] = v;
+            }
+            double a = 0.0, b = 0.0;
+            if (i < p.D) { a = pm[0]; b = pm[m2off]; pm += p.nchains; }
+            m[i] = a; m2[i] = b;
         }
-        double a = 0.0, b = 0.0;
-        if (i < p.D) { a = pm[0]; b = pm[m2off]; pm += p.nchains; }
-        r.m[i] = a; r.m2[i] = b;
+        fallbacks = 0;
     }
-    r.fallbacks = 0;
-}
-template <int E>
-__device__ __forceinline__ void am_store(const KParams& p, const LaneCtx<E>& cx, const AmRegs<E>& r)
-{
-    gdouble* pc = p.am_C + cx.chain;
-    gdouble* pm = p.am_mean + cx.chain;
-    const long long m2off = (long long)p.D * p.nchains;
+    __device__ __forceinline__ void put(const KParams& p, const LaneCtx<E>& cx) const
+    {
+        gdouble* pc = p.am_C + cx.chain;
+        gdouble* pm = p.am_mean + cx.chain;
+        const long long m2off = (long long)p.D * p.nchains;
 KLARA_PRAGMA_UNROLL_E
-    for (int i = 0; i < E; ++i) {
+        for (int i = 0; i < E; ++i) {
 KLARA_PRAGMA_UNROLL_E
-        for (int j = i; j < E; ++j)
-            if (j < p.D) { *pc = r.C[ktri(i, j, E)]; pc += p.nchains; }
-        if (i < p.D) { pm[0] = r.m[i]; pm[m2off] = r.m2[i]; pm += p.nchains; }
+            for (int j = i; j < E; ++j)
+                if (j < p.D) { *pc = C[ktri(i, j, E)]; pc += p.nchains; }
+            if (i < p.D) { pm[0] = m[i]; pm[m2off] = m2[i]; pm += p.nchains; }
+        }
+        if (fallbacks != 0) atomicAdd((unsigned long long*)p.am_fallbacks, fallbacks);
     }
-    if (r.fallbacks != 0) atomicAdd((unsigned long long*)p.am_fallbacks, r.fallbacks);
-}
+};
 // covariance!(C, C, k, x, lastmean, secondlastmean), stats/covariance.jl:6-19, on the triangle Hermitian(C) keeps (iterate/AM.jl:87-91): entry (i, j), i <= j,
 // with i as the row of the three rank-one updates; plain products and sums in the reference's order
 template <int E>
@@ -1395,6 +1481,20 @@ KLARA_PRAGMA_UNROLL_E
     return acc;
 }
 
+template <> struct SamplerOf<KLARA_SAMPLER_AM> : SamplerDefaults {
+    static constexpr bool built_in(int TARGET, int E) { return TARGET == KLARA_TARGET_LOGISTIC && E <= 8; }
+    // (E = 8 does not prefetch: with the second lane context the kernel's scalar registers spill into vector registers it has none left for, 28 B of
+    //  scratch in the compiler's report; the order of the loads changes no bit)
+    static constexpr bool prefetch(int E) { return E != 8; }
+    // (the covariance's triangle is live through the target's row loop, as RAM's factor is; the second triangle — the factor of corescale C — only until
+    //  the proposal is formed; the compiler's resource table is in DESIGN.md section 2)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return E == 8 ? 1 : 2; }
+    // the group's covariances and running means travel as RAM's factors do
+    template <int E> using State = AmRegs<E>;
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>& st) { return step_am<T, E, COMMIT>(p, tg, cx, gchain, t, z, ad, st, cur.x, cur.lt, prop); }
+};
+
 // ---- AMWG (src/samplers/AMWG.jl, iterate/AMWG.jl:82-171, tuners/RobertsRosenthalMCTuner.jl, after Roberts and Rosenthal 2009 section 3) ----
 // One chain per lane (G == 1; the row-split lanes of the logistic target replicate it): logsig and acc are the chain's log proposal scales and its accepted
 // proposals of the current tuning window.  The padding e >= D is loaded as zero, never proposed and never stored.  They travel between launches in
@@ -1404,29 +1504,34 @@ template <int E>
 struct AmwgRegs {
     double logsig[E];
     int acc[E];
-};
-template <int E>
-__device__ __forceinline__ void amwg_load(const KParams& p, const LaneCtx<E>& cx, AmwgRegs<E>& r)
-{
-    const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's state and store nothing)
-    const gdouble* pl = p.amwg_logsig + c0;
-    const gint* pa = p.amwg_acc + c0;
+    // the tuner's schedule follows from the transition index alone (count = t + 1: phase = count mod period, batch = count / period), so it is formed once
+    // per launch and stepped without a division; mask, row: the coordinate masks of the launch's transitions, where they are monitored, and the transition's row
+    int phase; long long batch;
+    KGLOBAL uint32_t* mask; int row;
+    template <class T, bool MONITORED> __device__ __forceinline__ void take(const KParams& p, const T&, const LaneCtx<E>& cx, const ChainRegs<E>&, unsigned long long t0)
+    {
+        const long long c0 = cx.chain_ok ? cx.chain : 0;      // (lanes past the last chain read chain 0's state and store nothing)
+        const gdouble* pl = p.amwg_logsig + c0;
+        const gint* pa = p.amwg_acc + c0;
 KLARA_PRAGMA_UNROLL_E
-    for (int e = 0; e < E; ++e) {
-        double v = 0.0; int a = 0;
-        if (e < p.D) { v = *pl; a = *pa; pl += p.nchains; pa += p.nchains; }
-        r.logsig[e] = v; r.acc[e] = a;
+        for (int e = 0; e < E; ++e) {
+            double v = 0.0; int a = 0;
+            if (e < p.D) { v = *pl; a = *pa; pl += p.nchains; pa += p.nchains; }
+            logsig[e] = v; acc[e] = a;
+        }
+        phase = (int)((long long)t0 % (long long)p.period); batch = (long long)t0 / (long long)p.period;
+        mask = nullptr; row = 0;
+        if (MONITORED && p.amwg_mask != nullptr) mask = p.amwg_mask + t0 * (unsigned long long)p.nchains;
     }
-}
-template <int E>
-__device__ __forceinline__ void amwg_store(const KParams& p, const LaneCtx<E>& cx, const AmwgRegs<E>& r)
-{
-    gdouble* pl = p.amwg_logsig + cx.chain;
-    gint* pa = p.amwg_acc + cx.chain;
+    __device__ __forceinline__ void put(const KParams& p, const LaneCtx<E>& cx) const
+    {
+        gdouble* pl = p.amwg_logsig + cx.chain;
+        gint* pa = p.amwg_acc + cx.chain;
 KLARA_PRAGMA_UNROLL_E
-    for (int e = 0; e < E; ++e)
-        if (e < p.D) { *pl = r.logsig[e]; *pa = r.acc[e]; pl += p.nchains; pa += p.nchains; }
-}
+        for (int e = 0; e < E; ++e)
+            if (e < p.D) { *pl = logsig[e]; *pa = acc[e]; pl += p.nchains; pa += p.nchains; }
+    }
+};
 // iterate!(job, MuvAMWG, Multivariate) — iterate/AMWG.jl:82-171 as DESIGN.md section 2 (W1-W6) states it: the sweep over the coordinates in order, each
 // one MH step on its own coordinate (the candidate replaces x_i in a copy of the state, W1), then — `tuning`: count is a multiple of the period — the
 // tuner's move of every coordinate's log scale by `delta` (RobertsRosenthalMCTuner.jl:99-108; a coordinate's scale is read by its own step alone, so moving
@@ -1487,6 +1592,32 @@ KLARA_PRAGMA_UNROLL_E
     }
     return moved;
 }
+
+template <> struct SamplerOf<KLARA_SAMPLER_AMWG> : SamplerDefaults {
+    static constexpr bool NEEDZ = false;         // (draws coordinate by coordinate, step_amwg)
+    static constexpr bool INPLACE = true;
+    static constexpr bool TUNED = false;         // (its tuner moves the scales, not a step size: cnt_predicate)
+    static constexpr bool built_in(int TARGET, int E) { return TARGET == KLARA_TARGET_LOGISTIC && E <= 16; }
+    static constexpr bool prefetch(int E) { return E < 8; }
+    // (E = 32: 4 E registers of sums next to the chain's 3 E of scales and counts spilled, 60 B in the compiler's report; a sweep is D evaluations)
+    static constexpr bool memsums(int E) { return E >= 32; }
+    // (the chain's 2 D scales and counts next to x and z, and one whole evaluation of the target per coordinate; the compiler's resource table is in
+    //  DESIGN.md section 2)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return E >= 16 ? 1 : E == 2 ? 3 : 2; }
+    template <int E> using State = AmwgRegs<E>;     // (the scales and window counts travel as RAM's factors do)
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>& st)
+    {
+        st.phase = (st.phase + 1 == p.period) ? 0 : st.phase + 1;
+        const bool tuning = st.phase == 0;                               // count % period == 0
+        st.batch += tuning ? 1 : 0;                                      // count / period
+        const double rs = 1.0 / __builtin_sqrt((double)st.batch);        // (W2: batch^-0.5)
+        const uint32_t moved = step_amwg<T, E>(p, tg, cx, gchain, t, tuning, rs < 0.01 ? rs : 0.01, st, cur.x, cur.lt);
+        if (MONITORED && st.mask != nullptr && cx.chain_ok && cx.q == 0 && cx.rq == 0) st.mask[(long long)st.row * p.nchains + cx.chain] = moved;
+        ++st.row;
+        return moved != 0u;
+    }
+};
 
 // iterate!(job, HMC, Multivariate) — iterate/HMC.jl:124-201; leapfrog! samplers.jl:122-134;
 // hamiltonian samplers.jl:103
@@ -1572,6 +1703,22 @@ KLARA_PRAGMA_UNROLL_E
     }
     return acc;
 }
+template <> struct SamplerOf<KLARA_SAMPLER_HMC> : SamplerDefaults {
+    static constexpr bool NEEDG = true, ADAPTS_STEP = true;
+    // (the logistic target at E = 4 has a figure of its own, as MALA's)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return group_waves(TARGET, E, GT, MODE, KLARA_E4_WAVES_LOGISTIC_HMC); }
+    // dual averaging: the trajectory's length follows the step size, and the step size the transition's acceptance probability
+    template <int E> struct State : SamplerDefaults::State<E> {
+        double a_prob;
+        template <bool PLAIN> __device__ __forceinline__ void tune(const KParams& p, TuneRegs& tn, unsigned long long t) const { if (KDA) da_update(p, tn, (long long)t + 1, a_prob); }     // iterate/HMC.jl:225-249
+    };
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>& st)
+    {
+        st.a_prob = 0.0;
+        return step_hmc<T, E, PLAIN, COMMIT>(p, tg, cx, gchain, t, z, ad, h, KDA ? (cx.chain_ok ? da_nleaps(p, h) : 1) : p.nleaps, st.a_prob, cur.x, cur.g, cur.lt, prop);
+    }
+};
 
 // iterate!(job, SliceSampler, Multivariate) — iterate/SliceSampler.jl:60-109 — with THE CHAINS OF A WAVEFRONT OUT OF LOCKSTEP (round 5).
 // A probe is a full evaluation of the log-target (the reference calls logtarget! on the whole vector, :77-94), made by all chains of the wavefront
@@ -1765,18 +1912,20 @@ __device__ __forceinline__ bool step_slice(const KParams& p, const T& tg, const 
     return step_slice_lockstep<T, E>(p, tg, cx, gchain, t, widths, x, lt, stuck);
 }
 
+template <> struct SamplerOf<KLARA_SAMPLER_SLICE> : SamplerDefaults {
+    static constexpr bool NEEDZ = false, INPLACE = true, ALWAYS_MOVES = true, VECPARAM = true;
+    template <int E> struct State : SamplerDefaults::State<E> {
+        bool stuck;                      // a chain of the group ran out of attempts
+        template <class T, bool MONITORED> __device__ __forceinline__ void take(const KParams&, const T&, const LaneCtx<E>&, const ChainRegs<E>&, unsigned long long) { stuck = false; }
+        __device__ __forceinline__ void put(const KParams& p, const LaneCtx<E>&) const { if (stuck) klara_raise(p.error_flag, KLARA_ERR_SLICE_STUCK); }
+    };
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>& st) { return step_slice<T, E>(p, tg, cx, gchain, t, vp, cur.x, cur.lt, st.stuck); }
+};
+
 // ------------------------------------------------------------------------------------------------
 // the transition kernel: run(job) loop of BasicMCJob.jl:219-238 for p.nsteps transitions
 // ------------------------------------------------------------------------------------------------
-// Per-chain registers that travel between HBM and the transition loop.
-template <int E>
-struct ChainRegs {
-    double x[E], g[E];
-    double lt;
-    double step; long long accepted, proposed, totproposed;
-    double epsbar, hbar;
-};
-
 template <int E, bool NEEDG, bool PLAIN>
 __device__ __forceinline__ void load_chain(const KParams& p, const LaneCtx<E>& cx, ChainRegs<E>& r, long long first_chain, int here)
 {
@@ -1813,42 +1962,24 @@ KLARA_PRAGMA_UNROLL_E
 // MODE bit 0 (PLAIN): nothing counts / tunes.  MODE bit 1 (NOMON): no monitor at all (no accept mask, running sums or
 // history) — the save-rule bookkeeping disappears from the generated code.
 template <int SAMPLER, int TARGET, int E, int GT, int MODE>
-// (MALA and HMC on the logistic target at E = 4 — cfg 4 — ask for 4 wavefronts per SIMD: its row loop is a chain of exp / log / division latencies that two
-//  wavefronts cannot cover; the 128-register budget spills 156-272 B outside the row loop and still measured 1.01e9 against 8.1e8
-//  transitions/s with running sums, 1.05e9 against 9.4e8 without, same box)
-// (RAM: the factor S, E (E + 1) / 2 doubles, is live through the whole transition — the target's row loop included — and a second triangle while
-//  S S' + c w w' is formed and factored in place: 2 E (E + 1) registers before x, x', z and w — 144 at E = 8.  From the compiler's resource report on the
-//  logistic target: E = 2 takes 168-215 registers and E = 4 205-253 — two wavefronts per SIMD without scratch (asked for three they spill 32-160 B and
-//  116-304 B); E = 8 takes 256 + 40-80 accumulation registers at one wavefront per SIMD without scratch, and spills 136-304 B at two.  So 2, 2, 1: no RAM
-//  kernel uses scratch; DESIGN.md section 2 and profiles/ram.txt have the table)
-__global__ __launch_bounds__(256, (SAMPLER == KLARA_SAMPLER_RAM ? KLARA_RAM_WAVES(E, MODE) :
-                                   SAMPLER == KLARA_SAMPLER_AM ? KLARA_AM_WAVES(E, MODE) :
-                                   SAMPLER == KLARA_SAMPLER_AMWG ? KLARA_AMWG_WAVES(E, MODE) :
-                                   SAMPLER == KLARA_SAMPLER_SMMALA ? (E == 8 || (E == 4 && (!(MODE & 1) || KLARA_SMMALA_SOFTABS_E4_ONE_WAVE)) ? 1 : 2) /* SMMALA: two factor states of E (E + 3) / 2 + 1 doubles and the
-                                                                                                  metric's triangle (E = 4 with the tuner's registers: 96 B of scratch at 2; with the
-                                                                                                  softabs transform's eigenvectors: 20-120 B in every mode) */ :
-                                   TARGET == KLARA_TARGET_CUSTOM && GT > 1 ? 2 /* staged closures: two workgroups' rows fit a CU's LDS */ :
-                                   E == 2 ? (TARGET == KLARA_TARGET_GAUSS_DIAG ? KLARA_E2_DIAG_WAVES : 3) : (E == 4 ? (TARGET == KLARA_TARGET_LOGISTIC && SAMPLER == KLARA_SAMPLER_MALA ? KLARA_E4_WAVES_LOGISTIC
-                                                                  : TARGET == KLARA_TARGET_LOGISTIC && SAMPLER == KLARA_SAMPLER_HMC ? KLARA_E4_WAVES_LOGISTIC_HMC
-                                                                  : ((MODE & 3) == 3 ? KLARA_E4_WAVES_PLAIN : KLARA_E4_WAVES))
-                                                  : (E == 8 && TARGET == KLARA_TARGET_LOGISTIC ? KLARA_E8_WAVES_LOGISTIC : 1))))
+__global__ __launch_bounds__(256, SamplerOf<SAMPLER>::waves(TARGET, E, GT, MODE))
 void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
 {
-    constexpr bool PLAIN = (MODE & 1) != 0 || SAMPLER == KLARA_SAMPLER_AMWG /* (no step-size tuner state: nothing counts, cnt_predicate) */, NOMON = (MODE & 2) != 0;
+    using S = SamplerOf<SAMPLER>;
+    constexpr bool PLAIN = (MODE & 1) != 0 || !S::TUNED, NOMON = (MODE & 2) != 0;
     constexpr bool ONESTEP = (MODE & 4) != 0;          // exactly one transition per launch (= one iterate!)
     const int nsteps = ONESTEP ? 1 : kl.nsteps;
     constexpr bool RSPL = TARGET == KLARA_TARGET_LOGISTIC;
     // single unmonitored transition: an accepted proposal goes from the proposal registers straight to HBM
-    constexpr bool DIRECT = ONESTEP && NOMON && SAMPLER != KLARA_SAMPLER_SLICE && SAMPLER != KLARA_SAMPLER_AMWG;
+    constexpr bool DIRECT = ONESTEP && NOMON && !S::INPLACE;
     // monitored jobs: the step functions hand the proposal back and the commit happens here, after the state being left has been
     // folded into the running sums (KParams::held)
-    constexpr bool OUTER = !NOMON && SAMPLER != KLARA_SAMPLER_SLICE && SAMPLER != KLARA_SAMPLER_AMWG;     // (the slice sampler and AMWG commit coordinate by coordinate, in place)
+    constexpr bool OUTER = !NOMON && !S::INPLACE;
     // The logistic targets fold the running sums of a chain that moves straight into memory (a read-modify-write of 2 D values per
     // accepted transition, against ~3,000 vector instructions of a transition) instead of keeping 4 E registers of sums resident:
     // with them the 128-register kernels of cfg 4 (4 wavefronts per SIMD) spilled.  Everything else keeps resident sums (the README
-    // job runs a transition in ~60 instructions: a memory round trip per accepted move would dominate it).
-    // (AMWG at E = 32 likewise: 4 E registers of sums next to the chain's 3 E of scales and counts spilled, 60 B in the compiler's report; a sweep is D evaluations)
-    constexpr bool MEMSUMS = TARGET == KLARA_TARGET_LOGISTIC || (SAMPLER == KLARA_SAMPLER_AMWG && E >= 32);
+    // job runs a transition in ~60 instructions: a memory round trip per accepted move would dominate it), but for a sampler's own exceptions.
+    constexpr bool MEMSUMS = TARGET == KLARA_TARGET_LOGISTIC || S::memsums(E);
     const KParams& p = *pp;
     kd_tables_to_lds();
     guchar* const accept_out = (!NOMON && p.accept != nullptr) ? p.accept + kl.t0 * (unsigned long long)p.nchains : nullptr;
@@ -1857,14 +1988,13 @@ void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
     gdouble* const hist_g = NOMON ? nullptr : p.hist_g;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using T = typename TargetSel<TARGET, E>::type;
-    constexpr bool NEEDG = (SAMPLER == KLARA_SAMPLER_MALA || SAMPLER == KLARA_SAMPLER_HMC || SAMPLER == KLARA_SAMPLER_SMMALA);
-    constexpr bool NEEDZ = (SAMPLER != KLARA_SAMPLER_SLICE && SAMPLER != KLARA_SAMPLER_AMWG);     // (AMWG draws coordinate by coordinate, step_amwg)
+    constexpr bool NEEDG = S::NEEDG, NEEDZ = S::NEEDZ;
 
     LaneCtx<E> cx = make_ctx<E, GT, RSPL>(p);
     T tg;
     tg.init(p, cx, reinterpret_cast<double*>(smem));
     double vp[E];
-    if (SAMPLER == KLARA_SAMPLER_MH || SAMPLER == KLARA_SAMPLER_SLICE) load_param<E>(cx, p.vecparam, p.D, 1.0, vp);
+    if (S::VECPARAM) load_param<E>(cx, p.vecparam, p.D, 1.0, vp);
 
     const int cpw = 64 / (cx.G * cx.RS);
     const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6);
@@ -1884,9 +2014,7 @@ void k_transitions(const KParams* __restrict__ pp, const KLaunch kl)
         // of the launch).  Fused launches amortise that latency over their transitions and load the next group when they get to it —
         // the prefetched copy would hold 2 E + 8 registers through every transition (logistic MALA at 4 wavefronts per SIMD: the
         // difference between fitting 128 registers and spilling).
-        // (AM at E = 8 does not prefetch either: with the second lane context the kernel's scalar registers spill into vector registers it has none left for,
-        //  28 B of scratch in the compiler's report; the order of the loads changes no bit)
-        constexpr bool PREFETCH = ONESTEP && !(SAMPLER == KLARA_SAMPLER_AM && E == 8) && !(SAMPLER == KLARA_SAMPLER_AMWG && E >= 8);
+        constexpr bool PREFETCH = ONESTEP && S::prefetch(E);
         const long long grp_next = grp + nwaves;
         const bool has_next = grp_next * cpw < p.nchains;
         LaneCtx<E> cxn = cx;
@@ -1929,28 +2057,8 @@ KLARA_PRAGMA_UNROLL_E
         AccDraw ad = { 0.5, 0.0, false };
         const int acc_slot = (p.D + 1) >> 1;
         if (NEEDZ) lane_normals<E>(cx, p.seed, gchain, kl.t0, z, ad, acc_slot, (p.D + 1) >> 1);   // before the loaded state is touched
-        // SMMALA: the factor state of the group's current states, formed again from x and its gradient at every launch (the same
-        // operations as when the state was accepted, so the bits do not depend on the launch length); a state is only ever reached through a
-        // positive-definite metric (checked at the start state by k_init_smmala)
-        SmmalaRegs<E> sms;
-        if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA) smmala_state_at<T, E>(p, tg, cx, cur.x, cur.g, sms);
-        // RAM: the group's factors come from memory with the group and go back at the end of the launch, so a launch continues where the
-        // last one stopped whatever its length
-        RamRegs<SAMPLER == KLARA_SAMPLER_RAM ? E : 2> rms;
-        if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_load<E>(p, cx, rms);
-        // AM: the group's covariances and running means likewise
-        AmRegs<SAMPLER == KLARA_SAMPLER_AM ? E : 2> ams;
-        if constexpr (SAMPLER == KLARA_SAMPLER_AM) am_load<E>(p, cx, ams);
-        // AMWG: the group's log proposal scales and window counts likewise; the tuner's schedule follows from the transition index alone (count = t + 1:
-        // phase = count mod period, batch = count / period), so it is formed once per launch and stepped without a division
-        AmwgRegs<(SAMPLER == KLARA_SAMPLER_AMWG && E <= 32) ? E : 2> wms;
-        int wphase = 0; long long wbatch = 0;
-        KGLOBAL uint32_t* wmask_out = nullptr;
-        if constexpr (SAMPLER == KLARA_SAMPLER_AMWG) {
-            amwg_load<E>(p, cx, wms);
-            wphase = (int)((long long)kl.t0 % (long long)p.period); wbatch = (long long)kl.t0 / (long long)p.period;
-            if (!NOMON && p.amwg_mask != nullptr) wmask_out = p.amwg_mask + kl.t0 * (unsigned long long)p.nchains;
-        }
+        typename S::template State<E> st;          // the sampler's own per-chain state, taken up with the group
+        st.template take<T, !NOMON>(p, tg, cx, cur, kl.t0);
 
         TuneRegs tn;
         if (per_chain_tune) tn = { cur.step, cur.accepted, cur.proposed, cur.totproposed, 0, 0.0, 0.0 };
@@ -1962,39 +2070,15 @@ KLARA_PRAGMA_UNROLL_E
         int sphase = kl.save_phase0;
         long long scol = kl.save_col0;
         unsigned long long nacc = 0;
-        bool stuck = false, last_acc = false;
+        bool last_acc = false;
         Proposal<E> prop;
 
         for (int s = 0; s < nsteps; ++s) {
             const unsigned long long t = kl.t0 + (unsigned long long)s;
             if (KCNT) tune_count_proposal(p, tn);
-            bool acc;
-            if constexpr (SAMPLER == KLARA_SAMPLER_SMMALA)
-                acc = step_smmala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, sms, prop);
-            else if constexpr (SAMPLER == KLARA_SAMPLER_RAM) acc = step_ram<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, rms, cur.x, cur.lt, prop);
-            else if constexpr (SAMPLER == KLARA_SAMPLER_AM) acc = step_am<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, ams, cur.x, cur.lt, prop);
-            else if constexpr (SAMPLER == KLARA_SAMPLER_AMWG) {
-                if (do_sum && held > 0) fold_state();                      // fold first, whatever the sweep will do: the position does not depend on data
-                wphase = (wphase + 1 == p.period) ? 0 : wphase + 1;
-                const bool tuning = wphase == 0;                           // count % period == 0
-                wbatch += tuning ? 1 : 0;                                  // count / period
-                const double rs = 1.0 / __builtin_sqrt((double)wbatch);   // (W2: batch^-0.5)
-                const uint32_t moved = step_amwg<T, E>(p, tg, cx, gchain, t, tuning, rs < 0.01 ? rs : 0.01, wms, cur.x, cur.lt);
-                acc = moved != 0u;
-                if (wmask_out != nullptr && cx.chain_ok && cx.q == 0 && cx.rq == 0) wmask_out[(long long)s * p.nchains + cx.chain] = moved;
-            }
-            else if (SAMPLER == KLARA_SAMPLER_MH) acc = step_mh<T, E, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop);
-            else if (SAMPLER == KLARA_SAMPLER_MALA) acc = step_mala<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, cur.x, cur.g, cur.lt, prop);
-            else if (SAMPLER == KLARA_SAMPLER_HMC) {
-                double a_prob = 0.0;
-                acc = step_hmc<T, E, PLAIN, !(DIRECT || OUTER)>(p, tg, cx, gchain, t, z, ad, tn.step, da ? (cx.chain_ok ? da_nleaps(p, tn.step) : 1) : p.nleaps, a_prob,
-                                     cur.x, cur.g, cur.lt, prop);
-                if (da) da_update(p, tn, (long long)t + 1, a_prob);                   // iterate/HMC.jl:225-249
-            }
-            else {
-                if (do_sum && held > 0) fold_state();                      // the slice sampler always moves: fold first
-                acc = step_slice<T, E>(p, tg, cx, gchain, t, vp, cur.x, cur.lt, stuck);
-            }
+            if (S::INPLACE && do_sum && held > 0) fold_state();            // fold first, whatever the step will do: the position does not depend on data
+            const bool acc = S::template step<T, E, PLAIN, !(DIRECT || OUTER), !NOMON>(p, tg, cx, gchain, t, z, ad, tn.step, vp, cur, prop, st);
+            if constexpr (S::ADAPTS_STEP && !PLAIN) st.template tune<PLAIN>(p, tn, t);      // (a plain kernel has no tuner state to adapt)
             if (OUTER) {
                 if (do_sum && acc && held > 0) fold_state();               // leaving a state after `held` saved steps
                 if (acc) {                                                 // commit (MH.jl:98-100, MALA.jl:95-105, HMC.jl:166-176)
@@ -2005,7 +2089,7 @@ KLARA_PRAGMA_UNROLL_E
             }
             nacc += acc ? 1ull : 0ull;
             last_acc = acc;
-            if (KCNT && acc && SAMPLER != KLARA_SAMPLER_SLICE) tn.accepted += 1;   // the slice sampler never counts accepts
+            if (KCNT && acc && !S::ALWAYS_MOVES) tn.accepted += 1;
             if (accept_out != nullptr && cx.chain_ok && cx.q == 0 && cx.rq == 0)
                 accept_out[(long long)s * p.nchains + cx.chain] = acc ? 1 : 0;
             if (per_chain_tune && !da) tuning_block(p, tn);
@@ -2044,7 +2128,7 @@ KLARA_PRAGMA_UNROLL_E
                 if (NEEDG) store_win<E>(cx, group_window(p.GR, first_chain, here, p.D), p.D, prop.g);
                 cur.lt = prop.lt;
             }
-        } else if (nacc != 0 || SAMPLER == KLARA_SAMPLER_SLICE || nsteps > 1) {
+        } else if (nacc != 0 || S::ALWAYS_MOVES || nsteps > 1) {
             // (with one transition per launch a rejected proposal leaves x, g untouched: skip the write-back)
             store_win<E>(cx, group_window(p.X, first_chain, here, p.D), p.D, cur.x);
             if (NEEDG) store_win<E>(cx, group_window(p.GR, first_chain, here, p.D), p.D, cur.g);
@@ -2056,9 +2140,7 @@ KLARA_PRAGMA_UNROLL_E
             }
         }
         if (cx.chain_ok && cx.q == 0 && cx.rq == 0) {
-            if constexpr (SAMPLER == KLARA_SAMPLER_RAM) ram_store<E>(p, cx, rms);
-            if constexpr (SAMPLER == KLARA_SAMPLER_AM) am_store<E>(p, cx, ams);
-            if constexpr (SAMPLER == KLARA_SAMPLER_AMWG) amwg_store<E>(p, cx, wms);
+            st.put(p, cx);
             if (do_sum) p.held[cx.chain] = held;
             if (nacc != 0) { p.LT[cx.chain] = cur.lt; p.naccept[cx.chain] += nacc; }
             if (da) { p.tune_step[cx.chain] = tn.step; p.da_epsbar[cx.chain] = tn.epsbar; p.da_hbar[cx.chain] = tn.hbar; }
@@ -2070,7 +2152,6 @@ KLARA_PRAGMA_UNROLL_E
             } else if (KPOOLED && KCNT) {
                 atomicAdd((unsigned long long*)p.pooled_accepted, (unsigned long long)(tn.accepted - acc0));
             }
-            if (stuck) klara_raise(p.error_flag, KLARA_ERR_SLICE_STUCK);
         }
         if (!has_next) break;
         if (PREFETCH) { cur = nxt; cx = cxn; }

@@ -63,28 +63,16 @@ static inline int klara_autodiff_order(const char* src)
     return 0;
 }
 
-// group-layout transition kernels; target in {GAUSS_DIAG, LOGISTIC}; E in {2,4,8}; G = lanes per chain
-hipError_t klara_launch_mh(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                           hipStream_t st);
-hipError_t klara_launch_mala(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                           hipStream_t st);
-hipError_t klara_launch_hmc(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                           hipStream_t st);
-hipError_t klara_launch_slice(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                           hipStream_t st);
-// SMMALA on the logistic target, E in {2, 4, 8} (klara_smmala.hip), and its start-state kernel (log-target, gradient, metric check)
-hipError_t klara_launch_smmala(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                               hipStream_t st);
+// group-layout transition kernels: one specialisation per sampler, each defined in a translation unit of its own (klara_{mh,mala,hmc,slice,smmala,ram,am,amwg}.hip)
+// as launch_group<S> below; G = lanes per chain
+template <int S>
+hipError_t klara_launch_sampler(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st);
+#define KLARA_LAUNCH_SAMPLER(S) \
+    template <> hipError_t klara_launch_sampler<S>(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
+KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_MH); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_MALA); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_HMC); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_SLICE);
+KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_SMMALA); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_RAM); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_AM); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_AMWG);
+// SMMALA's start-state kernel on the logistic target (log-target, gradient, metric check); RAM, AM and AMWG start from k_init
 hipError_t klara_launch_smmala_init(const KParams& p, int E, dim3 grid, size_t lds, hipStream_t st);
-// RAM on the logistic target, E in {2, 4, 8}, one chain per lane (klara_ram.hip); its start-state kernel is k_init
-hipError_t klara_launch_ram(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                            hipStream_t st);
-// AM on the logistic target, E in {2, 4, 8}, one chain per lane (klara_am.hip); its start-state kernel is k_init
-hipError_t klara_launch_am(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                           hipStream_t st);
-// AMWG on the logistic target, E in {2, 4, 8, 16}, one chain per lane (klara_amwg.hip); its start-state kernel is k_init
-hipError_t klara_launch_amwg(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds,
-                             hipStream_t st);
 // dense (MFMA) kernels; NE in {8,16,25,32}
 // (Pfrag: the fragment-ordered precision matrix, followed — hasmu — by the 4 NE zero-padded entries of the mean)
 hipError_t klara_launch_dense(const KParams* p, const KLaunch& kl, int sampler, int tuner, bool plain, int NE, const double* Pfrag, bool hasmu,
@@ -238,13 +226,17 @@ static hipError_t launch_transitions(const KParams* p, const KLaunch& kl, int mo
     });
 }
 
-// every group-layout launcher of the four base samplers (klara_{mh,mala,hmc,slice}.hip): E = 2 and 4 for every target, 8 for all but the hierarchical
-// one, 16 for the logistic regression alone; G != 0 names the diagonal target's one chain per wavefront (2, 64) and per half (4, 32)
+// every group-layout launcher: E = 2 and 4 for every target, 8 for all but the hierarchical one, 16 for the logistic regression alone — of those, what the
+// sampler is built for (SamplerOf<S>::built_in; anything else is hipErrorInvalidValue); G != 0 names the diagonal target's one chain per wavefront
+// (2, 64) and per half (4, 32).  (The logistic and hierarchical targets have one instantiation per E: the plan gives them G = 1 — RAM, AM and AMWG, one chain
+// per lane, rely on that — so G is not looked at there.)
 template <int S>
 static hipError_t launch_group(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
 {
     const auto go = [&](auto t, auto e, auto g) {
-        return launch_transitions<S, decltype(t)::value, decltype(e)::value, decltype(g)::value>(p, kl, mode, grid, lds, st);
+        if constexpr (SamplerOf<S>::built_in(decltype(t)::value, decltype(e)::value))
+            return launch_transitions<S, decltype(t)::value, decltype(e)::value, decltype(g)::value>(p, kl, mode, grid, lds, st);
+        else return hipErrorInvalidValue;
     };
     using G0 = KInt<0>;
     if (target == KLARA_TARGET_GAUSS_DIAG) {

@@ -701,25 +701,45 @@ extern "C" klara_status klara_get_dual_averaging(klara_handle* h, double* epsbar
     return KLARA_OK;
 }
 
+// The samplers' per-chain adaptive arrays are planes — plane k holds entry k of every chain, N values — and the API's arrays are chain-major rows of `row`
+// entries.  read_planes gathers out[c * row + i] = plane map(i) of chain c (map(i) < 0: zero), write_planes scatters the entries with map(i) >= 0 back.
+template <class T, class Map>
+static klara_status read_planes(const T* dev, size_t nplanes, size_t N, size_t row, Map map, T* out)
+{
+    std::vector<T> planes(nplanes * N);
+    HIPCHK(hipMemcpy(planes.data(), dev, planes.size() * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < N; ++c)
+        for (size_t i = 0; i < row; ++i) { const long long k = map(i); out[c * row + i] = k < 0 ? T(0) : planes[(size_t)k * N + c]; }
+    return KLARA_OK;
+}
+template <class T, class Map>
+static klara_status write_planes(T* dev, size_t nplanes, size_t N, size_t row, Map map, const T* in)
+{
+    std::vector<T> planes(nplanes * N);
+    for (size_t c = 0; c < N; ++c)
+        for (size_t i = 0; i < row; ++i) { const long long k = map(i); if (k >= 0) planes[(size_t)k * N + c] = in[c * row + i]; }
+    HIPCHK(hipMemcpy(dev, planes.data(), planes.size() * sizeof(T), hipMemcpyHostToDevice));
+    return KLARA_OK;
+}
+static long long plane_lower(size_t D, size_t ij) { const int i = (int)(ij / D), j = (int)(ij % D); return j <= i ? (long long)ktri(j, i, (int)D) : -1ll; }   // entry (i, j) of a row-major D x D lower triangle
+static const auto plane_same = [](size_t i) { return (long long)i; };                      // a vector per chain: entry i is plane i
+static klara_status read_counter(const unsigned long long* dev, int64_t* out)
+{
+    unsigned long long k = 0;
+    HIPCHK(hipMemcpy(&k, dev, sizeof(k), hipMemcpyDeviceToHost));
+    *out = (int64_t)k;
+    return KLARA_OK;
+}
+
 extern "C" klara_status klara_get_ram_factor(klara_handle* h, double* S, int64_t* skipped)
 {
     if (!h || h->d.sampler != KLARA_SAMPLER_RAM) return KLARA_ERR_INVALID_ARG;
     if (!h->have_state) return KLARA_ERR_STATE;
     HIPCHK(hipSetDevice(h->d.device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims, NP = D * (D + 1) / 2;
-    if (S) {
-        std::vector<double> planes(NP * N);
-        HIPCHK(hipMemcpy(planes.data(), h->ram_S, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t c = 0; c < N; ++c)
-            for (size_t i = 0; i < D; ++i)
-                for (size_t j = 0; j < D; ++j) S[(c * D + i) * D + j] = j <= i ? planes[(size_t)ktri((int)j, (int)i, (int)D) * N + c] : 0.0;
-    }
-    if (skipped) {
-        unsigned long long k = 0;
-        HIPCHK(hipMemcpy(&k, h->ram_skipped, sizeof(k), hipMemcpyDeviceToHost));
-        *skipped = (int64_t)k;
-    }
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
+    if (S) KCHK(read_planes(h->ram_S, D * (D + 1) / 2, N, D * D, [D](size_t ij) { return plane_lower(D, ij); }, S));
+    if (skipped) KCHK(read_counter(h->ram_skipped, skipped));
     return KLARA_OK;
 }
 
@@ -727,17 +747,13 @@ extern "C" klara_status klara_set_ram_factor(klara_handle* h, const double* S)
 {
     if (!h || !S || h->d.sampler != KLARA_SAMPLER_RAM) return KLARA_ERR_INVALID_ARG;
     if (!h->have_state) return KLARA_ERR_STATE;
-    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims, NP = D * (D + 1) / 2;
-    std::vector<double> planes(NP * N);
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
     for (size_t c = 0; c < N; ++c)
-        for (size_t i = 0; i < D; ++i) {
+        for (size_t i = 0; i < D; ++i)
             if (!(S[(c * D + i) * D + i] > 0.0) || !std::isfinite(S[(c * D + i) * D + i])) return KLARA_ERR_INVALID_ARG;
-            for (size_t j = 0; j <= i; ++j) planes[(size_t)ktri((int)j, (int)i, (int)D) * N + c] = S[(c * D + i) * D + j];
-        }
     HIPCHK(hipSetDevice(h->d.device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(h->ram_S, planes.data(), planes.size() * sizeof(double), hipMemcpyHostToDevice));
-    return KLARA_OK;
+    return write_planes(h->ram_S, D * (D + 1) / 2, N, D * D, [D](size_t ij) { return plane_lower(D, ij); }, S);
 }
 
 extern "C" klara_status klara_get_am_state(klara_handle* h, double* Cout, double* lastmean, double* secondlastmean, int64_t* fallbacks)
@@ -746,38 +762,12 @@ extern "C" klara_status klara_get_am_state(klara_handle* h, double* Cout, double
     if (!h->have_state) return KLARA_ERR_STATE;
     HIPCHK(hipSetDevice(h->d.device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims, NP = D * (D + 1) / 2;
-    if (Cout) {
-        std::vector<double> planes(NP * N);
-        HIPCHK(hipMemcpy(planes.data(), h->am_C, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t c = 0; c < N; ++c)
-            for (size_t i = 0; i < D; ++i)
-                for (size_t j = 0; j < D; ++j) Cout[(c * D + i) * D + j] = planes[(size_t)ktri((int)(i < j ? i : j), (int)(i < j ? j : i), (int)D) * N + c];
-    }
-    if (lastmean || secondlastmean) {
-        std::vector<double> planes(2 * D * N);
-        HIPCHK(hipMemcpy(planes.data(), h->am_mean, planes.size() * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t c = 0; c < N; ++c)
-            for (size_t i = 0; i < D; ++i) {
-                if (lastmean) lastmean[c * D + i] = planes[i * N + c];
-                if (secondlastmean) secondlastmean[c * D + i] = planes[(D + i) * N + c];
-            }
-    }
-    if (fallbacks) {
-        unsigned long long k = 0;
-        HIPCHK(hipMemcpy(&k, h->am_fallbacks, sizeof(k), hipMemcpyDeviceToHost));
-        *fallbacks = (int64_t)k;
-    }
-    return KLARA_OK;
-}
-
-// the D planes of an AMWG array as nchains x D rows, and back
-template <class T>
-static klara_status amwg_read_planes(const T* dev, size_t N, size_t D, T* out)
-{
-    std::vector<T> planes(D * N);
-    HIPCHK(hipMemcpy(planes.data(), dev, planes.size() * sizeof(T), hipMemcpyDeviceToHost));
-    for (size_t c = 0; c < N; ++c) for (size_t i = 0; i < D; ++i) out[c * D + i] = planes[i * N + c];
+    const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
+    const auto symmetric = [D](size_t ij) { const int i = (int)(ij / D), j = (int)(ij % D); return (long long)ktri(i < j ? i : j, i < j ? j : i, (int)D); };
+    if (Cout) KCHK(read_planes(h->am_C, D * (D + 1) / 2, N, D * D, symmetric, Cout));
+    if (lastmean) KCHK(read_planes(h->am_mean, D, N, D, plane_same, lastmean));
+    if (secondlastmean) KCHK(read_planes(h->am_mean + D * N, D, N, D, plane_same, secondlastmean));
+    if (fallbacks) KCHK(read_counter(h->am_fallbacks, fallbacks));
     return KLARA_OK;
 }
 
@@ -788,12 +778,12 @@ extern "C" klara_status klara_get_amwg_state(klara_handle* h, double* logsigma, 
     HIPCHK(hipSetDevice(h->d.device));
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
-    if (logsigma) KCHK(amwg_read_planes(h->amwg_logsig, N, D, logsigma));
-    if (accepted) KCHK(amwg_read_planes((const int32_t*)h->amwg_acc, N, D, accepted));
+    if (logsigma) KCHK(read_planes(h->amwg_logsig, D, N, D, plane_same, logsigma));
+    if (accepted) KCHK(read_planes((const int32_t*)h->amwg_acc, D, N, D, plane_same, accepted));
     if (naccept_coord) {                                         // the closed windows' counts + the open window's
         std::vector<int32_t> open(N * D);
-        KCHK(amwg_read_planes((const uint64_t*)h->amwg_nacc, N, D, naccept_coord));
-        KCHK(amwg_read_planes((const int32_t*)h->amwg_acc, N, D, open.data()));
+        KCHK(read_planes((const uint64_t*)h->amwg_nacc, D, N, D, plane_same, naccept_coord));
+        KCHK(read_planes((const int32_t*)h->amwg_acc, D, N, D, plane_same, open.data()));
         for (size_t k = 0; k < N * D; ++k) naccept_coord[k] += (uint64_t)open[k];
     }
     return KLARA_OK;
@@ -804,16 +794,10 @@ extern "C" klara_status klara_set_amwg_logsigma(klara_handle* h, const double* l
     if (!h || h->d.sampler != KLARA_SAMPLER_AMWG || !logsigma) return KLARA_ERR_INVALID_ARG;
     if (!h->have_state) return KLARA_ERR_STATE;
     const size_t N = (size_t)h->d.nchains, D = (size_t)h->d.ndims;
-    std::vector<double> planes(D * N);
-    for (size_t c = 0; c < N; ++c)
-        for (size_t i = 0; i < D; ++i) {
-            if (!std::isfinite(logsigma[c * D + i])) return KLARA_ERR_INVALID_ARG;
-            planes[i * N + c] = logsigma[c * D + i];
-        }
+    for (size_t k = 0; k < N * D; ++k) if (!std::isfinite(logsigma[k])) return KLARA_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(h->d.device));
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(h->amwg_logsig, planes.data(), planes.size() * sizeof(double), hipMemcpyHostToDevice));
-    return KLARA_OK;
+    return write_planes(h->amwg_logsig, D, N, D, plane_same, logsigma);
 }
 
 extern "C" klara_status klara_get_amwg_accept_mask(klara_handle* h, uint32_t* mask, int64_t capacity_steps, int64_t* nsteps_out)

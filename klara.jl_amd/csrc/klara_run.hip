@@ -28,28 +28,20 @@ __global__ void k_fill_tune(double* step, long long* acc, long long* prop, long 
     if (i < n) { step[i] = step0; acc[i] = 0; prop[i] = 0; tot[i] = period; }
 }
 
-// RAM: every chain's factor restarts from S0 (RAM.jl:155-162, 201-211): plane k of the factors <- entry k of the packed triangle
-__global__ void k_fill_ram(double* S, const double* tri, long long n, int nplanes)
+// The samplers' per-chain adaptive arrays are planes (plane k holds entry k of every chain): plane k of every chain <- entry k of a short vector.  RAM's
+// factors restart from S0 (RAM.jl:155-162, 201-211), AM's covariances from C0 (AM.jl:238-246), AMWG's log proposal scales from logsigma0 (AMWG.jl:165-170)
+__global__ void k_fill_planes(double* planes, const double* entries, long long n, int nplanes)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) for (int k = 0; k < nplanes; ++k) S[(long long)k * n + i] = tri[k];
+    if (i < n) for (int k = 0; k < nplanes; ++k) planes[(long long)k * n + i] = entries[k];
 }
 
-// AM: every chain's covariance restarts from C0 and both running means from the chain's start value (AM.jl:238-246, 292-304)
-__global__ void k_fill_am(double* Cm, const double* tri, double* mean, const double* X, long long n, int D)
+// AM: both running means restart from the chain's start value (AM.jl:292-304)
+__global__ void k_fill_am_means(double* mean, const double* X, long long n, int D)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    for (int k = 0; k < D * (D + 1) / 2; ++k) Cm[(long long)k * n + i] = tri[k];
     for (int k = 0; k < D; ++k) { const double v = X[i * D + k]; mean[(long long)k * n + i] = v; mean[(long long)(D + k) * n + i] = v; }
-}
-
-// AMWG: every chain's log proposal scales restart from logsigma0, its counts from zero (AMWG.jl:165-170, 205-214)
-__global__ void k_fill_amwg(double* logsig, const double* logsig0, int* acc, unsigned long long* nacc, long long n, int D)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    for (int k = 0; k < D; ++k) { logsig[(long long)k * n + i] = logsig0[k]; acc[(long long)k * n + i] = 0; nacc[(long long)k * n + i] = 0ull; }
 }
 
 __global__ void k_fill2(double* a, double* b, long long n, double va, double vb)
@@ -162,19 +154,24 @@ static klara_status init_common(klara_handle* h)
                            d.da_eps0bar, d.da_h0bar);
         HIPCHK(hipGetLastError());
     }
+    const dim3 fill_grid((unsigned)((N + 255) / 256));
     if (h->ram_S) {
-        hipLaunchKernelGGL(k_fill_ram, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->ram_S, h->ram_S0, (long long)N, (int)(D * (D + 1) / 2));
+        hipLaunchKernelGGL(k_fill_planes, fill_grid, dim3(256), 0, st, h->ram_S, h->ram_S0, (long long)N, (int)(D * (D + 1) / 2));
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(h->ram_skipped, 0, sizeof(unsigned long long), st));
     }
     if (h->am_C) {
-        hipLaunchKernelGGL(k_fill_am, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->am_C, h->am_C0, h->am_mean, h->X, (long long)N, (int)D);
+        hipLaunchKernelGGL(k_fill_planes, fill_grid, dim3(256), 0, st, h->am_C, h->am_C0, (long long)N, (int)(D * (D + 1) / 2));
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_fill_am_means, fill_grid, dim3(256), 0, st, h->am_mean, h->X, (long long)N, (int)D);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemsetAsync(h->am_fallbacks, 0, sizeof(unsigned long long), st));
     }
-    if (h->amwg_logsig) {
-        hipLaunchKernelGGL(k_fill_amwg, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, h->amwg_logsig, h->amwg_logsig0, h->amwg_acc, h->amwg_nacc, (long long)N, (int)D);
+    if (h->amwg_logsig) {                // (the counts restart from zero: AMWG.jl:205-214)
+        hipLaunchKernelGGL(k_fill_planes, fill_grid, dim3(256), 0, st, h->amwg_logsig, h->amwg_logsig0, (long long)N, (int)D);
         HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(h->amwg_acc, 0, N * D * sizeof(int), st));
+        HIPCHK(hipMemsetAsync(h->amwg_nacc, 0, N * D * sizeof(unsigned long long), st));
     }
     const int needgrad = sampler_needs_gradient(d.sampler);
     KParams p = make_params(h);
@@ -455,16 +452,10 @@ hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
         return klara_launch_hiert(p, kl, d.sampler, P.E / 2, d.hier_ntimes, mon, !P.plain || da, da, grid, h->stream);
     }
     if (d.target == KLARA_TARGET_CUSTOM) return klara_jit_launch(h->jit, mode, p, kl, grid_steps, P.lds, h->stream, 64 * P.custom_wpb);
-    switch (d.sampler) {
-    case KLARA_SAMPLER_MH: return klara_launch_mh(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    case KLARA_SAMPLER_MALA: return klara_launch_mala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    case KLARA_SAMPLER_HMC: return klara_launch_hmc(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    case KLARA_SAMPLER_SMMALA: return klara_launch_smmala(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    case KLARA_SAMPLER_RAM: return klara_launch_ram(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    case KLARA_SAMPLER_AM: return klara_launch_am(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    case KLARA_SAMPLER_AMWG: return klara_launch_amwg(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    default: return klara_launch_slice(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
-    }
+    return klara_pick<KLARA_SAMPLER_MH, KLARA_SAMPLER_MALA, KLARA_SAMPLER_HMC, KLARA_SAMPLER_SLICE, KLARA_SAMPLER_SMMALA, KLARA_SAMPLER_RAM, KLARA_SAMPLER_AM,
+                      KLARA_SAMPLER_AMWG>(d.sampler, [&](auto s) {
+        return klara_launch_sampler<decltype(s)::value>(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
+    });
 }
 
 // ---- launch planning: pure host logic (no device), shared by klara_run_async and klara_selftest_plan ------------------------

@@ -43,6 +43,7 @@ CLOSURE_DIMS = (1, 5, 16, 17, 32)        # E = 2, 8, 16, 32, 32; 17 is odd and t
 LOGIT = ["swiss_d4", "logit_d3", "logit_d8", "logit_d11"]
 CLOSURES = [f"{form}_d{d}" for d in CLOSURE_DIMS for form in ("quad", "likprior")]
 ALL = LOGIT + CLOSURES
+WALK = "quad_d5_n300"                    # quad_d5 on 300 chains: five groups of 64 (the last one short) for the four wavefronts of one workgroup
 
 
 def amwg(targetrate=0.44, period=5):
@@ -74,10 +75,10 @@ def make(name):
         x0 = 0.3 * np.random.default_rng(d).standard_normal((n, d))
         ls0 = np.log(np.linspace(0.2, 0.9, d))
         c = dict(target=K.LogisticTarget(X, y, 25.0), nchains=n, nsteps=40, burnin=4, thinning=3, amwg_logsigma0=ls0, x0=x0, **amwg())
-    elif name in CLOSURES:
-        form, d = name.split("_d")
+    elif name in CLOSURES or name == WALK:
+        form, d = name.split("_n")[0].split("_d")
         d = int(d)
-        n = 1 if (form, d) == ("quad", 1) else 200 if d <= 5 else 70
+        n = 300 if name == WALK else 1 if (form, d) == ("quad", 1) else 200 if d <= 5 else 70
         rng = np.random.default_rng(100 + d)
         if form == "quad":
             t = quad_target(0.5, conditioned_precision(d, 50.0, seed=d))

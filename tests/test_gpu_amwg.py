@@ -172,14 +172,17 @@ def test_chain_offset_sharding(gpu_required, name):
     assert np.array_equal(np.concatenate([p[6] for p in parts]), whole.sum) and np.array_equal(np.concatenate([p[7] for p in parts]), whole.sumsq)
 
 
-@pytest.mark.parametrize("name", ["swiss_d4", "quad_d5"])
+@pytest.mark.parametrize("name", ["swiss_d4", pytest.param(WC.WALK, id="quad_d5")])
 def test_several_chain_groups_per_wavefront(gpu_required, monkeypatch, name):
-    """KLARA_GROUPS_PER_WAVE=2: a persistent wavefront walks over two chain groups (13 and 4 groups of 200 chains), in fused and in one-transition launches"""
+    """KLARA_GROUPS_PER_WAVE=2: a persistent wavefront walks over two chain groups (13 groups of 16 chains on 8 wavefronts, 5 groups of 64 on 4), in fused
+    and in one-transition launches"""
     monkeypatch.setenv("KLARA_GROUPS_PER_WAVE", "2")
     case = WC.make(name)
     job = WC.reference(name)
     for spl in (0, 1):
         eng = _engine(case, steps_per_launch=spl)
+        groups = -(-case["nchains"] // (64 // eng.layout()[1]))
+        assert groups > 4 * -(-(-(-groups // 2)) // 4), "no wavefront takes a second group"      # (workgroups of four wavefronts)
         eng.run(case["nsteps"])
         _assert_same(eng, job)
         eng.close()
