@@ -820,7 +820,9 @@ __device__ __forceinline__ void da_update(const KParams& p, TuneRegs& tn, long l
 {
     if (count <= p.da_nadapt) {
         const double hweight = 1.0 / (double)(count + p.da_t0);
-        tn.hbar = (1.0 - hweight) * tn.hbar + hweight * (p.targetrate - a);
+        // a NaN acceptance probability (a proposal that is not finite) counts as 0 for the tuner: targetrate - 0
+        const double miss = p.targetrate - a;
+        tn.hbar = (1.0 - hweight) * tn.hbar + hweight * (miss == miss ? miss : p.targetrate);
         tn.step = kd_exp(p.da_mu - __builtin_sqrt((double)count) * tn.hbar / p.da_gamma);
         const double eweight = kd_exp(-p.da_kappa * kd_log((double)count));        // count^(-kappa)
         tn.epsbar = kd_exp((1.0 - eweight) * kd_log(tn.epsbar) + eweight * kd_log(tn.step));

@@ -1318,7 +1318,10 @@ int ko_run(const klara_desc* d, const ko_layout* L, double* X, double* G, double
                     const int64_t count = t + 1;                /* job.sstate.count, incremented at :125-127 */
                     if (count <= d->da_nadapt) {                /* tune!(tune, tuner, count, a) DualAveragingMCTuner.jl:95-101 */
                         const double hweight = 1.0 / (double)(count + d->da_t0);
-                        da_hbar[n] = (1.0 - hweight) * da_hbar[n] + hweight * (d->targetrate - a_prob);
+                        /* DEVIATION: a NaN a (a proposal that is not finite; the transition rejected it) counts as 0 here.  The
+                         * reference, DualAveragingMCTuner.jl:95-101, would carry it into h_bar and leave the chain with a NaN step for good. */
+                        const double a_tune = a_prob == a_prob ? a_prob : 0.0;
+                        da_hbar[n] = (1.0 - hweight) * da_hbar[n] + hweight * (d->targetrate - a_tune);
                         tn.step = kd_exp(da_mu - sqrt((double)count) * da_hbar[n] / d->da_gamma);
                         const double eweight = kd_exp(-d->da_kappa * kd_log((double)count));   /* count^(-kappa) */
                         da_epsbar[n] = kd_exp((1.0 - eweight) * kd_log(da_epsbar[n]) + eweight * kd_log(tn.step));

@@ -118,6 +118,14 @@ def pair_quartic_target(c, k, d):
     return lt, grad
 
 
+def _exp(v):
+    """math.exp, with +inf where it would raise (a trajectory that has left the range of doubles; tests/nonfinite_cases.py)"""
+    try:
+        return math.exp(v)
+    except OverflowError:
+        return math.inf
+
+
 def hier_normal_target(Y, xc, prior_prec, ga, gb):
     """The builder-defined BUGS "Rats" target of BASELINE cfg 5 (include/klara_hip.h KLARA_TARGET_HIER_NORMAL): Y_ij ~ N(a_i + b_i xc_j, s_c^2),
     a_i ~ N(a_c, s_a^2), b_i ~ N(b_c, s_b^2), a_c, b_c ~ N(0, 1 / prior_prec), 1 / s_k^2 ~ Gamma(ga, gb), in
@@ -131,14 +139,14 @@ def hier_normal_target(Y, xc, prior_prec, ga, gb):
     def lt(v):
         a, b, ac, bc, sc, sa, sb = split(v)
         r = Y - a[:, None] - b[:, None] * xc[None, :]
-        wc, wa, wb = math.exp(-2 * sc), math.exp(-2 * sa), math.exp(-2 * sb)
+        wc, wa, wb = _exp(-2 * sc), _exp(-2 * sa), _exp(-2 * sb)
         return float(-R * T * sc - 0.5 * wc * np.sum(r * r) - R * sa - 0.5 * wa * np.sum((a - ac) ** 2) - R * sb - 0.5 * wb * np.sum((b - bc) ** 2)
-                     - 0.5 * prior_prec * (ac * ac + bc * bc) + sum(-2 * ga * s_ - gb * math.exp(-2 * s_) for s_ in (sc, sa, sb)))
+                     - 0.5 * prior_prec * (ac * ac + bc * bc) + sum(-2 * ga * s_ - gb * _exp(-2 * s_) for s_ in (sc, sa, sb)))
 
     def grad(v):
         a, b, ac, bc, sc, sa, sb = split(v)
         r = Y - a[:, None] - b[:, None] * xc[None, :]
-        wc, wa, wb = math.exp(-2 * sc), math.exp(-2 * sa), math.exp(-2 * sb)
+        wc, wa, wb = _exp(-2 * sc), _exp(-2 * sa), _exp(-2 * sb)
         g = np.empty_like(v)
         g[0:2 * R:2] = wc * r.sum(axis=1) - wa * (a - ac)
         g[1:2 * R:2] = wc * (r * xc[None, :]).sum(axis=1) - wb * (b - bc)
@@ -181,6 +189,19 @@ class Chain:
             self.lam, self.mu_da, self.epsbar, self.hbar = nleaps * leapstep, math.log(10.0 * leapstep), eps0bar, h0bar
         self.t = 0
         self.accepts, self.saved = [], []
+        # the counting hook (tests/nonfinite_cases.py): per transition, whether lt', any gradient element, the ratio or a was not finite, and the largest
+        # magnitude that decided it.  It observes only: nothing below reads what it records.
+        self.seen = []
+        self.max_nleaps = 0                                       # HMC: the longest trajectory so far
+
+    def _observe(self, ltp, gp, ratio, a, sums):
+        """one entry of self.seen: dict(lt, grad, ratio, a = the value was not finite (None: the sampler forms no such value), nan = one of them was a NaN,
+        edge = the largest of |lt'| and the sums that enter the decision, for the borderline rule of tests/test_nonfinite_host.py)"""
+        vals = [ltp] + ([] if ratio is None else [ratio]) + ([] if a is None else [a])
+        gbad = gp is not None and not bool(np.all(np.isfinite(gp)))
+        self.seen.append(dict(lt=not math.isfinite(ltp), grad=gbad, ratio=None if ratio is None else not math.isfinite(ratio), a=None if a is None else not math.isfinite(a),
+                              nan=any(math.isnan(v) for v in vals) or (gp is not None and bool(np.any(np.isnan(gp)))),
+                              edge=max([abs(ltp)] + [abs(v) for v in sums if not math.isnan(v)]) if not math.isnan(ltp) else float("nan")))
 
     def _cnt(self):
         if self.sampler in ("mh", "slice"):
@@ -192,6 +213,7 @@ class Chain:
         ltp = self.ltf(xp)                                                           # :81
         ratio = ltp - self.lt                                                        # :83
         acc = ratio > 0 or ratio > math.log(accept_uniform(self.seed, self.cid, t, self.D))     # :97
+        self._observe(ltp, None, ratio, None, ())
         if acc:
             self.x, self.lt = xp, ltp
         return acc
@@ -202,10 +224,13 @@ class Chain:
         xp = mu + math.sqrt(h) * normals(self.seed, self.cid, t, self.D)             # :84
         ltp, gp = self.ltf(xp), self.gradf(xp)                                       # :86
         ratio = ltp - self.lt                                                        # :88
-        ratio += float(np.sum(0.5 * ((mu - xp) ** 2 / h)))                           # :90
+        s1 = float(np.sum(0.5 * ((mu - xp) ** 2 / h)))
+        ratio += s1                                                                  # :90
         mup = xp + 0.5 * h * gp                                                      # :91
-        ratio -= float(np.sum(0.5 * ((mup - self.x) ** 2 / h)))                      # :92
+        s2 = float(np.sum(0.5 * ((mup - self.x) ** 2 / h)))
+        ratio -= s2                                                                  # :92
         acc = ratio > 0 or ratio > math.log(accept_uniform(self.seed, self.cid, t, self.D))     # :94
+        self._observe(ltp, gp, ratio, None, (s1, s2))
         if acc:
             self.x, self.g, self.lt = xp, gp, ltp
         return acc
@@ -227,6 +252,8 @@ class Chain:
         a = 1.0 if d >= 0 else math.exp(d)                                           # :163  min(1, exp(ratio))
         acc = accept_uniform(self.seed, self.cid, t, self.D) < a                     # :165  rand() always drawn
         self.a = a
+        self.max_nleaps = max(self.max_nleaps, nleaps)
+        self._observe(ltp, gp, d, a, (0.5 * float(p @ p), h1))
         if acc:
             self.x, self.g, self.lt = xp, gp, ltp
         return acc
@@ -278,7 +305,8 @@ class Chain:
                 count = t + 1                                                        # job.sstate.count, incremented at :125-127
                 if count <= self.nadapt:                                             # tune!: DualAveragingMCTuner.jl:95-101
                     hw = 1.0 / (count + self.t0)
-                    self.hbar = (1.0 - hw) * self.hbar + hw * (self.targetrate - self.a)
+                    a = 0.0 if math.isnan(self.a) else self.a                        # (a NaN a counts as 0 for the tuner: DESIGN.md section 2, D1)
+                    self.hbar = (1.0 - hw) * self.hbar + hw * (self.targetrate - a)
                     self.step = math.exp(self.mu_da - math.sqrt(count) * self.hbar / self.gamma)
                     ew = count ** (-self.kappa)
                     self.epsbar = math.exp((1.0 - ew) * math.log(self.epsbar) + ew * math.log(self.step))
