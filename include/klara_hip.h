@@ -67,7 +67,7 @@ typedef enum klara_status {
     KLARA_ERR_COMPILE = 8          /* CUSTOM target: the user's source did not compile (klara_compile_log) */
 } klara_status;
 
-/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM,AM,AMWG}.jl */
+/* src/samplers/{MH,MALA,HMC,SliceSampler,SMMALA,RAM,AM,AMWG}.jl (MH twice: its vector and its matrix constructor) */
 typedef enum klara_sampler {
     KLARA_SAMPLER_MH = 0,      /* MH(sigma): symmetric normal random walk, MH.jl:63-66            */
     KLARA_SAMPLER_MALA = 1,    /* MALA(driftstep), MALA.jl:61-70                                   */
@@ -122,7 +122,20 @@ typedef enum klara_sampler {
      * hierarchical families: KLARA_ERR_UNSUPPORTED.  The accept count and the accept mask record whether at least one coordinate moved;
      * klara_get_amwg_state / klara_get_amwg_accept_mask have the per-coordinate view.  klara_set_state and klara_reset put
      * logsigma = klara_desc.amwg_logsigma0, clear the counts and restart the schedule.  DESIGN.md section 2, W1-W6. */
-    KLARA_SAMPLER_AMWG = 10
+    KLARA_SAMPLER_AMWG = 10,
+    /* (11 is reserved like 5, 7 and 9) */
+    /* MH(Σ::Matrix), samplers/MH.jl:63-66 (x -> MvNormal(x, Σ)) with iterate/MH.jl:72-124, symmetric normalised branch: random-walk Metropolis with a full
+     * proposal covariance, one for the whole job.  With L the lower Cholesky factor of Σ (klara_desc.mh_factor) and z the D normals MH draws for the chain
+     * and transition, the proposal is x' = x + L z, row i summed as w_i = L_i0 z_0, then w_i = w_i + L_ik z_k for k = 1 .. i ascending, each a separate
+     * multiplication and addition; everything else is KLARA_SAMPLER_MH — the evaluation, ratio = lt' - lt, the accept test with MH's accept uniform from
+     * its slot, the monitors; the stream does not move.  The proposal densities of a symmetric proposal cancel and are not formed.  The factor lives on the
+     * device once per handle (klara_get_mh_factor / klara_set_mh_factor), not per chain.  Only KLARA_TUNER_VANILLA per chain (it counts when verbose, as
+     * for MH; any other tuner and the pooled mode: KLARA_ERR_UNSUPPORTED).  KLARA_SAMPLER_AMWG's scope: KLARA_TARGET_LOGISTIC up to 16 parameters whose
+     * rows fit the LDS (layout kinds 0 and 2, never the matrix cores) and KLARA_TARGET_CUSTOM whole-vector closures (plain, likelihood + prior, autodiff
+     * sources) with D <= 32 at one chain per lane; pair closures, staged closures, the Gaussian and hierarchical families: KLARA_ERR_UNSUPPORTED.
+     * klara_desc.mh_sigma is not read.  klara_reset puts klara_desc.mh_factor back; klara_set_state leaves the factor alone (it is the job's, not a
+     * chain's).  DESIGN.md section 2, C1-C3. */
+    KLARA_SAMPLER_MH_COV = 12
 } klara_sampler;
 
 /* Target families evaluated on device (stand-ins for the user closures of
@@ -258,6 +271,9 @@ typedef struct klara_desc {
                                     proposal's standard deviation is sqrt(exp(logsigma)), iterate/AMWG.jl:96), all finite.  Required for
                                     KLARA_SAMPLER_AMWG; NULL for every other sampler (else KLARA_ERR_INVALID_ARG).  Copied at create.  (Beside the
                                     other samplers' vectors: the fields behind steps_per_launch and in front of stream are the derived quantities') */
+    const double* mh_factor;     /* MH(Σ): the lower Cholesky factor L of the proposal covariance, Σ = L L', D x D row-major; only the lower triangle is
+                                    read, every read entry finite and the diagonal positive (else KLARA_ERR_INVALID_ARG).  Required for
+                                    KLARA_SAMPLER_MH_COV; NULL for every other sampler (else KLARA_ERR_INVALID_ARG).  Copied at create. */
 
     /* tuner (AcceptanceRateMCTuner.jl:38-44; VanillaMCTuner: only period/verbose are used) */
     double   targetrate;         /* in (0,1)                                                         */
@@ -671,6 +687,14 @@ klara_status klara_set_amwg_logsigma(klara_handle* h, const double* logsigma);
 /* KLARA_SAMPLER_AMWG with KLARA_MON_ACCEPT: one uint32 per transition and chain, step-major like klara_get_accept_mask, bit i set where coordinate i
  * moved (D <= 32).  *nsteps_out receives the number of recorded steps.  Without the monitor: KLARA_ERR_STATE. */
 klara_status klara_get_amwg_accept_mask(klara_handle* h, uint32_t* mask, int64_t capacity_steps, int64_t* nsteps_out);
+/* KLARA_SAMPLER_MH_COV: the job's current proposal factor L, D x D row-major, lower triangular with zeros above the diagonal — what the descriptor or the
+ * last klara_set_mh_factor gave.  KLARA_ERR_INVALID_ARG on a handle of another sampler. */
+klara_status klara_get_mh_factor(klara_handle* h, double* L);
+/* KLARA_SAMPLER_MH_COV: a new proposal factor (D x D row-major, the lower triangle is read: every entry finite, the diagonal positive, else
+ * KLARA_ERR_INVALID_ARG), in effect from the next transition; the states, the transition count and the monitors are kept.  Like the other setters it
+ * waits for the transitions a klara_run_async has queued before it writes.  Changing the proposal from the chains' own past is an adaptation step: the
+ * samples that are kept belong behind it.  klara_reset puts klara_desc.mh_factor back. */
+klara_status klara_set_mh_factor(klara_handle* h, const double* L);
 
 /* Measurement: duration (ms, HIP events on the launch stream) and launch count of the transition
  * kernels enqueued by the last klara_run / klara_run_async (after synchronisation). */

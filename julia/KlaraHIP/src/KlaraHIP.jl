@@ -37,7 +37,7 @@ import Distributions: Continuous, Multivariate
 import Base: run, reset, show
 export HIPMCJob, HIPParameter, HIPTarget, GaussDiagTarget, GaussDenseTarget, LogisticTarget, HierNormalTarget, CustomTarget,
        chainvalue, chainmeans, chainacceptance, chainmcvar_bm, chainlzv, chainqzv, streamkey, launchmodes, shaderclock, check_custom_target,
-       check_custom_target_softabs, SoftAbs, ramfactor, amstate, amwgstate,
+       check_custom_target_softabs, SoftAbs, ramfactor, amstate, amwgstate, mhfactor, setmhfactor!,
        HIPComm, comm_unique_id, comm_info, gather_summaries, gather_moments, pooledmoments, gather_covariance, pooledcovariance, rhat, gather_rhat, pooledess, gather_ess,
        pooledhistogram, pooledquantiles, gather_histogram, Derived, derivedsums, derivedmoments, derivedrhat, derivedhistogram, derivedquantiles,
        gather_derived_moments, gather_derived_rhat, gather_derived_histogram, check_derived, KlaraDesc, klara_desc
@@ -60,6 +60,7 @@ const SAMPLER_SMMALA = Int32(4)      # SMMALA(driftstep) with transform = nothin
 const SAMPLER_RAM = Int32(6)         # RAM(S0; targetrate, γ): the logistic target or a CustomTarget's whole-vector closure, D <= 8 (5 is reserved)
 const SAMPLER_AM = Int32(8)          # AM(C0; corescale, minorscale, c, t0): RAM's targets, D <= 8 (7 is reserved)
 const SAMPLER_AMWG = Int32(10)       # MuvAMWG(σ) with RobertsRosenthalMCTuner: the logistic target up to 16 parameters or a CustomTarget's whole-vector closure, D <= 32 (9 is reserved)
+const SAMPLER_MH_COV = Int32(12)     # MH(Σ::Matrix) with a Σ that is not diagonal: AMWG's targets, D <= 32, one factor for the job (11 is reserved)
 const TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = Int32(0), Int32(1), Int32(2), Int32(3), Int32(4)
 const TUNER_VANILLA, TUNER_ACCEPT_RATE, TUNER_DUAL_AVERAGING = Int32(0), Int32(1), Int32(2)
 const TUNER_ROBERTS_ROSENTHAL = Int32(3)      # RobertsRosenthalMCTuner(targetrate, period): MuvAMWG only
@@ -75,7 +76,7 @@ struct KlaraDesc
     sampler::Int32; target::Int32; tuner::Int32; tuner_mode::Int32
     nchains::Int64; chain_offset::Int64; ndims::Int32; device::Int32
     mh_sigma::Ptr{Float64}; driftstep::Float64; leapstep::Float64
-    nleaps::Int32; slice_stepout::Int32; slice_widths::Ptr{Float64}; amwg_logsigma0::Ptr{Float64}
+    nleaps::Int32; slice_stepout::Int32; slice_widths::Ptr{Float64}; amwg_logsigma0::Ptr{Float64}; mh_factor::Ptr{Float64}
     targetrate::Float64; score_k::Float64; period::Int32; verbose::Int32
     da_nadapt::Int64; da_eps0bar::Float64; da_h0bar::Float64; da_gamma::Float64; da_kappa::Float64
     da_t0::Int32; tuner_score::Int32
@@ -101,7 +102,7 @@ end
 function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_VANILLA, tuner_mode=TUNE_PER_CHAIN,
                     nchains=1, chain_offset=0, ndims=1, device=0,
                     mh_sigma=Ptr{Float64}(C_NULL), driftstep=1.0, leapstep=0.1, nleaps=10, slice_stepout=1, slice_widths=Ptr{Float64}(C_NULL),
-                    amwg_logsigma0=Ptr{Float64}(C_NULL),
+                    amwg_logsigma0=Ptr{Float64}(C_NULL), mh_factor=Ptr{Float64}(C_NULL),
                     targetrate=0.0, score_k=7.0, period=100, verbose=0,
                     da_nadapt=0, da_eps0bar=1.0, da_h0bar=0.0, da_gamma=0.05, da_kappa=0.75, da_t0=10, tuner_score=0,
                     nsteps=100, burnin=0, thinning=1,
@@ -121,7 +122,7 @@ function klara_desc(; sampler=SAMPLER_MH, target=TARGET_GAUSS_DIAG, tuner=TUNER_
               sampler, target, tuner, tuner_mode,
               nchains, chain_offset, ndims, device,
               mh_sigma, driftstep, leapstep,
-              nleaps, slice_stepout, slice_widths, amwg_logsigma0,
+              nleaps, slice_stepout, slice_widths, amwg_logsigma0, mh_factor,
               targetrate, score_k, period, verbose,
               da_nadapt, da_eps0bar, da_h0bar, da_gamma, da_kappa,
               da_t0, tuner_score,
@@ -225,6 +226,25 @@ end
 
 rowmajor(A::Matrix{Float64}) = collect(transpose(A))       # Julia is column-major, the C ABI row-major
 
+# the lower Cholesky factor L of a symmetric positive definite matrix, A = L L' (plain loops: the same text on every Julia version)
+function lowerfactor(A::Matrix{Float64})
+    n = size(A, 1)
+    size(A, 2) == n || error("MH: the proposal covariance must be a square matrix")
+    Lf = zeros(n, n)
+    for j in 1:n
+        s = A[j, j]
+        for k in 1:j-1; s -= Lf[j, k]^2; end
+        (s > 0 && isfinite(s)) || error("MH: the proposal covariance must be positive definite")
+        Lf[j, j] = sqrt(s)
+        for i in j+1:n
+            a = A[i, j]
+            for k in 1:j-1; a -= Lf[i, k] * Lf[j, k]; end
+            Lf[i, j] = a / Lf[j, j]
+        end
+    end
+    Lf
+end
+
 # Klara's structs -> klara_desc.  Field names read from Klara (file:line in /root/reference/src):
 #   MALA.driftstep                         samplers/MALA.jl:61-70
 #   SMMALA.driftstep, .transform (nothing or SoftAbs(a)) samplers/SMMALA.jl:127-137
@@ -309,11 +329,17 @@ function HIPMCJob(parameter::HIPParameter, sampler, mcrange, v0::Dict;
         kw[:sampler] = SAMPLER_SLICE; kw[:slice_widths] = pointer(w); kw[:slice_stepout] = Int32(sampler.stepout)
     elseif isa(sampler, MH)
         (sampler.symmetric && sampler.normalised) || error("only the symmetric normalised random-walk MH(sigma) runs on the device (iterate/MH.jl:72-124)")
-        prop = sampler.setproposal(BasicContMuvParameterState(zeros(D)))    # MvNormal(x, sigma): its variances give sigma
-        sig = sqrt.(Distributions.var(prop)); push!(keep, sig)
-        kw[:sampler] = SAMPLER_MH; kw[:mh_sigma] = pointer(sig)
+        prop = sampler.setproposal(BasicContMuvParameterState(zeros(D)))    # MvNormal(x, sigma) or MvNormal(x, Σ): its covariance says which (MH.jl:63-66)
+        Sigma = convert(Matrix{Float64}, Distributions.cov(prop))
+        if all(i == j || Sigma[i, j] == 0 for i in 1:D, j in 1:D)           # diagonal: MH(sigma), the variances give sigma
+            sig = sqrt.(Distributions.var(prop)); push!(keep, sig)
+            kw[:sampler] = SAMPLER_MH; kw[:mh_sigma] = pointer(sig)
+        else                                                                # MH(Σ): the lower factor, Σ = L L'; off-diagonals are never dropped
+            Lf = rowmajor(lowerfactor(Sigma)); push!(keep, Lf)
+            kw[:sampler] = SAMPLER_MH_COV; kw[:mh_factor] = pointer(Lf)
+        end
     else
-        error("sampler $(typeof(sampler)) is not on the device path (MH, RAM, AM, MuvAMWG, MALA, SMMALA, HMC, SliceSampler are)")
+        error("sampler $(typeof(sampler)) is not on the device path (MH with a vector or a matrix, RAM, AM, MuvAMWG, MALA, SMMALA, HMC, SliceSampler are)")
     end
     # --- tuner
     tn = tuner === nothing ? (isa(sampler, MuvAMWG) ? RobertsRosenthalMCTuner() : VanillaMCTuner()) : tuner
@@ -456,6 +482,21 @@ function show(io::IO, job::HIPMCJob)                     # BasicMCJob.jl:281-295
     print(io, "\n  "); show(io, job.sampler)
     print(io, "\n  "); show(io, job.tuner)
     print(io, "\n  "); show(io, job.range)
+end
+
+# mhfactor(job): the lower factor L of an MH(Σ) job's proposal covariance as it stands, Σ = L L' (the job's own, or what setmhfactor! gave)
+function mhfactor(job::HIPMCJob)
+    Lt = newarray(Float64, job.ndims, job.ndims)                    # row-major D x D == the transpose, column-major
+    check(ccall((:klara_get_mh_factor, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), job.handle, Lt), "klara_get_mh_factor")
+    collect(transpose(Lt))
+end
+
+# setmhfactor!(job, L): a new lower factor for an MH(Σ) job, in effect from the next transition — an adaptation step, which belongs before the samples that
+# are kept; reset(job) puts the job's own factor back
+function setmhfactor!(job::HIPMCJob, Lf::Matrix{Float64})
+    size(Lf) == (job.ndims, job.ndims) || error("setmhfactor!: the factor must be D x D")
+    check(ccall((:klara_set_mh_factor, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), job.handle, rowmajor(Lf)), "klara_set_mh_factor")
+    job
 end
 
 # amstate(job): (C, lastmean, secondlastmean, fallbacks) of an AM job — C[:, :, c] is chain c's current covariance (sstate.C of iterate/AM.jl:87-91),

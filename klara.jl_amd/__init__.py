@@ -8,7 +8,7 @@ from ._lib import KlaraError  # noqa: F401
 from .engine import CustomTarget, Derived, Engine, GaussDenseTarget, GaussDiagTarget, HierNormalTarget, LogisticTarget, Marginals, check_derived, histogram_quantiles  # noqa: F401
 from .api import (  # noqa: F401
     AM, AMWG, HMC, MALA, MH, MuvAMWG, RAM, RobertsRosenthalMCTuner, SMMALA, SoftAbs, AcceptanceRateMCTuner, DualAveragingMCTuner, DiffOptions, BasicContMuvParameter, BasicMCJob, BasicMCRange, GenericModel,
-    MuvChains, SliceSampler, VanillaMCTuner, acceptance, chain_ess, chain_iact, chain_mcvar, erf_rate_score, likelihood_model, logistic, logistic_rate_score,
+    MuvChains, SliceSampler, VanillaMCTuner, rwm_factor, acceptance, chain_ess, chain_iact, chain_mcvar, erf_rate_score, likelihood_model, logistic, logistic_rate_score,
     mcvar_iid, mean, output, reset, run, chain_lzv, chain_qzv, lzv, qzv, pooled_cov, pooled_cor, rhat, pooled_hist, pooled_quantiles, pooled_ess, pooled_iact,
     derived_mean, derived_var, derived_rhat, derived_quantiles,
 )

@@ -25,6 +25,7 @@ SAMPLER_MH, SAMPLER_MALA, SAMPLER_HMC, SAMPLER_SLICE, SAMPLER_SMMALA = range(5)
 SAMPLER_RAM = 6                   # (5 is reserved: the library refuses it)
 SAMPLER_AM = 8                    # (7 is reserved too)
 SAMPLER_AMWG = 10                 # (and 9)
+SAMPLER_MH_COV = 12               # (and 11) MH(Σ::Matrix): random-walk MH with a full proposal covariance
 # klara_target
 TARGET_GAUSS_DIAG, TARGET_GAUSS_DENSE, TARGET_LOGISTIC, TARGET_HIER_NORMAL, TARGET_CUSTOM = range(5)
 # klara_tuner / mode
@@ -52,7 +53,7 @@ class KlaraDesc(C.Structure):
         ("sampler", C.c_int32), ("target", C.c_int32), ("tuner", C.c_int32), ("tuner_mode", C.c_int32),
         ("nchains", C.c_int64), ("chain_offset", C.c_int64), ("ndims", C.c_int32), ("device", C.c_int32),
         ("mh_sigma", _dp), ("driftstep", C.c_double), ("leapstep", C.c_double),
-        ("nleaps", C.c_int32), ("slice_stepout", C.c_int32), ("slice_widths", _dp), ("amwg_logsigma0", _dp),
+        ("nleaps", C.c_int32), ("slice_stepout", C.c_int32), ("slice_widths", _dp), ("amwg_logsigma0", _dp), ("mh_factor", _dp),
         ("targetrate", C.c_double), ("score_k", C.c_double), ("period", C.c_int32), ("verbose", C.c_int32),
         ("da_nadapt", C.c_int64), ("da_eps0bar", C.c_double), ("da_h0bar", C.c_double), ("da_gamma", C.c_double),
         ("da_kappa", C.c_double), ("da_t0", C.c_int32), ("tuner_score", C.c_int32),
@@ -93,7 +94,7 @@ EXPORTS = [
     "klara_create", "klara_destroy", "klara_set_state", "klara_init_state_normal", "klara_run",
     "klara_run_async", "klara_synchronize", "klara_reset", "klara_stream_key", "klara_get_state", "klara_get_accept_mask", "klara_get_accept_rows",
     "klara_get_accept_counts", "klara_get_chain_sums", "klara_get_pooled_summaries", "klara_get_chain",
-    "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_get_ram_factor", "klara_set_ram_factor", "klara_get_am_state", "klara_get_amwg_state", "klara_set_amwg_logsigma", "klara_get_amwg_accept_mask", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
+    "klara_get_chain_fields", "klara_get_chain_likelihood_prior", "klara_get_chain_mcvar", "klara_get_chain_mcvar_ipse", "klara_get_chain_zv", "klara_get_chain_zv_series", "klara_get_chain_zv_one", "klara_get_chain_acov_mcvar", "klara_saved_steps", "klara_get_chain_bm", "klara_get_tune", "klara_get_dual_averaging", "klara_get_ram_factor", "klara_set_ram_factor", "klara_get_am_state", "klara_get_amwg_state", "klara_set_amwg_logsigma", "klara_get_amwg_accept_mask", "klara_get_mh_factor", "klara_set_mh_factor", "klara_last_run_ms", "klara_device_ptrs", "klara_get_layout", "klara_get_launch_modes", "klara_get_kernel_attributes", "klara_get_shader_clock",
     "klara_selftest_rocrand_blocks", "klara_selftest_math", "klara_selftest_normal_tail", "klara_selftest_transition_normals", "klara_selftest_mfma_f64", "klara_selftest_mfma_f64_4x4x4", "klara_selftest_chain_stats", "klara_selftest_pooled", "klara_strerror",
     "klara_comm_unique_id", "klara_comm_init", "klara_comm_info", "klara_comm_destroy", "klara_gather_summaries", "klara_gather_moments", "klara_gather_covariance", "klara_selftest_covariance",
     "klara_gather_rhat", "klara_selftest_rhat",
@@ -148,6 +149,8 @@ def load() -> C.CDLL:
         "klara_get_amwg_state": [H, C.c_void_p, C.c_void_p, C.c_void_p],
         "klara_set_amwg_logsigma": [H, C.c_void_p],
         "klara_get_amwg_accept_mask": [H, C.c_void_p, C.c_int64, i64p],
+        "klara_get_mh_factor": [H, C.c_void_p],
+        "klara_set_mh_factor": [H, C.c_void_p],
         "klara_last_run_ms": [H, C.POINTER(C.c_double), i64p],
         "klara_device_ptrs": [H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)],
         "klara_get_layout": [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],

@@ -52,13 +52,50 @@ class MCSampler:
 
 
 class MH(MCSampler):
-    """MH(sigma::Vector): symmetric, normalised MvNormal(x, sigma) random walk — MH.jl:63-66."""
+    """MH(sigma::Real) / MH(sigma::Vector) / MH(Σ::Matrix): symmetric, normalised MvNormal(x, ·) random walk — MH.jl:63-66.  As in Distributions a
+    number or a vector holds standard deviations and a matrix holds the covariance, so MH(np.diag(sigma**2)) is MH(sigma).  The matrix form proposes
+    x + L z with L = cholesky(Σ), one factor for the whole job (`cov`, `factor`; BasicMCJob.engine.mh_factor() / set_mh_factor()); on the device for
+    the logistic regression up to 16 parameters and user-defined whole-vector targets with D <= 32.  rwm_factor(cov) gives the factor of the
+    classical (2.38² / D) Σ̂ from a pilot run's pooled_cov."""
 
     def __init__(self, sigma):
-        self.sigma = np.atleast_1d(np.asarray(sigma, dtype=np.float64)).copy()
+        a = np.asarray(sigma, dtype=np.float64)
         self.symmetric, self.normalised = True, True
+        if a.ndim == 2:                                          # MH(σ::Matrix{N}) = MH(x -> MvNormal(x, σ))
+            assert a.shape[0] == a.shape[1], "MH: the proposal covariance must be a square matrix"
+            assert np.allclose(a, a.T, rtol=1e-12, atol=0.0), "MH: the proposal covariance must be symmetric"
+            try:
+                f = np.linalg.cholesky(a)
+            except np.linalg.LinAlgError:
+                f = None
+            assert f is not None and np.all(np.isfinite(f)), "MH: the proposal covariance must be positive definite"
+            self.cov, self.factor, self.kind = a.copy(), f, L.SAMPLER_MH_COV
+        else:
+            self.sigma = np.atleast_1d(a).copy()
+
+    @classmethod
+    def from_factor(cls, factor):
+        """MH(Σ) from a lower factor the caller already holds (Σ = L L'; the lower triangle is read, its diagonal must be positive)"""
+        f = np.asarray(factor, dtype=np.float64)
+        assert f.ndim == 2 and f.shape[0] == f.shape[1], "MH.from_factor: the factor must be a square matrix"
+        f = np.tril(f)
+        assert np.all(np.isfinite(f)) and np.all(np.diag(f) > 0), "MH.from_factor: the factor needs finite entries and a positive diagonal"
+        s = cls.__new__(cls)
+        s.symmetric, s.normalised = True, True
+        s.cov, s.factor, s.kind = f @ f.T, f.copy(), L.SAMPLER_MH_COV
+        return s
 
     kind = L.SAMPLER_MH
+
+
+def rwm_factor(cov, scale=None) -> np.ndarray:
+    """cholesky(scale · cov), scale = 2.38² / D by default: the factor of the random-walk Metropolis proposal that is optimal for a Gaussian target
+    of covariance `cov` (Gelman, Roberts and Gilks 1996; Roberts and Rosenthal 2001) — for MH.from_factor or Engine.set_mh_factor."""
+    c = np.asarray(cov, dtype=np.float64)
+    assert c.ndim == 2 and c.shape[0] == c.shape[1], "rwm_factor: the covariance must be a square matrix"
+    s = 2.38 ** 2 / c.shape[0] if scale is None else float(scale)
+    assert s > 0, "rwm_factor: the scale must be positive"
+    return np.linalg.cholesky(s * c)
 
 
 class MALA(MCSampler):
@@ -749,7 +786,11 @@ class BasicMCJob:
                   acov_maxlag=int(acov_maxlag), sparse_moves=int(sparse_moves), marginals=marginals, derived=derived,
                   hist_ring_cols=int(self.outopts["chunk"]) if self.outopts["destination"] == "iostream" else 0)
         self.bm_batchlen, self.acov_maxlag = int(bm_batchlen), int(acov_maxlag)
-        if isinstance(sampler, MH):
+        if isinstance(sampler, MH) and sampler.kind == L.SAMPLER_MH_COV:               # MH.jl:63-66, the matrix form; the tuner only counts, as for MH
+            if not isinstance(self.tuner, VanillaMCTuner):
+                raise NotImplementedError("MH(Σ) is not tuned: only VanillaMCTuner (which counts proposals when verbose) is accepted")
+            kw["mh_factor"] = sampler.factor
+        elif isinstance(sampler, MH):
             kw["mh_sigma"] = sampler.sigma
         elif isinstance(sampler, (MALA, SMMALA)):
             kw["driftstep"] = sampler.driftstep

@@ -4,6 +4,20 @@
 
 std::string pair_as_whole_source(const char* src) { return std::string("#define KLARA_PAIR_AS_WHOLE 1\n") + src; }
 
+bool pack_mh_factor(const double* L, int D, std::vector<double>& tri)
+{
+    tri.assign(KLARA_MHCOV_TRI + 16, 0.0);      // (16 doubles behind the triangle: a scalar load of 16 dwords that starts at its last entries stays inside the array)
+    for (int i = 0; i < 32; ++i) tri[(size_t)i * (i + 1) / 2 + i] = 1.0;
+    for (int i = 0; i < D && i < 32; ++i) {
+        if (!(L[(size_t)i * D + i] > 0.0)) return false;
+        for (int k = 0; k <= i; ++k) {
+            if (!std::isfinite(L[(size_t)i * D + k])) return false;
+            tri[(size_t)i * (i + 1) / 2 + k] = L[(size_t)i * D + k];
+        }
+    }
+    return true;
+}
+
 static klara_status validate_fields(const klara_desc* d)
 {
     if (!d) return KLARA_ERR_INVALID_ARG;
@@ -69,6 +83,14 @@ static klara_status validate_fields(const klara_desc* d)
         if (d->tuner != KLARA_TUNER_ROBERTS_ROSENTHAL || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
         if (!(d->targetrate > 0.0 && d->targetrate < 1.0) || d->period > 0x7fffffff) return KLARA_ERR_INVALID_ARG;
         break;
+    case KLARA_SAMPLER_MH_COV: {                                 // MH.jl:63-66, the matrix form: the factor of Σ; mh_sigma is not read
+        if (!d->mh_factor) return KLARA_ERR_INVALID_ARG;
+        std::vector<double> tri;
+        if (d->ndims <= 32 && !pack_mh_factor(d->mh_factor, d->ndims, tri)) return KLARA_ERR_INVALID_ARG;     // (beyond: KLARA_ERR_UNSUPPORTED from the planner, whatever the factor)
+        // the tuner only counts proposals, as for MH: VanillaMCTuner, per chain
+        if (d->tuner != KLARA_TUNER_VANILLA || d->tuner_mode != KLARA_TUNE_PER_CHAIN) return KLARA_ERR_UNSUPPORTED;
+        break;
+    }
     default:                                                     // SliceSampler.jl:27
         if (!d->slice_widths) return KLARA_ERR_INVALID_ARG;
         for (int i = 0; i < d->ndims; ++i) if (!(d->slice_widths[i] > 0.0)) return KLARA_ERR_INVALID_ARG;
@@ -95,6 +117,7 @@ static klara_status validate_fields(const klara_desc* d)
     if (d->sampler != KLARA_SAMPLER_RAM && (d->ram_S0 != nullptr || d->ram_targetrate != 0.0 || d->ram_gamma != 0.0)) return KLARA_ERR_INVALID_ARG;
     if (d->sampler != KLARA_SAMPLER_AMWG && d->amwg_logsigma0 != nullptr) return KLARA_ERR_INVALID_ARG;
     if (d->sampler != KLARA_SAMPLER_AMWG && d->tuner == KLARA_TUNER_ROBERTS_ROSENTHAL) return KLARA_ERR_UNSUPPORTED;
+    if (d->sampler != KLARA_SAMPLER_MH_COV && d->mh_factor != nullptr) return KLARA_ERR_INVALID_ARG;
     if (d->sampler != KLARA_SAMPLER_AM && (d->am_C0 != nullptr || d->am_corescale != 0.0 || d->am_minorscale != 0.0 || d->am_c != 0.0 || d->am_t0 != 0))
         return KLARA_ERR_INVALID_ARG;
     // pooled marginal histograms: 0 = off and no pointers; 1 .. KLARA_MARG_MAX_BINS with finite lo[d] < hi[d]
@@ -418,6 +441,10 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
         HIPCHK(mem.alloc(&h->amwg_logsig, D * N)); HIPCHK(mem.alloc(&h->amwg_acc, D * N)); HIPCHK(mem.alloc(&h->amwg_nacc, D * N));
         if (desc->monitor & KLARA_MON_ACCEPT) HIPCHK(mem.alloc(&h->amwg_mask, (size_t)desc->nsteps * N));
     }
+    if (desc->sampler == KLARA_SAMPLER_MH_COV) {                 // one triangle for the job (validated above)
+        (void)pack_mh_factor(desc->mh_factor, (int)D, h->mh_factor0);
+        KCHK(upload(mem, &h->mh_factor, h->mh_factor0.data(), h->mh_factor0.size()));
+    }
     if (desc->target == KLARA_TARGET_GAUSS_DIAG) {
         if (desc->gauss_w) KCHK(upload(mem, &h->gw, desc->gauss_w, D));
         if (desc->gauss_mu) KCHK(upload(mem, &h->gmu, desc->gauss_mu, D));
@@ -454,7 +481,7 @@ static klara_status create_impl(const klara_desc* desc, const KlaraPlan& plan, k
     // the descriptor's host pointers are not retained
     h->d.mh_sigma = nullptr; h->d.slice_widths = nullptr; h->d.gauss_w = nullptr; h->d.gauss_mu = nullptr;
     h->d.gauss_prec = nullptr; h->d.logit_X = nullptr; h->d.logit_y = nullptr; h->d.hier_Y = nullptr; h->d.hier_xc = nullptr; h->d.stream = nullptr;
-    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.am_C0 = nullptr; h->d.amwg_logsigma0 = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
+    h->d.custom_src = nullptr; h->d.custom_data = nullptr; h->d.ram_S0 = nullptr; h->d.am_C0 = nullptr; h->d.amwg_logsigma0 = nullptr; h->d.mh_factor = nullptr; h->d.marg_lo = nullptr; h->d.marg_hi = nullptr;
     h->d.derived_src = nullptr; h->d.derived_data = nullptr; h->d.derived_lo = nullptr; h->d.derived_hi = nullptr;
     {   // static kernel parameters live in device memory (read with scalar loads at the point of use)
         const KParams hp = make_params(h);
@@ -553,6 +580,7 @@ KParams make_params(klara_handle* h)
     p.am_corescale = d.am_corescale; p.am_sqrtminor = std::sqrt(d.am_minorscale); p.am_w1 = 1.0 - d.am_c; p.am_t0 = d.am_t0;     // AM.jl:235-236: sqrtminorscale, w = [1 - c, c]
     p.amwg_logsig = (decltype(p.amwg_logsig))h->amwg_logsig; p.amwg_acc = (decltype(p.amwg_acc))h->amwg_acc; p.amwg_nacc = (decltype(p.amwg_nacc))h->amwg_nacc;
     p.amwg_mask = (decltype(p.amwg_mask))h->amwg_mask;
+    p.mh_factor = (decltype(p.mh_factor))h->mh_factor;
     return p;
 }
 

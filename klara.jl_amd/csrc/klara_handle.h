@@ -98,6 +98,9 @@ struct klara_handle {
     // AMWG: the chains' log proposal scales, window counts and accepted proposals per coordinate (D planes of nchains each, KParams::amwg_*), the D scales of
     // klara_desc.amwg_logsigma0 they restart from, the coordinate masks of the transitions (KLARA_MON_ACCEPT: nsteps x nchains)
     double *amwg_logsig = nullptr, *amwg_logsig0 = nullptr; int* amwg_acc = nullptr; unsigned long long* amwg_nacc = nullptr; uint32_t* amwg_mask = nullptr;
+    // MH(Σ) (KLARA_SAMPLER_MH_COV): the job's proposal factor as the kernels read it (KParams::mh_factor, KLARA_MHCOV_TRI doubles), and the packed triangle of
+    // klara_desc.mh_factor that klara_reset puts back
+    double* mh_factor = nullptr; std::vector<double> mh_factor0;
     // streaming batch means (bm_batchlen > 0): running sum at the last batch boundary, Welford mean / M2 of the batch means
     double *bm_prev = nullptr, *bm_mean = nullptr, *bm_m2 = nullptr; long long bm_count = 0;
     KParams* d_params = nullptr;    // device copy of the handle's static kernel parameters
@@ -131,6 +134,9 @@ struct klara_handle {
 klara_status validate(const klara_desc* d);                 // every check a descriptor can fail without a device
 std::string pair_as_whole_source(const char* src);
 KParams make_params(klara_handle* h);
+// MH(Σ): the D x D row-major factor L (its lower triangle) as KParams::mh_factor holds it — packed by rows, the rows from D on the identity's; false where a
+// read entry is not finite or a diagonal entry is not positive
+bool pack_mh_factor(const double* L, int D, std::vector<double>& tri);
 
 // ---- klara_run.hip
 void part_range(const klara_handle* h, int nparts, int j, long long* c0, long long* c1);

@@ -98,6 +98,15 @@ typedef KGLOBAL long long glong;
 typedef KGLOBAL unsigned long long gulong;
 typedef KGLOBAL uint8_t guchar;
 typedef KGLOBAL int gint;
+// Memory no kernel writes (the host fills it between launches), read through the constant address space: a load whose address is the same on every lane is
+// then a scalar load whatever the kernel stores elsewhere — through a global pointer the compiler has to prove that first, and falls back to a vector load
+// per lane where it cannot.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const __attribute__((address_space(4))) double cdouble;
+#else
+typedef const double cdouble;
+#endif
+#define KLARA_MHCOV_TRI (32 * 33 / 2)      // doubles of KParams::mh_factor: the packed lower triangle of 32 rows
 
 // A device-detected error (non-finite start, slice sampler stuck).  The flag is a word of host memory mapped into the device's address
 // space (klara_create.hip): klara_synchronize then reads it without a copy command; a plain store is all a PCIe write offers (no fetch-max), and
@@ -157,6 +166,9 @@ struct KParams {
     // per coordinate of the windows closed since the start state, likewise; the coordinate masks, [transition][nchains], or null (KLARA_MON_ACCEPT).  The tuner's period and
     // target rate are `period` and `targetrate` above.
     gdouble* amwg_logsig; gint* amwg_acc; gulong* amwg_nacc; KGLOBAL uint32_t* amwg_mask;     // (amwg_nacc: the closed windows; the open one is amwg_acc)
+    // MH(Σ) (KLARA_SAMPLER_MH_COV): the job's proposal factor, one packed lower triangle by rows (entry L_ik, k <= i, at i (i + 1) / 2 + k: an index that
+    // does not depend on D) of KLARA_MHCOV_TRI doubles, the rows D <= i < 32 holding the identity; written by the host between launches only
+    const gdouble* mh_factor;
 };
 
 // Per-launch values, passed by value.  Everything else (KParams) is static for a handle and lives in device memory:
@@ -945,6 +957,60 @@ template <> struct SamplerOf<KLARA_SAMPLER_MH> : SamplerDefaults {
     static constexpr bool VECPARAM = true;
     template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
     static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>&) { return step_mh<T, E, COMMIT>(p, tg, cx, gchain, t, z, ad, vp, cur.x, cur.lt, prop); }
+};
+
+// MH(Σ::Matrix) — samplers/MH.jl:63-66 with iterate/MH.jl:72-124: step_mh with the proposal x + L z, L the job's lower factor of Σ (KParams::mh_factor), in
+// RAM's order R1 (w_i = L_i0 z_0, then + L_ik z_k, k ascending).  One chain per lane.  No lane keeps the triangle: entry (i, k) is
+// read where it is used, at an address that is the same on every lane and a constant once the loops are unrolled, so it arrives in scalar registers and is
+// the scalar operand of the multiplication (E = 32: 528 entries, 1,056 vector registers if a lane held them as RAM's lanes hold S).  The rows D <= i < E
+// hold the identity (z is zero there, so w is: no bit depends on E); beyond E = 8 the rows are taken in blocks of eight and a block that lies wholly in the
+// padding is skipped — D = 17 at E = 32 pays for 24 rows, not 32.
+template <class T, int E, bool COMMIT = true>
+__device__ __forceinline__ bool step_mhcov(const KParams& p, const T& tg, const LaneCtx<E>& cx,
+                                           unsigned long long gchain, unsigned long long t,
+                                           const double (&z)[E], const AccDraw& ad,
+                                           double (&x)[E], double& lt, Proposal<E>& prop)
+{
+    double xp[E], gd[E], red[1];
+    cdouble* const Lf = (cdouble*)p.mh_factor;
+    const int D = p.D;
+KLARA_PRAGMA_UNROLL_E
+    for (int i = 0; i < E; ++i) {
+        double a = 0.0;
+        if (E <= 8 || (i & ~7) < D) {                                                 // (uniform: D is the job's)
+            a = Lf[i * (i + 1) / 2] * z[0];                                           // C1: k ascending, a multiplication and an addition each
+KLARA_PRAGMA_UNROLL_E
+            for (int k = 1; k <= i; ++k) a = a + Lf[i * (i + 1) / 2 + k] * z[k];
+        }
+        xp[i] = x[i] + a;                                                             // MH.jl:79 with MvNormal(x, Σ)
+    }
+    tg.template eval<true, false>(cx, xp, red[0], gd);                                // :81
+    group_allreduce<1>(red, cx.G, cx.lane);
+    const double ltp = tg.finalize(red[0]);
+    const double ratio = ltp - lt;                                                    // :83
+    bool acc = ratio > 0.0;                                                           // :97
+    acc = accept_log_test<E>(p, cx, gchain, t, ad, acc, ratio);
+    if (!COMMIT) {
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) prop.x[e] = xp[e];
+        prop.lt = ltp;
+    } else if (acc) {                                                                 // :98-100
+KLARA_PRAGMA_UNROLL_E
+        for (int e = 0; e < E; ++e) x[e] = xp[e];
+        lt = ltp;
+    }
+    return acc;
+}
+
+template <> struct SamplerOf<KLARA_SAMPLER_MH_COV> : SamplerDefaults {
+    static constexpr bool built_in(int TARGET, int E) { return TARGET == KLARA_TARGET_LOGISTIC && E <= 16; }
+    // MH's figures, but for the counting kernel of the logistic target at E = 2: asked for three wavefronts per SIMD it spills 64 B (as MH's own does), at two it
+    // takes no scratch — no MH(Σ) kernel uses any (DESIGN.md section 2 has the table)
+    static constexpr int waves(int TARGET, int E, int GT, int MODE) { return TARGET == KLARA_TARGET_LOGISTIC && E == 2 && (MODE & 1) == 0 ? 2 : group_waves(TARGET, E, GT, MODE); }
+    // (E = 32: 4 E registers of resident sums next to x, x' and z spilled, 80 B in MODE 0 and 32 B in MODE 1 on the README closure; folded into memory, as AMWG's)
+    static constexpr bool memsums(int E) { return E >= 32; }
+    template <class T, int E, bool PLAIN, bool COMMIT, bool MONITORED>
+    static __device__ __forceinline__ bool step(KLARA_STEP_ARGS(E), State<E>&) { return step_mhcov<T, E, COMMIT>(p, tg, cx, gchain, t, z, ad, cur.x, cur.lt, prop); }
 };
 
 // iterate!(job, MALA, Multivariate) — iterate/MALA.jl:78-128

@@ -63,7 +63,7 @@ static inline int klara_autodiff_order(const char* src)
     return 0;
 }
 
-// group-layout transition kernels: one specialisation per sampler, each defined in a translation unit of its own (klara_{mh,mala,hmc,slice,smmala,ram,am,amwg}.hip)
+// group-layout transition kernels: one specialisation per sampler, each defined in a translation unit of its own (klara_{mh,mala,hmc,slice,smmala,ram,am,amwg,mhcov}.hip)
 // as launch_group<S> below; G = lanes per chain
 template <int S>
 hipError_t klara_launch_sampler(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st);
@@ -71,7 +71,8 @@ hipError_t klara_launch_sampler(const KParams* p, const KLaunch& kl, int mode, i
     template <> hipError_t klara_launch_sampler<S>(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)
 KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_MH); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_MALA); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_HMC); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_SLICE);
 KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_SMMALA); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_RAM); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_AM); KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_AMWG);
-// SMMALA's start-state kernel on the logistic target (log-target, gradient, metric check); RAM, AM and AMWG start from k_init
+KLARA_LAUNCH_SAMPLER(KLARA_SAMPLER_MH_COV);
+// SMMALA's start-state kernel on the logistic target (log-target, gradient, metric check); RAM, AM, AMWG and MH(Σ) start from k_init
 hipError_t klara_launch_smmala_init(const KParams& p, int E, dim3 grid, size_t lds, hipStream_t st);
 // dense (MFMA) kernels; NE in {8,16,25,32}
 // (Pfrag: the fragment-ordered precision matrix, followed — hasmu — by the 4 NE zero-padded entries of the mean)
@@ -228,7 +229,7 @@ static hipError_t launch_transitions(const KParams* p, const KLaunch& kl, int mo
 
 // every group-layout launcher: E = 2 and 4 for every target, 8 for all but the hierarchical one, 16 for the logistic regression alone — of those, what the
 // sampler is built for (SamplerOf<S>::built_in; anything else is hipErrorInvalidValue); G != 0 names the diagonal target's one chain per wavefront
-// (2, 64) and per half (4, 32).  (The logistic and hierarchical targets have one instantiation per E: the plan gives them G = 1 — RAM, AM and AMWG, one chain
+// (2, 64) and per half (4, 32).  (The logistic and hierarchical targets have one instantiation per E: the plan gives them G = 1 — RAM, AM, AMWG and MH(Σ), one chain
 // per lane, rely on that — so G is not looked at there.)
 template <int S>
 static hipError_t launch_group(const KParams* p, const KLaunch& kl, int mode, int target, int E, int G, dim3 grid, size_t lds, hipStream_t st)

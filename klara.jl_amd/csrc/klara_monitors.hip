@@ -812,6 +812,32 @@ extern "C" klara_status klara_get_amwg_accept_mask(klara_handle* h, uint32_t* ma
     return KLARA_OK;
 }
 
+// MH(Σ): the job's factor — one triangle for all chains, so no planes: the packed rows as KParams::mh_factor holds them
+extern "C" klara_status klara_get_mh_factor(klara_handle* h, double* Lout)
+{
+    if (!h || h->d.sampler != KLARA_SAMPLER_MH_COV) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (!Lout) return KLARA_OK;
+    std::vector<double> tri(KLARA_MHCOV_TRI);
+    HIPCHK(hipMemcpy(tri.data(), h->mh_factor, tri.size() * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t D = (size_t)h->d.ndims;
+    for (size_t i = 0; i < D; ++i)
+        for (size_t k = 0; k < D; ++k) Lout[i * D + k] = k <= i ? tri[i * (i + 1) / 2 + k] : 0.0;
+    return KLARA_OK;
+}
+
+extern "C" klara_status klara_set_mh_factor(klara_handle* h, const double* Lin)
+{
+    if (!h || !Lin || h->d.sampler != KLARA_SAMPLER_MH_COV) return KLARA_ERR_INVALID_ARG;
+    std::vector<double> tri;
+    if (!pack_mh_factor(Lin, h->d.ndims, tri)) return KLARA_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(h->d.device));
+    HIPCHK(hipStreamSynchronize(h->stream));                     // (the transitions queued so far read the factor they were queued with)
+    HIPCHK(hipMemcpy(h->mh_factor, tri.data(), tri.size() * sizeof(double), hipMemcpyHostToDevice));
+    return KLARA_OK;
+}
+
 extern "C" klara_status klara_device_ptrs(klara_handle* h, void** x, void** logtarget, void** gradlogtarget)
 {
     if (!h) return KLARA_ERR_INVALID_ARG;

@@ -67,19 +67,19 @@ struct KlaraPlan {
 
 static int cnt_predicate(const klara_desc& d)
 {
-    if (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_SLICE || d.sampler == KLARA_SAMPLER_RAM || d.sampler == KLARA_SAMPLER_AM) return d.verbose != 0;   // (iterate/RAM.jl:68, iterate/AM.jl:80: tuner.verbose)
+    if (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_SLICE || d.sampler == KLARA_SAMPLER_RAM || d.sampler == KLARA_SAMPLER_AM || d.sampler == KLARA_SAMPLER_MH_COV) return d.verbose != 0;   // (iterate/RAM.jl:68, iterate/AM.jl:80: tuner.verbose)
     if (d.sampler == KLARA_SAMPLER_AMWG) return 0;        // (its window counts are per coordinate and travel with the chain: KParams::amwg_acc; the step-size tuners' state is not used)
     return (d.tuner == KLARA_TUNER_VANILLA && d.verbose) || d.tuner == KLARA_TUNER_ACCEPT_RATE ||
            (d.tuner == KLARA_TUNER_DUAL_AVERAGING && d.verbose);
 }
 
-// per-sampler facts: the ids the library serves (0..4, 6, 8 and 10; 5, 7 and 9 are reserved), which samplers carry a gradient, and the tuner's first step
+// per-sampler facts: the ids the library serves (0..4, 6, 8, 10 and 12; 5, 7, 9 and 11 are reserved), which samplers carry a gradient, and the tuner's first step
 // (tuner_state, samplers.jl:29-45: the slice sampler has none)
-static bool sampler_valid(int s) { return (s >= KLARA_SAMPLER_MH && s <= KLARA_SAMPLER_SMMALA) || s == KLARA_SAMPLER_RAM || s == KLARA_SAMPLER_AM || s == KLARA_SAMPLER_AMWG; }
+static bool sampler_valid(int s) { return (s >= KLARA_SAMPLER_MH && s <= KLARA_SAMPLER_SMMALA) || s == KLARA_SAMPLER_RAM || s == KLARA_SAMPLER_AM || s == KLARA_SAMPLER_AMWG || s == KLARA_SAMPLER_MH_COV; }
 static bool sampler_needs_gradient(int s) { return s == KLARA_SAMPLER_MALA || s == KLARA_SAMPLER_HMC || s == KLARA_SAMPLER_SMMALA; }
 static double sampler_step0(const klara_desc& d)
 {
-    return (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_RAM || d.sampler == KLARA_SAMPLER_AM || d.sampler == KLARA_SAMPLER_AMWG) ? 1.0 : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
+    return (d.sampler == KLARA_SAMPLER_MH || d.sampler == KLARA_SAMPLER_RAM || d.sampler == KLARA_SAMPLER_AM || d.sampler == KLARA_SAMPLER_AMWG || d.sampler == KLARA_SAMPLER_MH_COV) ? 1.0 : (d.sampler == KLARA_SAMPLER_MALA || d.sampler == KLARA_SAMPLER_SMMALA) ? d.driftstep
          : d.sampler == KLARA_SAMPLER_HMC ? d.leapstep : (double)NAN;
 }
 
@@ -242,6 +242,9 @@ static bool amwg_eligible(const klara_desc& d, const KlaraOverrides& o)
     return d.ndims <= 32 && d.target == KLARA_TARGET_CUSTOM && d.custom_src != nullptr && strstr(d.custom_src, "KLARA_USER_PAIR_TARGET") == nullptr;
 }
 
+// MH(Σ) (KLARA_SAMPLER_MH_COV), one chain per lane, the job's factor read as scalars: AMWG's scope
+static bool mhcov_eligible(const klara_desc& d, const KlaraOverrides& o) { return amwg_eligible(d, o); }
+
 // kind, G, E (and a staged closure's wavefronts per workgroup) of the job as it runs (a closure-form rewrite has made it a user-defined target)
 static klara_status select_layout(const klara_desc& d, const KlaraOverrides& o, KlaraPlan& p)
 {
@@ -323,6 +326,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     if (d.sampler == KLARA_SAMPLER_RAM && !ram_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
     if (d.sampler == KLARA_SAMPLER_AM && !am_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
     if (d.sampler == KLARA_SAMPLER_AMWG && !amwg_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
+    if (d.sampler == KLARA_SAMPLER_MH_COV && !mhcov_eligible(d, o)) return KLARA_ERR_UNSUPPORTED;
     if (custom_autodiff(d) > 0 && d.custom_src != nullptr && strstr(d.custom_src, "KLARA_USER_PAIR_TARGET") != nullptr) return KLARA_ERR_UNSUPPORTED;
     if (d.target == KLARA_TARGET_LOGISTIC && !logit_mfma_eligible(d, o) && logit_beyond_rowsplit(d)) p.rewrite = KLARA_REWRITE_LOGIT_WIDE;
     else if (pair_as_whole(d, o)) p.rewrite = KLARA_REWRITE_PAIR_AS_WHOLE;
@@ -338,7 +342,7 @@ static klara_status klara_plan_job(const klara_desc& desc, const KlaraOverrides&
     if (st != KLARA_OK) return st;
     if (d.tuner_mode == KLARA_TUNE_POOLED && d.sampler == KLARA_SAMPLER_SLICE) return KLARA_ERR_UNSUPPORTED;
     if (d.sampler == KLARA_SAMPLER_SMMALA && p.G != 1) return KLARA_ERR_UNSUPPORTED;     // (one chain per lane: KLARA_CUSTOM_LANES may ask for more)
-    if ((d.sampler == KLARA_SAMPLER_RAM || d.sampler == KLARA_SAMPLER_AM || d.sampler == KLARA_SAMPLER_AMWG) && (p.G != 1 || p.kind == 5)) return KLARA_ERR_UNSUPPORTED;
+    if ((d.sampler == KLARA_SAMPLER_RAM || d.sampler == KLARA_SAMPLER_AM || d.sampler == KLARA_SAMPLER_AMWG || d.sampler == KLARA_SAMPLER_MH_COV) && (p.G != 1 || p.kind == 5)) return KLARA_ERR_UNSUPPORTED;
     // the logistic kernels keep the data rows (padded to E columns, + the responses) in LDS next to the 8 KB of math tables: up to
     // 144 KB of the CU's 160 (swiss: 200 x 5 doubles = 8 KB); beyond the 56 KB a launch gets by default the launchers raise the
     // kernel's limit, and fewer workgroups share a CU

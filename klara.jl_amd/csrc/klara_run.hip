@@ -295,6 +295,8 @@ extern "C" klara_status klara_reset(klara_handle* h, const double* x_host)
     klara_status st = put_params();
     if (st == KLARA_OK) st = x_host ? klara_set_state(h, x_host) : init_common(h);
     if (st != KLARA_OK) { h->epoch -= 1; (void)put_params(); }
+    // MH(Σ): the descriptor's factor again (klara_set_state alone keeps what klara_set_mh_factor gave: the factor is the job's, not a chain's)
+    if (st == KLARA_OK && h->mh_factor) HIPCHK(hipMemcpy(h->mh_factor, h->mh_factor0.data(), h->mh_factor0.size() * sizeof(double), hipMemcpyHostToDevice));
     return st;
 }
 
@@ -453,7 +455,7 @@ hipError_t launch_steps(klara_handle* h, const KLaunch& kl, int nparts)
     }
     if (d.target == KLARA_TARGET_CUSTOM) return klara_jit_launch(h->jit, mode, p, kl, grid_steps, P.lds, h->stream, 64 * P.custom_wpb);
     return klara_pick<KLARA_SAMPLER_MH, KLARA_SAMPLER_MALA, KLARA_SAMPLER_HMC, KLARA_SAMPLER_SLICE, KLARA_SAMPLER_SMMALA, KLARA_SAMPLER_RAM, KLARA_SAMPLER_AM,
-                      KLARA_SAMPLER_AMWG>(d.sampler, [&](auto s) {
+                      KLARA_SAMPLER_AMWG, KLARA_SAMPLER_MH_COV>(d.sampler, [&](auto s) {
         return klara_launch_sampler<decltype(s)::value>(p, kl, mode, d.target, P.E, P.G, grid_steps, P.lds, h->stream);
     });
 }

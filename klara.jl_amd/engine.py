@@ -321,7 +321,7 @@ class Engine:
                  acov_maxlag: int = 0, sparse_moves: int = 0, smmala_softabs: float = 0.0,
                  ram_S0=None, ram_targetrate: float = 0.0, ram_gamma: float = 0.0, marginals=None, derived=None,
                  am_C0=None, am_corescale: float = 0.0, am_minorscale: float = 0.0, am_c: float = 0.0, am_t0: int = 0,
-                 amwg_logsigma0=None):
+                 amwg_logsigma0=None, mh_factor=None):
         self._lib = L.load()
         self.target = target
         self.ndims = int(target.ndims)
@@ -398,6 +398,12 @@ class Engine:
         # MuvAMWG(sigma): the D initial log proposal scales (klara_desc.amwg_logsigma0; a number serves every coordinate), AMWG.jl:139-151
         if amwg_logsigma0 is not None:
             a = _f64(np.broadcast_to(_f64(amwg_logsigma0).ravel(), (self.ndims,))); keep.append(a); d.amwg_logsigma0 = _ptr(a)
+        # MH(Σ): the D x D lower factor of the proposal covariance (klara_desc.mh_factor), MH.jl:63-66
+        if mh_factor is not None:
+            a = _f64(mh_factor)
+            if a.shape != (self.ndims, self.ndims):
+                raise ValueError(f"mh_factor must be {self.ndims} x {self.ndims}, not {a.shape}")
+            keep.append(a); d.mh_factor = _ptr(a)
         # pooled marginal histograms (klara_desc.marg_lo / marg_hi / marg_nbins): a Marginals, or (nbins, lo, hi)
         self.marginals = None
         if marginals is not None:
@@ -776,6 +782,20 @@ class Engine:
         m = np.empty((n.value, self.nchains), dtype=np.uint32)
         L.check(self._lib.klara_get_amwg_accept_mask(self._h, m.ctypes.data, n.value, C.byref(n)), "klara_get_amwg_accept_mask")
         return m
+
+    def mh_factor(self) -> np.ndarray:
+        """(ndims, ndims): the MH(Σ) sampler's current proposal factor, zeros above the diagonal (klara_get_mh_factor)"""
+        f = np.empty((self.ndims, self.ndims))
+        L.check(self._lib.klara_get_mh_factor(self._h, f.ctypes.data), "klara_get_mh_factor")
+        return f
+
+    def set_mh_factor(self, factor) -> None:
+        """a new proposal factor for the MH(Σ) sampler, in effect from the next transition (klara_set_mh_factor).  An adaptation step: it belongs before
+        the samples that are kept.  reset() puts the job's own factor back."""
+        a = _f64(factor)
+        if a.shape != (self.ndims, self.ndims):
+            raise ValueError(f"the factor must be {self.ndims} x {self.ndims}, not {a.shape}")
+        L.check(self._lib.klara_set_mh_factor(self._h, a.ctypes.data), "klara_set_mh_factor")
 
     def dual_averaging(self):
         eb = np.empty(self.nchains); hb = np.empty(self.nchains)
